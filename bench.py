@@ -14,21 +14,28 @@ counted per launch.  Inputs are resident in HBM before the timed region.
 N GPUs = N independent shards of 2^20 states (weak scaling, no collective on the
 data path).
 
-Beside the headline the line carries, all measured live in this process:
-  roofline            the 2^20-state launch (36.7 MB: resident in the 256 MiB Infinity Cache, labelled so),
-                      with the plain-copy time of the same bytes as `copy_ceiling`;
+A plain run sets up, warms up, times the K steps and prints the line: the headline, `ms_per_step` and the
+roofline of the timed launches (the 2^20-state launch, 36.7 MB: resident in the 256 MiB Infinity Cache, labelled so).
+`--dump-outputs DIR` writes what the last timed launch handed its caller as DIR/*.npy (dump_outputs()).
+
+`--full` adds, all measured live in this process after the timed region:
+  parity              every state of the timed batch against the CPU reference (--parity-states);
+  roofline            with the plain-copy time of the same bytes as `copy_ceiling`;
   roofline.dram_leg   the same kernel over 2^24 states (587 MB per launch, beyond every cache) with its own
                       copy ceiling: the DRAM-true figure;
-  persistent          K = 32 random env steps per launch with the state in registers (osg_random_steps).
+  persistent          K = 32 random env steps per launch with the state in registers (osg_random_steps);
+  secondary           the MCTS / CFR / MCCFR / env-step workloads beside the headline;
+  the in-run counter passes and the CPU baseline (each of these can still be left out with its --no-* option).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with no WORLD_SIZE in the environment re-executes itself as N ranks under
 torch.distributed.run (one rank per GPU, RCCL; 127.0.0.1 rendezvous on a free port), so both command forms give
-the same line.  At N > 1 the line keeps everything the N = 1 line has (rank 0 runs the roofline legs and the CPU
-baseline while the other ranks wait on a host-side barrier) and adds per-rank rates, the collective's latency and the
-strong-scaling efficiency of the sharded search against the same run's single-rank search of all roots.
+the same line.  At N > 1 the line keeps everything the N = 1 line has and adds per-rank rates; with --full (rank 0 runs
+the roofline legs and the CPU baseline while the other ranks wait on a host-side barrier) also the collective's latency
+and the strong-scaling efficiency of the sharded search against the same run's single-rank search of all roots.
+--dump-outputs writes rank 0's shard.
 
 Prints ONE JSON line (rank 0).
 """
@@ -1468,6 +1475,29 @@ def emit(full):
     return line
 
 
+DUMP_SAMPLE = 1 << 16             # states whose successor ObservationTensor --dump-outputs writes (126 floats each)
+DUMP_FULL_STATES = 1 << 21        # up to this many states the mask and status bytes are written for every state
+
+
+def dump_outputs(torch, out_dir, dst, mask, status):
+    """--dump-outputs DIR: what the last timed launch handed its caller, as float32 .npy files — the successor legal-mask
+    bytes (mask.npy, [n, compact_mask_bytes]) and status bytes (status.npy, [n]) of every state, and the successor state
+    as its ObservationTensor(0) for a fixed sample of DUMP_SAMPLE states drawn with SEED (observation_sample.npy, with
+    their indices in sample_index.npy, float64).  Beyond DUMP_FULL_STATES states mask and status are written for the
+    sample only.  40 MiB at the default 2^20 states, under 64 MB at any --states."""
+    import numpy as np
+    n = dst.n
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(SEED).choice(n, DUMP_SAMPLE, replace=False))
+    idx_t = torch.from_numpy(idx).to(mask.device)
+    if n > DUMP_FULL_STATES:
+        mask, status = mask.index_select(0, idx_t), status.index_select(0, idx_t)
+    arrays = {"mask": mask, "status": status, "observation_sample": dst.gather(idx_t).observation_tensor(0)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1475,15 +1505,24 @@ def main():
                     help=f"timed steps; one step = {LAUNCHES_PER_STEP} launches of the fused kernel over the batch")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--states", type=int, default=STATES_PER_GPU, help="states per GPU (default 2^20)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed launch computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the parity check, the roofline legs, the secondary "
+                         "workloads, the in-run counter passes and the CPU baseline (each left out by its --no-* option)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the MCTS / CFR / MCCFR workloads")
     ap.add_argument("--no-legs", action="store_true", help="skip the DRAM-true and persistent legs")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the in-run rocprofv3 counter passes")
-    ap.add_argument("--parity-states", type=int, default=-1,
+    ap.add_argument("--parity-states", type=int, default=None,
                     help="states of rank 0's timed batch checked against the CPU reference after the timed region "
-                         "(-1: all of them, 0: none)")
+                         "(-1: all of them, 0: none; default: all of them with --full, none without)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.parity_states is None:
+        args.parity_states = -1 if args.full else 0
+    if not args.full:
+        args.no_cpu_baseline = args.no_secondary = args.no_legs = args.no_pmc = True
 
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and not args.pmc_child and (world_env is None or (world_env == "1" and "OSG_BENCH_SPAWNED" not in os.environ)):
@@ -1576,6 +1615,8 @@ def main():
     per_rank_kernel_us = gather_floats(avg_kernel_s * 1e6)
     elapsed = max(per_rank_elapsed)
     assert int((status & 0x40).sum().item()) == 0, "synthetic actions must all be legal"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, dst, mask, status)
     # parity of the TIMED launches: every state of rank 0's shard (or --parity-states of them) regenerated by the CPU
     # reference and compared with what the last timed launch wrote (the checker never runs inside the timed region)
     parity = None

@@ -5,7 +5,7 @@
 // State / LoadGame / Policy / Bot ... (open_spiel/spiel.h:301-1314, policy.h, spiel_bots.h) and
 // open_spiel::algorithms::{MCTSBot, CFRSolver, ExternalSamplingMCCFRSolver, ...}.  A program written against the
 // reference for this path compiles unchanged (tests/dropin/user_program.cc does, and so do the reference's own
-// unit-test sources: tests/native/Makefile.reftests), for the five games of the path.
+// unit-test sources: oracle/Makefile.mirror_tests), for the five games of the path.
 #ifndef OSG_INCLUDE_OPEN_SPIEL_SPIEL_H_
 #define OSG_INCLUDE_OPEN_SPIEL_SPIEL_H_
 #include <cmath>

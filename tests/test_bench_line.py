@@ -150,3 +150,41 @@ def test_profile_source_stamps_detect_a_changed_kernel(tmp_path, monkeypatch):
     (csrc / "osg_cfr_small.hip").write_text("kernel v2")
     assert ps.status("pmc_solvers")[1] == "stale: open_spiel_amd/csrc/osg_cfr_small.hip"
     assert ps.is_current("profiles/r09_pmc_solvers.json") is False and ps.is_current("profiles/other.json") is None
+
+
+class _FakeBatch:
+    """dump_outputs() reads n, gather() and observation_tensor() of the successor batch: a host stand-in."""
+
+    def __init__(self, n, fill=0.0):
+        self.n, self.fill = n, fill
+
+    def gather(self, index):
+        return _FakeBatch(int(index.numel()), self.fill)
+
+    def observation_tensor(self, player):
+        import torch
+        return torch.full((self.n, 126), self.fill)
+
+
+@pytest.mark.parametrize("n", [1 << 12, 1 << 20, 1 << 24])
+def test_dump_outputs_is_float_seeded_and_under_64_mb(n, tmp_path):
+    """--dump-outputs: float32 / float64 .npy files only, under 64 MB in all at any batch size, the same sample every run;
+    every state's mask and status bytes up to DUMP_FULL_STATES states."""
+    import numpy as np
+    import torch
+    mask = (torch.arange(n, dtype=torch.int64) % 251).to(torch.uint8).reshape(n, 1)
+    status = (torch.arange(n, dtype=torch.int64) % 7).to(torch.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(torch, str(tmp_path / d), _FakeBatch(n, 1.0), mask, status)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["mask.npy", "observation_sample.npy", "sample_index.npy", "status.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 << 20
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    idx = np.load(tmp_path / "a" / "sample_index.npy").astype(np.int64)
+    assert len(idx) == min(n, bench.DUMP_SAMPLE) and (np.diff(idx) > 0).all() and idx[-1] < n
+    m = np.load(tmp_path / "a" / "mask.npy")
+    want = np.arange(n) if n <= bench.DUMP_FULL_STATES else idx
+    assert np.array_equal(m[:, 0], (want % 251).astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), (want % 7).astype(np.float32))

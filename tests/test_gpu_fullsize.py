@@ -241,7 +241,7 @@ def test_bench_two_ranks_code_path(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-pmc", "--states", str(1 << 16)]
+           "--full", "--no-cpu-baseline", "--no-pmc", "--states", str(1 << 16)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     sys.path.insert(0, root)
@@ -269,6 +269,45 @@ def test_bench_two_ranks_code_path(tmp_path):
     assert q["world"] == 2 and q["nash_conv"] < 4.7 and q["overlapped"]["nash_conv"] < 4.7
     with open(os.path.join(root, line["detail"])) as f:
         assert json.load(f)["value"] == full["value"]
+
+
+def test_bench_plain_run_dumps_the_last_timed_launch(oracle, tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: the contract's fields and none of the
+    --full legs in the line, and what the last timed launch computed — the same in two runs of the same command, and
+    the same as the CPU oracle's record of that batch (every state: successor mask byte, status, ObservationTensor)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    n = 1 << 16
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        env = dict(os.environ, OSG_BENCH_DETAIL_DIR=str(tmp_path))
+        for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
+            env.pop(k, None)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--states", str(n), "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=300, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line, _full = bench.read_lines(r.stdout)
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "env-steps/s" and line["higher_is_better"] is True and line["dtype"] == "u64"
+        for k in ("secondary", "cpu_baseline", "persistent"):
+            assert k not in line, k
+        assert line["parity_checked_states"] == 0 and "copy_gbs" not in line["roofline"]
+        dumps.append({f: np.load(out / f"{f}.npy") for f in ("mask", "status", "observation_sample", "sample_index")})
+    a, b = dumps
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    assert np.array_equal(a["sample_index"], np.arange(n))
+    rec = oracle.Game("connect_four").synth_batch(bench.SEED, n, bench.C4_DEPTH_MOD)
+    assert np.array_equal(a["mask"][:, 0], (rec["mask1"][:, 0] & 0xFF).astype(np.float32))
+    assert np.array_equal(a["observation_sample"], rec["obs1"].astype(np.float32))
+    st = a["status"].astype(np.uint8)
+    assert np.array_equal((st & 0x80) != 0, rec["term1"] != 0) and not (st & 0x40).any()
 
 
 def test_hex9_mcts_2pow16_roots_under_full_load(oracle, ctx):

@@ -149,7 +149,7 @@ def test_bench_eight_ranks_code_path():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(WORLD), "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--no-pmc", "--states", str(1 << 16)]
+           "--full", "--no-cpu-baseline", "--no-pmc", "--states", str(1 << 16)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     import bench

@@ -1,8 +1,9 @@
 """The reference's own C++ unit tests for the hot path, run against the MI355X host mirror on the device.
 
-tests/native/Makefile.reftests compiles the reference's test SOURCES unmodified (read where they lie under
-/root/reference, never copied) against open_spiel_amd/csrc/host/osg_spiel.h + libosg_hip.so; the binaries land in
-tests/_refbuilt/ (git-ignored, shipped with the repo snapshot) and are run here.  A test passes iff the binary
+oracle/Makefile.mirror_tests (run by __graft_entry__.build()) compiles the reference's test SOURCES unmodified (read
+where they lie in the reference tree, never copied) against open_spiel_amd/csrc/host/osg_spiel.h + libosg_hip.so; the
+binaries land in oracle/_ref/mirror_tests/ (git-ignored, carried with the built tree like the rest of oracle/_ref/) and
+are run here.  A test passes iff the binary
 exits 0, i.e. every SPIEL_CHECK_* of the reference's own test held on the MI355X path:
 
 * cfr_br_test.cc (as is): CFR-BR on kuhn/leduc reaches the reference's NashConv bounds; 3-player kuhn runs.
@@ -37,8 +38,10 @@ import subprocess
 
 import pytest
 
+import reference_py
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILT = os.path.join(ROOT, "tests", "_refbuilt")
+BUILT = os.path.join(ROOT, "oracle", "_ref", "mirror_tests")
 BINARIES = ["reference_cfr_br_test", "reference_mcts_test_on_mirror", "reference_es_mccfr_test_on_mirror",
             "reference_os_mccfr_test_on_mirror", "reference_cfr_test_on_mirror", "reference_tabular_exploitability_test",
             "reference_best_response_test_on_mirror", "reference_hex_test", "reference_kuhn_poker_test",
@@ -47,17 +50,20 @@ BINARIES = ["reference_cfr_br_test", "reference_mcts_test_on_mirror", "reference
             "reference_get_legal_actions_map_test_on_mirror"]
 
 
-def _ensure_built():
-    if os.path.isdir("/root/reference/open_spiel"):
-        subprocess.check_call(["make", "-s", "-j4", "-C", os.path.join(ROOT, "tests", "native"), "-f",
-                               "Makefile.reftests"])
+def _built(binary):
+    """The binary as __graft_entry__.build() left it (the GPU tests never rebuild: the reference tree is not read here)."""
+    path = os.path.join(BUILT, binary)
+    if not os.access(path, os.X_OK):
+        pytest.fail(f"{path} missing: run __graft_entry__.build() where the reference tree exists before shipping")
+    return path
 
 
 def test_reference_test_sources_compile_against_the_mirror():
     """CPU half: where the reference tree exists, its test sources compile and link against the mirror."""
-    if not os.path.isdir("/root/reference/open_spiel"):
-        pytest.skip("no /root/reference here: the binaries are built where it exists and shipped prebuilt")
-    _ensure_built()
+    if not reference_py.sources_present():
+        pytest.skip("no reference tree here: the binaries are built where it exists and carried prebuilt")
+    subprocess.check_call(["make", "-s", "-j4", "-C", os.path.join(ROOT, "oracle"), "-f", "Makefile.mirror_tests",
+                           "REF=" + reference_py.REFERENCE_ROOT])
     for b in BINARIES + SLOW_BINARIES + [e[0] for e in EXAMPLES]:
         assert os.access(os.path.join(BUILT, b), os.X_OK), b
 
@@ -84,10 +90,7 @@ EXAMPLES = [
 @pytest.mark.gpu
 @pytest.mark.parametrize("binary,args,expect", EXAMPLES)
 def test_reference_example_program_runs_on_the_mirror(binary, args, expect):
-    _ensure_built()
-    path = os.path.join(BUILT, binary)
-    if not os.access(path, os.X_OK):
-        pytest.fail(f"{path} missing: run __graft_entry__.build() where /root/reference exists before shipping")
+    path = _built(binary)
     r = subprocess.run([path] + args, capture_output=True, text=True, timeout=600)
     print((r.stdout + r.stderr)[-1500:])
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
@@ -112,10 +115,7 @@ def test_slow_reference_unit_test_passes_on_the_mirror(binary):
 @pytest.mark.gpu
 @pytest.mark.parametrize("binary", BINARIES)
 def test_reference_unit_test_passes_on_the_mirror(binary):
-    _ensure_built()
-    path = os.path.join(BUILT, binary)
-    if not os.access(path, os.X_OK):
-        pytest.fail(f"{path} missing: run __graft_entry__.build() where /root/reference exists before shipping")
+    path = _built(binary)
     r = subprocess.run([path], capture_output=True, text=True, timeout=1200)
     print(r.stdout[-1500:])
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

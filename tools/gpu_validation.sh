@@ -7,7 +7,7 @@
 #    __graft_entry__.smoke();
 # 1. the GPU test suite (parity vs the oracle, vs the recorded outputs of the genuine reference,
 #    checkpoint interop with oracle/_ref, the world-size-1 collective);
-# 2. bench.py (one JSON line: env-steps/s + roofline + cpu_baseline of the genuine reference build);
+# 2. bench.py --full (one JSON line: env-steps/s + roofline + cpu_baseline of the genuine reference build);
 # 3. rocprofv3 --kernel-trace --stats of the same bench command (per-kernel average durations);
 # 4. two separate --pmc passes (FETCH_SIZE, WRITE_SIZE) -> tools/pmc_traffic.py.
 # Never combines --pmc with trace domains other than kernel-trace (gpurun refuses that combination).
@@ -35,7 +35,7 @@ echo "pytest exit $?" | tee -a "$OUT/summary.txt"
 tail -5 "$OUT/pytest_gpu.log" | tee -a "$OUT/summary.txt"
 
 echo "== bench.py" | tee -a "$OUT/summary.txt"
-timeout 900 python bench.py > "$OUT/bench_n1.log" 2> "$OUT/bench_n1.err"
+timeout 900 python bench.py --full > "$OUT/bench_n1.log" 2> "$OUT/bench_n1.err"
 echo "bench exit $?" | tee -a "$OUT/summary.txt"
 tail -c 3000 "$OUT/bench_n1.log" | tee -a "$OUT/summary.txt"
 
@@ -43,7 +43,7 @@ echo "== rocprofv3 --kernel-trace --stats" | tee -a "$OUT/summary.txt"
 # (OSG_CFR_PLAIN_LAUNCH=1: on ROCm 7.0.2 a process that made a COOPERATIVE launch crashes in an exit handler under
 #  rocprofv3 --kernel-trace — after the tool has written its output — tools/probe_exit_under_tracer.sh; the traced run
 #  launches the two barrier kernels with ordinary launches, same kernels, same durations)
-OSG_CFR_PLAIN_LAUNCH=1 timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -- python bench.py --no-cpu-baseline > "$OUT/trace.log" 2>&1
+OSG_CFR_PLAIN_LAUNCH=1 timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -- python bench.py --full --no-cpu-baseline > "$OUT/trace.log" 2>&1
 echo "trace exit $?" | tee -a "$OUT/summary.txt"
 DB=$(find "$OUT/trace" -name '*.db' | head -1)
 if [ -n "$DB" ]; then python tools/rocpd_summary.py "$DB" > "$OUT/kernel_stats.csv" 2>> "$OUT/trace.log"; fi
@@ -54,7 +54,7 @@ python tools/launch_timing.py "$OUT" > "$OUT/launch_timing.txt" 2>&1; cat "$OUT/
 for C in FETCH_SIZE WRITE_SIZE; do
   echo "== rocprofv3 --pmc $C" | tee -a "$OUT/summary.txt"
   timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$OUT/pmc_$C" -- \
-    python bench.py --steps 1 --warmup 1 --no-secondary --no-cpu-baseline > "$OUT/pmc_$C.log" 2>&1
+    python bench.py --steps 1 --warmup 1 --full --no-secondary --no-cpu-baseline > "$OUT/pmc_$C.log" 2>&1
   echo "pmc $C exit $?" | tee -a "$OUT/summary.txt"
 done
 python tools/pmc_traffic.py "$OUT/pmc_FETCH_SIZE" "$OUT/pmc_WRITE_SIZE" "$TAG" > "$OUT/pmc_traffic.log" 2>&1

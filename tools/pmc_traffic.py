@@ -1,5 +1,5 @@
 """Turns two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; --output-format csv) of
-`bench.py --no-secondary --no-cpu-baseline` into profiles/pmc_traffic.json and the per-counter summaries.
+`bench.py --full --no-secondary --no-cpu-baseline` into profiles/pmc_traffic.json and the per-counter summaries.
 FETCH_SIZE / WRITE_SIZE are in KB; FETCH_SIZE is doubled as MI355X_MICROARCH.md prescribes for gfx950 (the
 128-byte requests of a coalesced streaming read are tallied at 64 B).  The guide calibrated that on 16-byte-per-lane
 reads; this kernel reads 8 bytes per lane, so the same pass's plain copy kernel (k_copy16, whose bytes are known)
@@ -47,7 +47,7 @@ for states in sorted(by_grid):
             res["dram_leg"] = dram
     if states == 1 << 24:
         res["dram_leg"] = rec
-res["source"] = (f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes of bench.py --no-secondary "
+res["source"] = (f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes of bench.py --full --no-secondary "
                  f"--no-cpu-baseline), profiles/{TAG}_pmc_*_k_step_c4std.csv; FETCH_SIZE doubled per "
                  "MI355X_MICROARCH.md (gfx950 tallies the 128-byte requests of coalesced reads at 64 B; checked in "
                  "the same pass against the plain copy k_copy16, whose bytes are known)")

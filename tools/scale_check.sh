@@ -18,11 +18,11 @@ for N in 1 2 4 8; do
   [ "$N" -gt "$MAX" ] && break
   [ "$N" -gt "$HAVE" ] && break
   if [ "$N" -eq 1 ]; then
-    python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_n$N.log" 2> "$OUT/bench_n$N.err"
+    python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_n$N.log" 2> "$OUT/bench_n$N.err"
   else
     PORT=$(python3 -c "import socket; s=socket.socket(); s.bind(('127.0.0.1',0)); print(s.getsockname()[1])")
     python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "$PORT" \
-      bench.py --gpus "$N" --steps 20 --warmup 5 > "$OUT/bench_n$N.log" 2> "$OUT/bench_n$N.err"
+      bench.py --gpus "$N" --steps 20 --warmup 5 --full > "$OUT/bench_n$N.log" 2> "$OUT/bench_n$N.err"
   fi
   echo "N=$N rc=$?"
   tail -1 "$OUT/bench_n$N.log" | python3 -c "
