@@ -8,6 +8,8 @@ struct-of-arrays in HBM.  PyTorch is plumbing only (device buffers, streams,
 torch.distributed); every rule evaluation runs in libosg_hip.so.
 """
 import ctypes as C
+import os
+import warnings
 
 import numpy as np
 import torch
@@ -17,6 +19,33 @@ from ._abi import OsgError, check, lib
 
 TERMINAL_PLAYER = -4
 CHANCE_PLAYER = -1
+
+
+def _bad_tensor_message(t, dtype, numel, what, device):
+    """Why `t` is not a buffer StateBatch hands to a kernel (StateBatch._checked; the native step raises the same text)."""
+    if not isinstance(t, torch.Tensor):
+        return f"{what}: expected a torch tensor on {device}"
+    return (f"{what}: need a contiguous {dtype} tensor of {numel} elements on {device}, "
+            f"got {t.dtype} {tuple(t.shape)} on {t.device}"
+            f"{'' if t.is_contiguous() else ' (non-contiguous)'}")
+
+
+def _import_native_step():
+    """open_spiel_amd._osg_step_fast (csrc/host/osg_step_fast.cc): StateBatch.step's tensor checks and its osg_step
+    call in one native call.  None under OSG_STEP_PY=1 (an A/B switch: step() runs its Python body, _step_py), or when
+    the extension does not import; then step() runs the Python body and this warns once."""
+    if os.environ.get("OSG_STEP_PY") == "1":
+        return None
+    try:
+        from . import _osg_step_fast
+    except ImportError as e:
+        warnings.warn(f"open_spiel_amd._osg_step_fast did not import ({e}); StateBatch.step runs its Python body "
+                      "(build it with `make -C open_spiel_amd/csrc`)", RuntimeWarning)
+        return None
+    return _osg_step_fast
+
+
+_native_step = _import_native_step()
 
 
 def _ptr(t):
@@ -125,19 +154,30 @@ class StateBatch:
         h = C.c_void_p()
         check(lib().osg_batch_create(ctx._h, game_string.encode(), self.n, C.byref(h)))
         self._h = h
+        self._hraw = h.value  # the osg_batch* as an int for the native step (0 once closed)
         self.desc = _abi.GameDesc()
         check(lib().osg_batch_describe(self._h, C.byref(self.desc)))
         self.num_players = self.desc.num_players
         self.num_distinct_actions = self.desc.num_distinct_actions
+        self._cmb = self.desc.compact_mask_bytes
+        self._device_index = ctx.device.index
+        if _native_step is not None and not _native_step.bound():
+            _native_step.bind(OsgError, _bad_tensor_message, torch.uint8, torch.device,
+                              C.cast(lib().osg_step, C.c_void_p).value, C.cast(lib().osg_last_error, C.c_void_p).value)
 
     def __len__(self):
         return self.n
 
+    def close(self):
+        """Free the states now; step() on a closed batch (as source or destination) raises."""
+        if self._h:
+            lib().osg_batch_destroy(self._h)
+            self._h = None
+            self._hraw = 0
+
     def __del__(self):
         try:
-            if self._h:
-                lib().osg_batch_destroy(self._h)
-                self._h = None
+            self.close()
         except Exception:
             pass
 
@@ -148,13 +188,9 @@ class StateBatch:
         """A caller-supplied device buffer handed to a kernel by raw pointer: right dtype, on this
         context's device, contiguous, exactly `numel` elements — anything else would read or write
         out of bounds silently."""
-        if not isinstance(t, torch.Tensor):
-            raise OsgError(f"{what}: expected a torch tensor on {self.ctx.device}")
-        if t.dtype != dtype or not t.is_cuda or t.device != self.ctx.device or not t.is_contiguous() \
-                or t.numel() != numel:
-            raise OsgError(f"{what}: need a contiguous {dtype} tensor of {numel} elements on {self.ctx.device}, "
-                           f"got {t.dtype} {tuple(t.shape)} on {t.device}"
-                           f"{'' if t.is_contiguous() else ' (non-contiguous)'}")
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or t.device != self.ctx.device \
+                or not t.is_contiguous() or t.numel() != numel:
+            raise OsgError(_bad_tensor_message(t, dtype, numel, what, self.ctx.device))
         return t
 
     # -- State::Clone / reset ------------------------------------------------
@@ -316,8 +352,28 @@ class StateBatch:
         (default: in place).  Returns (mask bytes [n, compact_mask_bytes], status [n]).
         want_mask=False (hex boards of up to 128 cells): the successor's mask row is not written — on a hex
         board it is ~occupied of the successor record; returns (None, status).
+        The checks of the caller's buffers and the launch are one native call (_osg_step_fast); _step_py is the same
+        step in Python (OSG_STEP_PY=1).
         """
-        dst = dst or self
+        if _native_step is None:
+            return self._step_py(actions_u8, dst, mask, status, want_mask)
+        if dst is None:
+            dst = self
+        if not want_mask:
+            mask = None
+            if status is None:
+                status = self._dev((self.n,), torch.uint8)
+        elif mask is None or status is None:
+            mask, status = self.step_buffers()
+        _native_step.step(self._hraw, dst._hraw, self.n, dst.n, self.game_string, dst.game_string,
+                          actions_u8, mask, status, self._cmb, self._device_index)
+        return mask, status
+
+    def _step_py(self, actions_u8, dst=None, mask=None, status=None, want_mask=True):
+        if dst is None:
+            dst = self
+        if not self._h or not dst._h:
+            raise OsgError("step: the batch or its destination is closed")
         if not want_mask:
             mask = None
             if status is None:
