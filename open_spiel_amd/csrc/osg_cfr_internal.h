@@ -30,14 +30,6 @@ namespace osg_cfr_impl {
 constexpr int kMaxA = 4;        // widest decision node the MCCFR frame holds (kuhn 2, leduc 3)
 constexpr int kMaxPolicyRow = 8;  // widest policy row a thread regret-matches in registers (kuhn 2, leduc 3)
 constexpr int kMaxFrames = 24;  // traverser decision nodes on one path
-#ifndef OSG_MCCFR_FRAMES2
-#define OSG_MCCFR_FRAMES2 1     // the flat ES-MCCFR kernel keeps the two upper frames of the traverser's stack in registers (0: A/B)
-#endif
-#ifndef OSG_MCCFR_PEEK
-#define OSG_MCCFR_PEEK 0        // 1: the flat ES-MCCFR kernel forms the next draw while the node record is in flight — measured
-                                // 2.7 % SLOWER (profiles/r05_ab_solvers.txt: the draws of traverser / terminal visits are wasted
-                                // vector work on a SIMD that is already two thirds busy issuing); kept as a switch
-#endif
 constexpr double kMccfrInit = 0.000001;  // external_sampling_mccfr.h:59 kInitialTableValues
 
 enum NodeKind : uint8_t { kChanceNode = 0, kDecisionNode = 1, kTerminalNode = 2 };
@@ -272,9 +264,9 @@ OSG_HD uint64_t es_stream(int level, int b1, int b2) {
   return level == 0 ? 0u : (level == 1 ? 1u + static_cast<uint64_t>(b1) : 16u + 8u * static_cast<uint64_t>(b1) + static_cast<uint64_t>(b2));
 }
 
-#ifndef OSG_MCCFR_TREE_GLOBAL_DEFAULT
-#define OSG_MCCFR_TREE_GLOBAL_DEFAULT 1   // round 6: 3.04e9 -> 4.23e9 trajectories/s at 16 x 2^20 (profiles/r06c_mccfr_tree_in_l2_ab.txt)
-#endif
+// Where OSG_MCCFR_TREE is unset, the flat kernel's tree goes to global memory when that helps (round 6: 3.04e9 -> 4.23e9 trajectories/s at 16 x 2^20,
+// profiles/r06c_mccfr_tree_in_l2_ab.txt).
+constexpr bool kMccfrTreeGlobalDefault = true;
 struct ResidentTree {
   const uint2* rec;      // [H]
   const double* uret;    // [K, P] distinct Returns() vectors

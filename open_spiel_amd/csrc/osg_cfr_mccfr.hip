@@ -18,11 +18,6 @@ namespace {
 // of the counter streams: with the sequence the reference's std::mt19937 + uniform_real_distribution would
 // produce, one trajectory IS one UpdateRegrets call of the reference, draw for draw
 // (ExternalSamplingMCCFRSolver::RunIteration(std::mt19937*), external_sampling_mccfr.h:63-100).
-#ifdef OSG_MCCFR_DIAG_NOATOMIC   // MEASUREMENT ONLY: what the general kernel would last without its global atomics
-OSG_D void k_add_f64(double* p, double v) { *p = v; }
-#else
-OSG_D void k_add_f64(double* p, double v) { add_f64(p, v); }
-#endif
 template <bool kLdsDelta, bool kExtU = false>
 __global__ void __launch_bounds__(256)
 k_mccfr(Tree t, const double* __restrict__ regrets, double* g_dreg, double* g_dpol, uint64_t seed,
@@ -85,7 +80,7 @@ k_mccfr(Tree t, const double* __restrict__ regrets, double* g_dreg, double* g_dp
             acc += pr;
           }
           if (t.actor[node] == (trav + 1) % P)  // kSimple averaging at player+1's nodes (:177-183)
-            for (int a = 0; a < nc; ++a) k_add_f64(&dpol[i * A + a], pol[a]);
+            for (int a = 0; a < nc; ++a) add_f64(&dpol[i * A + a], pol[a]);
           node = fc + pick;
           continue;
         }
@@ -115,7 +110,7 @@ k_mccfr(Tree t, const double* __restrict__ regrets, double* g_dreg, double* g_dp
           break;
         }
         const double v = f_value[sp - 1];
-        for (int b = 0; b < nc; ++b) k_add_f64(&dreg[i * A + b], f_cv[sp - 1][b] - v);  // (:167-172)
+        for (int b = 0; b < nc; ++b) add_f64(&dreg[i * A + b], f_cv[sp - 1][b] - v);  // (:167-172)
         ret = v;
         --sp;
       }
@@ -127,8 +122,8 @@ k_mccfr(Tree t, const double* __restrict__ regrets, double* g_dreg, double* g_dp
     __syncthreads();
     for (int k = threadIdx.x; k < IA; k += blockDim.x) {
       const double r = smem[k], q = smem[IA + k];
-      if (r != 0.0) k_add_f64(&g_dreg[k], r);
-      if (q != 0.0) k_add_f64(&g_dpol[k], q);
+      if (r != 0.0) add_f64(&g_dreg[k], r);
+      if (q != 0.0) add_f64(&g_dpol[k], q);
     }
   }
 }
@@ -420,16 +415,11 @@ k_mccfr_resident_flat(int H, int I, int P, ResidentTree rt, const int32_t* __res
     // those with the same traverser (index = lane * P + w), so that the 64 lanes of a wavefront agree at every node
     // on whether they walk all actions or sample one — half the divergence of the natural order, same set of
     // trajectories.  (The last, partial group keeps the natural order.)
-#if defined(OSG_MCCFR_DIAG_COHERENT) && OSG_MCCFR_DIAG_COHERENT == 1
-    const int64_t jj = j0 & ~static_cast<int64_t>(63);   // MEASUREMENT ONLY: a wavefront's lanes all walk its first lane's trajectory (no divergence at all)
-#else
-    const int64_t jj = j0;
-#endif
-    int64_t j = jj;
+    int64_t j = j0;
     {
-      const int64_t span = 64 * static_cast<int64_t>(P), group = jj / span;
+      const int64_t span = 64 * static_cast<int64_t>(P), group = j0 / span;
       if ((group + 1) * span <= count) {
-        const int r = static_cast<int>(jj - group * span);
+        const int r = static_cast<int>(j0 - group * span);
         j = group * span + static_cast<int64_t>(r & 63) * P + (r >> 6);
       }
     }
@@ -438,12 +428,6 @@ k_mccfr_resident_flat(int H, int I, int P, ResidentTree rt, const int32_t* __res
     const int trav = P == 2 ? static_cast<int>(g & 1) : static_cast<int>(g % P);
     const int next = trav + 1 == P ? 0 : trav + 1;
     Rng rng(seed, static_cast<uint64_t>(g), 0);
-#if defined(OSG_MCCFR_DIAG_COHERENT) && OSG_MCCFR_DIAG_COHERENT == 2
-    // MEASUREMENT ONLY: the first two draws of a trajectory (leduc: the two private cards) are the wavefront's, the rest
-    // its own — what sorting the trajectories by their deal would give a wavefront
-    Rng rng_w(seed, static_cast<uint64_t>(first + (j0 & ~static_cast<int64_t>(63))), 0);
-    int diag_draws = 0;
-#endif
     const uint64_t s0 = rng.s;   // the sub-streams of the traverser's first two levels are jumps of this counter (es_stream)
     int b1 = 0;
     // backing store of the frames below the top one
@@ -454,7 +438,6 @@ k_mccfr_resident_flat(int H, int I, int P, ResidentTree rt, const int32_t* __res
     double top_v = 0.0, top_cv[kA];
 #pragma unroll
     for (int b = 0; b < kA; ++b) top_cv[b] = 0.0;
-#if OSG_MCCFR_FRAMES2
     // the frame below the top one, in registers too: a pop then takes its frame from registers and only REQUESTS the one
     // that becomes second — nobody waits for the backing store on the traversal's chain, and a push writes to it only
     // from the third level on (leduc_poker: the traverser acts at most four times on a path)
@@ -463,37 +446,18 @@ k_mccfr_resident_flat(int H, int I, int P, ResidentTree rt, const int32_t* __res
     double sec_v = 0.0, sec_cv[kA];
 #pragma unroll
     for (int b = 0; b < kA; ++b) sec_cv[b] = 0.0;
-#endif
     int sp = 0;
     int node = 0;
     for (;;) {
       const uint2 rec = nodes[node];
-#if OSG_MCCFR_PEEK
-      // The next uniform of the stream, formed WHILE the node's record is on its way from LDS: the generator is a
-      // counter and a mixer, so the draw does not depend on the node — only whether it is consumed does (a node of the
-      // traverser or a terminal leaves the counter where it was).  Inside the branch the ~35 instructions of the mixer
-      // sat on the traversal's dependent chain behind the record's decode (profiles/r05a_pmc_solvers.json: the waves of
-      // this kernel are parked two thirds of their cycles); the empty asm keeps the compiler from sinking them back.
-      const uint64_t s_peek = rng.s + 0x9E3779B97F4A7C15ULL;
-      double z_peek = static_cast<double>(mix64(s_peek) >> 11) * (1.0 / 9007199254740992.0);
-      asm volatile("" : "+v"(z_peek));
-#endif
+      // (forming the next draw while the record is in flight measured 2.7 % slower: DESIGN.md §13 r5, profiles/r05_ab_solvers.txt)
       const int kind = rec.x & 3u;
       if (kind != kTerminalNode) {
         const int nc = (rec.x >> 2) & 63u, fc = rec.y & 0xFFFFFFu;
         const int i = rec.x >> 12;
         const int actor = static_cast<int>((rec.x >> 8) & 15u) - 1;  // -1 at chance nodes
         if (actor != trav) {
-#if OSG_MCCFR_PEEK
-          const double z = z_peek;
-          rng.s = s_peek;
-#elif defined(OSG_MCCFR_DIAG_COHERENT) && OSG_MCCFR_DIAG_COHERENT == 2
-          double z = rng.unit();
-          if (diag_draws < 2) z = rng_w.unit();
-          ++diag_draws;
-#else
           const double z = rng.unit();
-#endif
           int pick = nc - 1;
           if (kind == kChanceNode) {  // SampleAction(ChanceOutcomes(), z) (spiel.cc:372-409)
             double acc = 0.0;
@@ -534,7 +498,6 @@ k_mccfr_resident_flat(int H, int I, int P, ResidentTree rt, const int32_t* __res
         // traverser: walk every action (:155-162)
         if (sp > 0) {
           if (sp == 1) b1 = top_a;   // entering the traverser's second node inside child top_a of the first
-#if OSG_MCCFR_FRAMES2
           if (sp > 1) {              // the frame below the top one leaves for the backing store (slot k = frame k)
             s_x[sp - 2] = sec_x;
             s_fa[sp - 2] = sec_fc | (static_cast<uint32_t>(sec_a) << 24);
@@ -545,13 +508,6 @@ k_mccfr_resident_flat(int H, int I, int P, ResidentTree rt, const int32_t* __res
           sec_x = top_x; sec_fc = top_fc; sec_a = top_a; sec_v = top_v;
 #pragma unroll
           for (int b = 0; b < kA; ++b) sec_cv[b] = top_cv[b];
-#else
-          s_x[sp - 1] = top_x;
-          s_fa[sp - 1] = top_fc | (static_cast<uint32_t>(top_a) << 24);
-          s_v[sp - 1] = top_v;
-#pragma unroll
-          for (int b = 0; b < kA; ++b) s_cv[sp - 1][b] = top_cv[b];
-#endif
         }
         top_x = rec.x; top_fc = fc; top_a = 0; top_v = 0.0;
         ++sp;
@@ -581,7 +537,6 @@ k_mccfr_resident_flat(int H, int I, int P, ResidentTree rt, const int32_t* __res
         ret = top_v;
         --sp;
         if (sp > 0) {
-#if OSG_MCCFR_FRAMES2
           top_x = sec_x; top_fc = sec_fc; top_a = sec_a; top_v = sec_v;
 #pragma unroll
           for (int b = 0; b < kA; ++b) top_cv[b] = sec_cv[b];
@@ -593,14 +548,6 @@ k_mccfr_resident_flat(int H, int I, int P, ResidentTree rt, const int32_t* __res
 #pragma unroll
             for (int b = 0; b < kA; ++b) sec_cv[b] = s_cv[sp - 2][b];
           }
-#else
-          top_x = s_x[sp - 1];
-          top_fc = s_fa[sp - 1] & 0xFFFFFFu;
-          top_a = s_fa[sp - 1] >> 24;
-          top_v = s_v[sp - 1];
-#pragma unroll
-          for (int b = 0; b < kA; ++b) top_cv[b] = s_cv[sp - 1][b];
-#endif
         }
       }
       if (done) break;
@@ -1176,7 +1123,7 @@ static int mccfr_sample_impl(osg_cfr* s, uint64_t seed, int64_t first_trajectory
       const size_t tables_only = s->resident_lds_bytes - sizeof(uint64_t) * s->H;
       const bool helps = fit <= 1 && (160 * 1024) / std::max<size_t>(tables_only, 1) >= 2 &&
                          trajectories >= static_cast<int64_t>(s->num_cus) * 2048;
-      const bool want = where ? std::strcmp(where, "global") == 0 : OSG_MCCFR_TREE_GLOBAL_DEFAULT != 0;
+      const bool want = where ? std::strcmp(where, "global") == 0 : kMccfrTreeGlobalDefault;
       if (want && helps && split == 0 && s->cfg.solver != 2) {
         tree_global = 1;
         shmem_bytes = tables_only;

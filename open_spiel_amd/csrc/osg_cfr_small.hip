@@ -325,10 +325,8 @@ k_cfr_small(Tree t, SmallTree st, SmallGlobal sg, Tables tb, int iters, int iter
         if (kOwner && b_fast) {
           // (opaque per pass: otherwise every `slot == q` comparison is hoisted out of the iteration loop as a lane mask
           // in a scalar register pair and spilled to vector lanes — see k_cfr_split)
-#ifndef OSG_AB_R4_REGS
 #pragma unroll
           for (int j = 0; j < kOwnerPath; ++j) asm volatile("" : "+v"(b_code[j]));
-#endif
           double pr[kOwnerPath];
 #pragma unroll
           for (int j = 0; j < kOwnerPath; ++j) pr[j] = cur[b_code[j] >= 0 ? (b_code[j] & 0x7FFFFF) : 0];
@@ -480,11 +478,7 @@ k_cfr_small(Tree t, SmallTree st, SmallGlobal sg, Tables tb, int iters, int iter
       __syncthreads();
       // ---- C: per infostate ----
       if (kOwner) {
-#ifdef OSG_AB_R4_REGS
-        if (tid < I) do_info(tid, c_n, c_pl, c_m0, c_m1);
-#else
         if (tid < I) do_info_owner(tid, c_n, c_pl, c_m0, c_m1);   // (the host launches the owner form for A <= kMaxA only)
-#endif
       } else {
         for (int i = tid; i < I; i += nt) do_info(i, nact[i], info_player[i], mem_off[i], mem_off[i + 1]);
       }
@@ -537,9 +531,7 @@ int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, int threads, unsigned gr
     // Path-based kernel: no top-down reach pass; all-in-LDS when the tree is small enough.
     const int M = static_cast<int>(s->mem.size());
     SmallTree st{s->d_path_off, s->d_path, M, static_cast<int>(s->path.size())};
-#ifndef OSG_AB_R4_REGS
     st.L0 = s->first_decision_level;
-#endif
     SmallGlobal sg{s->d_value, s->d_node_delta, s->d_node_delta + static_cast<size_t>(M) * s->A, s->d_skip,
                    s->d_meta32, s->d_info_player32};
 #define OSG_CFR_SMALL(LDS, OWNER, THREADS, SHMEM)                                                                  \
@@ -550,16 +542,12 @@ int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, int threads, unsigned gr
   } while (0)
     if (s->small_tree && s->H <= 1024 && s->A <= kMaxA) {  // one thread per history: descriptors live in registers
       const int owner_threads = std::max(64, ((s->H + 63) / 64) * 64);
-#ifdef OSG_AB_R4_REGS
-      if (false) {}
-#else
       if (s->P == 2 && s->max_path_decisions <= 2 && s->A == 2 && s->cfg.alternating_updates)   // kuhn_poker
         k_cfr_small<true, true, 3, 2, 2><<<dim3(grid_b), dim3(owner_threads), s->small_lds_bytes, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg);
       else if (s->P == 2 && s->max_path_decisions <= 2)   // two players, short paths: the 2-entry reach block
         k_cfr_small<true, true, 3, 2><<<dim3(grid_b), dim3(owner_threads), s->small_lds_bytes, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg);
       else if (s->P == 2 && s->max_path_decisions <= 4)
         k_cfr_small<true, true, 3, 4><<<dim3(grid_b), dim3(owner_threads), s->small_lds_bytes, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg);
-#endif
       else
         OSG_CFR_SMALL(true, true, owner_threads, s->small_lds_bytes);
       s->last_kernel = "k_cfr_small<lds, owner>";

@@ -134,12 +134,6 @@ __global__ void __launch_bounds__(256) k_gcfr_fold(GridCfr g, int upd, osg_cfr_c
 // worth (3 260 -> 8 260 iterations/s on 3-player leduc in round 5).
 // Reference: cfr.cc:331-408 (ComputeCounterFactualRegret), 443-469, 596-615.
 // ---------------------------------------------------------------------------
-#ifndef OSG_SUB_KEEP_DESCRIPTORS
-#define OSG_SUB_KEEP_DESCRIPTORS 1
-#endif
-#ifndef OSG_SUB_QUAD_STORE
-#define OSG_SUB_QUAD_STORE 1
-#endif
 OSG_D unsigned int dlo(double v) { return static_cast<unsigned int>(__double_as_longlong(v)); }
 OSG_D unsigned int dhi(double v) { return static_cast<unsigned int>(__double_as_longlong(v) >> 32); }
 // Lane kSrc of every quad (four consecutive lanes) broadcast to the quad: a DPP move, no LDS.
@@ -266,7 +260,7 @@ k_cfr_sub(Tree t, SmallTree st, SubTree sp, Tables tb, int iters, int iteration0
       }
     }
   };
-  const bool one_bin = OSG_SUB_KEEP_DESCRIPTORS && sp.G <= static_cast<int>(gridDim.x);
+  const bool one_bin = sp.G <= static_cast<int>(gridDim.x);
   if (one_bin && static_cast<int>(blockIdx.x) < sp.G) load_descriptors(blockIdx.x, sp.nloc[blockIdx.x]);
   for (int it = 0; it < iters; ++it) {
     const int iteration = iteration0 + it + 1;
@@ -466,7 +460,7 @@ k_cfr_sub(Tree t, SmallTree st, SubTree sp, Tables tb, int iters, int iteration0
               dr[1] = 0.0;
             }
             static_assert(kSplitMaxA == 4 && kSubRecDoubles == 8, "the record is two pieces of regret terms, two of policy terms");
-            if (A > 2 && OSG_SUB_QUAD_STORE) {   // (workgroup-uniform)
+            if (A > 2) {   // (workgroup-uniform)
               // A member's 64-byte record leaves as ONE contiguous piece of memory traffic: the four lanes of a quad write
               // the four 16-byte pieces of ONE member's record together, member by member (round 6).  Written by its own
               // lane piece by piece, every store instruction put 64 scattered 16-byte fragments on the fabric — the records
@@ -480,15 +474,9 @@ k_cfr_sub(Tree t, SmallTree st, SubTree sp, Tables tb, int iters, int iteration0
               quad_store<1>(rec_buf, own, at, wr, rq);
               quad_store<2>(rec_buf, own, at, wr, rq);
               quad_store<3>(rec_buf, own, at, wr, rq);
-            } else if (live[u]) {
+            } else if (live[u]) {   // A <= 2: the two pieces of a member's lane
               store_through16(rec_buf, at, osg_d2{dr[0], dr[1]});
-              if (!pruned[u]) {
-                store_through16(rec_buf, at + 32, osg_d2{dp[0], dp[1]});
-                if (A > 2) {   // (workgroup-uniform)
-                  store_through16(rec_buf, at + 16, osg_d2{dr[2], dr[3]});
-                  store_through16(rec_buf, at + 48, osg_d2{dp[2], dp[3]});
-                }
-              }
+              if (!pruned[u]) store_through16(rec_buf, at + 32, osg_d2{dp[0], dp[1]});
             }
           }
         };

@@ -36,9 +36,6 @@ __global__ void __launch_bounds__(kBlock) k_init(typename G::Params p, typename 
 // 16 bytes per lane, 4 KiB per workgroup: the plain-copy ceiling (osg_copy_bytes).
 __global__ void __launch_bounds__(256) k_copy16(const uint4* __restrict__ src, uint4* __restrict__ dst, int64_t n16) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-#ifdef OSG_COPY_PLAIN
-  if (i < n16) dst[i] = src[i];
-#else
   // non-temporal stores, like the kernels it is the ceiling of (a copy with plain stores is slower: §9)
   if (i < n16) {
     const uint4 v = src[i];
@@ -47,7 +44,6 @@ __global__ void __launch_bounds__(256) k_copy16(const uint4* __restrict__ src, u
     __builtin_nontemporal_store(v.z, &dst[i].z);
     __builtin_nontemporal_store(v.w, &dst[i].w);
   }
-#endif
 }
 
 template <class G>
@@ -308,10 +304,7 @@ k_step_hexvec(typename HexT<NW>::Params p, const uint32_t* src, uint32_t* dst, i
 
 // connect_four, other geometries than 6 x 7 x 4: TWO consecutive states per thread so that every state access is
 // one 16-byte vector load/store per lane per plane; actions / masks / statuses move as u16.
-#ifndef OSG_C4STEP_BLOCK
-#define OSG_C4STEP_BLOCK 128
-#endif
-constexpr int kC4StepBlock = OSG_C4STEP_BLOCK;
+constexpr int kC4StepBlock = 128;
 template <class G>
 __global__ void __launch_bounds__(kC4StepBlock)
 k_step_c4x2(typename G::Params p, const uint64_t* src, uint64_t* dst, int64_t n,  // src may BE dst (in-place step)
@@ -414,23 +407,15 @@ typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));  // rows 
 // 0.83, kuhn [n, 7] 0.60 -> 0.67, [n, 11] 0.69 -> 0.76, hex(9) 0.67 -> 0.71; the tic_tac_toe rows keep plain stores
 // (0.77 -> 0.70 with non-temporal ones), the connect_four planes take them from 2^22 states on (see the kernel).
 OSG_D void store_row4(float4u* dst, const float4u& v) {  // 4-byte aligned rows
-#ifdef OSG_OBS_PLAIN
-  *dst = v;
-#else
   __builtin_nontemporal_store(v, dst);
-#endif
 }
 template <bool kNt = true>
 OSG_D void store_row4(float4* dst, const float4& v) {  // 16-byte aligned spans
   if constexpr (!kNt) { *dst = v; return; }
-#ifdef OSG_OBS_PLAIN
-  *dst = v;
-#else
   __builtin_nontemporal_store(v.x, &dst->x);
   __builtin_nontemporal_store(v.y, &dst->y);
   __builtin_nontemporal_store(v.z, &dst->z);
   __builtin_nontemporal_store(v.w, &dst->w);
-#endif
 }
 template <class G, int F>  // F = floats per lane (a multiple of 4): 4 for short rows, 16 for long ones
 __global__ void __launch_bounds__(kBlock)
@@ -630,10 +615,7 @@ k_observation_c4std(C4Params p, const uint64_t* __restrict__ base, int64_t n, in
 // row per lane would (about 1.2 instructions per output byte instead of 5; 117 -> 94 us for [2^20, 126]).  A wavefront owns a contiguous, 16-byte
 // aligned span of 64 x 42 floats; it is staged in LDS (8-byte writes at a 168-byte lane stride) and
 // written back as aligned float4, one KiB per store instruction.  Needs a 16-byte aligned output.
-#ifndef OSG_C4OBS_BLOCK
-#define OSG_C4OBS_BLOCK 128
-#endif
-constexpr int kC4ObsBlock = OSG_C4OBS_BLOCK;
+constexpr int kC4ObsBlock = 128;
 // kNt: non-temporal stores — slower while the tensor is small (2^20 states: 95.7 vs 90.8 us), faster once it is
 // gigabytes (2^24 states, 8.5 GB: 1 395 vs 1 485 us); the launcher picks by size.
 template <bool kNt>
@@ -1556,9 +1538,6 @@ k_rollout(typename G::Params p, const typename G::word_t* base, int64_t n, int n
 // The same work items for hex when nobody asks for the ply counts (round 6): a playout is HexT::fill_playout_winner —
 // the stones placed with the same draws until the board is full, the winner read off by one flood — so every playout of
 // a root has the same length and the loop needs no retire / refill phase.  Same sums as k_rollout.
-#ifndef OSG_HEX_FILL_PLAYOUT
-#define OSG_HEX_FILL_PLAYOUT 1
-#endif
 template <class G>
 __global__ void __launch_bounds__(kBlock)
 k_rollout_hexfill(typename G::Params p, const typename G::word_t* base, int64_t n, uint64_t seed, int64_t index_offset,
@@ -2290,10 +2269,8 @@ int osg_random_steps(osg_batch* b, uint64_t seed, int64_t index_offset, int step
   osg_ctx* ctx = b->ctx;
   unsigned long long* partials = ctx->d_illegal + 1;
   int64_t blocks = (b->n + kBlock - 1) / kBlock;
-#ifndef OSG_RS_BLOCKS
-#define OSG_RS_BLOCKS 4096
-#endif
-  if (blocks > OSG_RS_BLOCKS) blocks = OSG_RS_BLOCKS;  // 16 workgroups per CU (4096 measured 4 % faster than 2048), grid-strided beyond
+  constexpr int64_t kMaxBlocks = 4096;
+  if (blocks > kMaxBlocks) blocks = kMaxBlocks;  // 16 workgroups per CU (4096 measured 4 % faster than 2048), grid-strided beyond
   OSG_DISPATCH_WIDE(b->spec, k_random_steps<G><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, ctx->stream>>>(P,
                                             static_cast<typename G::word_t*>(b->d_words), b->n, seed, index_offset,
                                             steps, partials));
@@ -2327,10 +2304,8 @@ int osg_rollout(const osg_batch* roots, uint64_t seed, int64_t index_offset, int
   if (n_rollouts <= 0) return set_error(OSG_ERR_INVALID, "n_rollouts must be positive");
   if (int rc = refuse_endless_playouts(roots->spec, "osg_rollout")) return rc;
   // Lanes per root: enough shares to fill the chip (8 waves per SIMD = 2^19 lanes), no more.
-#ifndef OSG_ROLLOUT_LANES_LOG2
-#define OSG_ROLLOUT_LANES_LOG2 19
-#endif
-  int64_t group = ((int64_t{1} << OSG_ROLLOUT_LANES_LOG2) + n - 1) / std::max<int64_t>(n, 1);
+  constexpr int kLanesLog2 = 19;
+  int64_t group = ((int64_t{1} << kLanesLog2) + n - 1) / std::max<int64_t>(n, 1);
   if (group > n_rollouts) group = n_rollouts;
   if (group < 1) group = 1;
   // scratch: [sums | steps] when the results go to the host, then the per-share slots when group > 1
@@ -2353,7 +2328,7 @@ int osg_rollout(const osg_batch* roots, uint64_t seed, int64_t index_offset, int
   // Persistent grid: at most 8 blocks per CU x 256 CUs, grid-strided beyond that.
   int64_t blocks = (total + kBlock - 1) / kBlock;
   if (blocks > 2048) blocks = 2048;
-  if (OSG_HEX_FILL_PLAYOUT && !steps && roots->spec.desc.game_kind == kHex) {
+  if (!steps && roots->spec.desc.game_kind == kHex) {
     OSG_DISPATCH_WIDE(roots->spec, launch_rollout_hexfill<G>(P, roots->d_words, n, seed, index_offset, n_rollouts,
                                                              static_cast<int>(group), d_part, static_cast<unsigned>(blocks), ctx->stream));
   } else {

@@ -37,9 +37,6 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
   using LegalMask = MaskT<G::kMaskW>;
   const int64_t r = static_cast<int64_t>(blockIdx.x) * kBlockM + threadIdx.x;
   if (r >= n) return;
-#ifndef OSG_MCTS_LDS_SHUFFLE
-#define OSG_MCTS_LDS_SHUFFLE 1
-#endif
   // the lane's column of the shuffle stage: entry k at sh[k * kBlockM] (dynamic LDS: widest node x kBlockM entries)
   using act_t = uint8_t;   // (boards of up to six plane words: at most 193 actions)
   extern __shared__ unsigned char s_shuffle[];
@@ -91,7 +88,7 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
         if (c == 0 || used + static_cast<uint32_t>(c) > static_cast<uint32_t>(pool.cap)) break;
         const uint32_t first = used;
         used += c;
-        if constexpr (OSG_MCTS_LDS_SHUFFLE && G::kMaskW < 8) {
+        if constexpr (G::kMaskW < 8) {
         // Round 6: the children's order is formed in LDS and every header written ONCE.  The shuffle used to run on
         // the pool — per child two loads and two stores of the lane's own, scattered node words on top of the five
         // initialising stores — which is most of what an expansion of a wide node (hex: ~100 children) costs.

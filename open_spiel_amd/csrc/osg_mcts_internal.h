@@ -9,10 +9,7 @@
 
 namespace osg {
 
-#ifndef OSG_MCTS_LANE_BLOCK
-#define OSG_MCTS_LANE_BLOCK 64
-#endif
-constexpr int kBlockM = OSG_MCTS_LANE_BLOCK;  // one wave per block: searches differ in length, keep blocks small
+constexpr int kBlockM = 64;  // one wave per block: searches differ in length, keep blocks small
 constexpr uint64_t kTreeSalt = 0x7265655F73616C74ULL;  // stream separation for the tree-policy RNG
 constexpr uint32_t kNoNode = 0xFFFFFFFFu;
 
@@ -81,12 +78,6 @@ OSG_D double outcome_value(uint32_t meta, uint32_t count, double total, int play
 // Wave-wide maximum of an fp32 value as a DPP reduction (gfx9 row_shr 1, 2, 4, 8, row_bcast 15 / 31; identity -infinity),
 // handed back wave-uniform.  All 64 lanes must be active.  (The fp32 filter of the UCT arg-max: k_mcts_wave's
 // select_child, k_mcts_advance's lockstep search.)
-#ifndef OSG_UCT_FILTER_STEP
-#define OSG_UCT_FILTER_STEP 1   // k_mcts_advance's lockstep (one-root) search through the filter (1) or always fp64 (0)
-#endif
-#ifndef OSG_COOP_BACKUP
-#define OSG_COOP_BACKUP 1       // the one-root search's backup by one lane per path node (1) or up the parent links (0)
-#endif
 template <int kCtrl, int kRowMask>
 OSG_D float dpp_maxf_step_(float v) {
   const int o = __builtin_amdgcn_update_dpp(static_cast<int>(0xFF800000u), __float_as_int(v), kCtrl, kRowMask, 0xf, false);
@@ -104,10 +95,7 @@ OSG_D float wave_max_f32_dpp(float v) {
 
 // One playout of RandomRolloutEvaluator::Evaluate (mcts.cc:45-56) from `s` on `rng`: Returns() of the finished game in
 // rr.  hex: the winner from the filled board (HexT::fill_playout_winner, round 6 — the same draws and moves without the
-// edge labels; OSG_HEX_FILL_PLAYOUT=0 at build time keeps the move-by-move rules); the other games move by move.
-#ifndef OSG_HEX_FILL_PLAYOUT
-#define OSG_HEX_FILL_PLAYOUT 1
-#endif
+// edge labels); the other games move by move.
 // The k-th (0-based) set bit of a 9-bit set; k < popcount(x).  (select32 without its two widest halvings.)
 OSG_D int select9(uint32_t x, int k) {
   const int c8 = __builtin_popcount(x & 0xFFu);
@@ -122,12 +110,9 @@ OSG_D int select9(uint32_t x, int k) {
   }
   return pos;
 }
-#ifndef OSG_TTT_PLAYOUT
-#define OSG_TTT_PLAYOUT 1   // tic_tac_toe playouts test the mover's lines only (1) or run the generic rule calls (0)
-#endif
 template <class G>
 OSG_D void playout_returns(const typename G::Params& p, const typename G::State& s, Rng& rng, double* rr) {
-  if constexpr (std::is_same<G, Ttt>::value && OSG_TTT_PLAYOUT != 0) {
+  if constexpr (std::is_same<G, Ttt>::value) {
     // The same draws and moves as the generic loop below (rng.below(number of empty cells), the k-th empty cell), with
     // the rules' work cut to what a move can change: only the player who just moved can have completed a line, and the
     // board is full after nine stones (tic_tac_toe.cc:109-136, 215-227).
@@ -144,7 +129,7 @@ OSG_D void playout_returns(const typename G::Params& p, const typename G::State&
       }
     }
     G::returns(p, w, rr);
-  } else if constexpr (is_hex<G>::value && OSG_HEX_FILL_PLAYOUT) {
+  } else if constexpr (is_hex<G>::value) {
     const double r0 = G::fill_playout_winner(p, s, rng) == 0 ? 1.0 : -1.0;
     rr[0] = r0;
     rr[1] = -r0;

@@ -135,41 +135,28 @@ OSG_D LdsTree lds_tree(void* base) {
 }
 constexpr size_t kLdsTreeBytes = static_cast<size_t>(kLdsNodes) * (sizeof(double) + 4 * sizeof(uint32_t));
 // One field of one node: in LDS (kCoop and a low index) or in the pool.
-#ifndef OSG_NODEREF_MODE
-#define OSG_NODEREF_MODE 1   // round 6: 12.39 -> 11.68 ms per 1000-simulation tic_tac_toe search (profiles/r06d_one_root_noderef_ab.txt), parity green
-#endif
 template <class T, bool kCoop>
 struct NodeRef {
   T* l;
   T* g;
   bool in_lds;
-  // kCoop: lane 0 alone stores and all 64 lanes read the field back, so the accesses are VOLATILE there: with plain
-  // ones the compiler may serve a lane that did not store from a value it loaded earlier (e.g. after COUNT(v) += 1),
-  // and the replicated search state of the lanes would part ways.  (The other form has one lane per search: plain.)
-  // OSG_NODEREF_MODE 1 (A/B, round 6): plain accesses, and a compiler-level memory barrier after lane 0's store — every
-  // later read is loaded again (the hazard above), while reads BETWEEN two stores may still be shared, which volatile forbids.
+  // kCoop: lane 0 alone stores and all 64 lanes read the field back.  The compiler must not serve a lane that did not
+  // store from a value it loaded earlier (e.g. after COUNT(v) += 1), or the replicated search state of the lanes would
+  // part ways: a compiler-level memory barrier after lane 0's store makes every later read load again, while reads
+  // BETWEEN two stores may still be shared (11.68 ms per 1000-simulation tic_tac_toe search against 12.39 with volatile
+  // accesses, profiles/r06d_one_root_noderef_ab.txt).  (The other form has one lane per search: plain.)
   OSG_D operator T() const {
-#if OSG_NODEREF_MODE == 1
     if (kCoop) return in_lds ? *l : *g;
-#else
-    if (kCoop) return in_lds ? *static_cast<volatile T*>(l) : *static_cast<volatile T*>(g);
-#endif
     return *g;
   }
   OSG_D T operator=(T v) const {
     // kCoop: the whole first wavefront runs the search in lockstep (every lane holds the same search state, so that
     // the lanes can share out a node's children); one lane's store is enough — 64 stores to one LDS address serialise
     if (kCoop) {
-#if OSG_NODEREF_MODE == 1
       if (threadIdx.x == 0) {
         if (in_lds) *l = v; else *g = v;
       }
       asm volatile("" ::: "memory");
-#else
-      if (threadIdx.x == 0) {
-        if (in_lds) *static_cast<volatile T*>(l) = v; else *static_cast<volatile T*>(g) = v;
-      }
-#endif
       return v;
     }
     *g = v;
@@ -387,7 +374,7 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
       trng = Rng(cfg.seed ^ kTreeSalt, gr, static_cast<uint64_t>(sims_done));
       s = root_state;
       node = 0;
-      path_node = 0; path_depth = 0; path_ok = kCoop && OSG_COOP_BACKUP != 0;
+      path_node = 0; path_depth = 0; path_ok = kCoop;
     } else {  // resume at the parked node: its state is in the leaf batch
       s = G::load(p, leaf_words, n, r);
       path_ok = false;
@@ -471,7 +458,7 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
                 bc = 0;
                 bf = static_cast<uint32_t>(__shfl(static_cast<int>(cf), src, 64));
                 decided = true;
-              } else if constexpr (kBoard && OSG_UCT_FILTER_STEP != 0) {
+              } else if constexpr (kBoard) {
                 // (round 6, as in k_mcts_wave's select_child) the arg-max through an fp32 filter: every child's value in
                 // single precision (a proven outcome is a small integer, exact; the others within 2^-20 (1 + |c| sqrt(log
                 // n)) of the fp64 value: returns in [-1, 1]); only children within 2^-18 of the largest can hold the exact
@@ -602,7 +589,7 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
             playout_returns<G>(p, s, rng, rr);
             for (int q = 0; q < num_players; ++q) sum[q] += rr[q];
           }
-          if (kBoard && cfg.n_rollouts <= 64 && OSG_COOP_BACKUP != 0) {
+          if (kBoard && cfg.n_rollouts <= 64) {
             // win / draw / loss games, one playout per lane: the sum of player 0's returns (each -1, 0 or +1) is wins
             // minus losses — two ballots instead of two 64-bit butterflies through the LDS crossbar — and player 1's
             // is its negation (Returns() of these games: {r, -r + 0.0}; small integers, exact in any order)

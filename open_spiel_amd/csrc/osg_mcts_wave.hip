@@ -78,35 +78,12 @@ extern "C" int osg_debug_phase_cycles(unsigned long long* out8, int reset) {
 
 namespace {
 
-#ifndef OSG_WAVES_PER_BLOCK
-#define OSG_WAVES_PER_BLOCK 4
-#endif
-constexpr int kWavesPerBlock = OSG_WAVES_PER_BLOCK;
+constexpr int kWavesPerBlock = 4;
 constexpr int kMaxPath = 160;
-// Where the hex playout's bookkeeping runs: 1 = on the vector unit (measured on MI355X, config 4: key threshold
-// 0 -> 1: 9.48e8 -> 1.003e9 sims/s; flood 0 -> 1: 9.89e8 -> 1.003e9), 0 = the scalar formulation.  Flood mode 2 (round 5:
-// the two exits on the vector unit as well, tested once per two steps — ~20 -> ~8 scalar instructions per pair of
-// steps) measured 1.105e9 -> 1.090e9: the vector pipe is as full as the scalar one (SQ_ACTIVE_INST_VALU 549 quad-cycles
-// per simulation against SQ_WAVE_CYCLES / 7 resident wavefronts = 503, SQ_ACTIVE_INST_SCA 382), so moving work across
-// no longer pays (profiles/r05y_hex_flood_exits_ab.txt).
-#ifndef OSG_THR_MODE
-#define OSG_THR_MODE 3
-#endif
-#ifndef OSG_FLOOD_MODE
-#define OSG_FLOOD_MODE 1
-#endif
-#ifndef OSG_HASH_VALU
-#define OSG_HASH_VALU 1
-#endif
-// The hex fill kernel's expansion from the legal cells as lane masks (1) or through the 4-word action mask (0, the form up
-// to round 5; the boards above 128 cells always take the lane masks).
-// The UCT arg-max through an fp32 filter (1) or always in fp64 (0): see select_child.
-#ifndef OSG_UCT_FILTER
-#define OSG_UCT_FILTER 1
-#endif
-#ifndef OSG_EXPAND_SETS
-#define OSG_EXPAND_SETS 1
-#endif
+constexpr int kFloodUnroll = 2;  // the hex playout flood's steps per loop trip
+// The hex playout's key threshold and flood bookkeeping run on the vector unit (config 4: threshold 9.48e8 -> 1.003e9
+// sims/s, flood 9.89e8 -> 1.003e9 against the scalar forms); the flood's two exits there as well measured slower
+// (1.105e9 -> 1.090e9, DESIGN.md §13 r5, profiles/r05y_hex_flood_exits_ab.txt).
 
 OSG_D int lane_id() { return static_cast<int>(threadIdx.x & 63u); }
 template <class T>
@@ -300,7 +277,6 @@ OSG_D Chosen select_child(const uint32_t* __restrict__ META, const uint32_t* __r
     for (int j = 0; j < kSlots; ++j) cand[j] = unvisited[j];
   } else {
     bool decided = false;
-#if OSG_UCT_FILTER
     if constexpr (kBoard) {
       if (!puct && any_outcome == 0ull) {
         // The arg-max WITHOUT the fp64 divisions and square root where single precision already decides it.  Every value
@@ -361,7 +337,6 @@ OSG_D Chosen select_child(const uint32_t* __restrict__ META, const uint32_t* __r
         }
       }
     }
-#endif
     if (!decided) {
     double v[kSlots];
     if (!puct && any_outcome == 0ull) {
@@ -476,26 +451,17 @@ template <int kS>
 constexpr int hex_band() { return kS < 3 ? kS : 3; }
 template <int kS>
 constexpr int hex_win(int j) { return j - 1 < 0 ? 0 : (j - 1 > kS - hex_band<kS>() ? kS - hex_band<kS>() : j - 1); }
-// (OSG_HEX_ONE_SET=1: hex boards of up to 64 cells — two plane words — walk with ONE cell set per colour and one child slot
-// per lane; 0 keeps two, the form up to round 6's first sessions)
-#ifndef OSG_HEX_ONE_SET
-#define OSG_HEX_ONE_SET 1
-#endif
+// Hex boards of up to 64 cells (two plane words) walk with ONE cell set per colour and one child slot per lane.
 template <class G> struct hex_plane_words { static constexpr int value = kMaskWords; };
 template <int NW> struct hex_plane_words<HexT<NW>> { static constexpr int value = NW; };
 template <class G>
 constexpr int wave_sets() {
-  return G::kMaskW > kMaskWords ? (G::kMaskW + 1) / 2 : ((OSG_HEX_ONE_SET != 0 && is_hex<G>::value && hex_plane_words<G>::value <= 2) ? 1 : 2);
+  return G::kMaskW > kMaskWords ? (G::kMaskW + 1) / 2 : ((is_hex<G>::value && hex_plane_words<G>::value <= 2) ? 1 : 2);
 }
-// Which boards flood on packed per-lane flags (HexLaneT): those above 128 cells; OSG_PACKED_FLOOD_2=1 builds the form
-// for the smaller boards too (an A/B build: hex(9) config 4 1.255e9 -> 1.11e9 simulations/s at 7 and at 6 wavefronts per
-// SIMD, 10 / 4 vector registers in scratch — with two cell sets the neighbour bands are the cheaper step;
-// profiles/r06zw_*).
-#ifndef OSG_PACKED_FLOOD_2
-#define OSG_PACKED_FLOOD_2 0
-#endif
+// Which boards flood on packed per-lane flags (HexLaneT): those above 128 cells (the smaller boards on them measured
+// slower, hex(9) config 4 1.255e9 -> 1.11e9 simulations/s: profiles/r06zw_*).
 template <int kS>
-constexpr bool hex_packed() { return kS > 2 || OSG_PACKED_FLOOD_2 != 0; }
+constexpr bool hex_packed() { return kS > 2; }
 template <int kS>
 struct HexLaneT {
   uint64_t nb[kS][hex_band<kS>()];  // slot j: neighbours among the cells of sets hex_win(j) ... hex_win(j) + kB - 1
@@ -813,32 +779,10 @@ OSG_D int hex_fill_winner(const HexWT<kS>& s, uint64_t base, const HexLaneT<kS>&
   // set while no more than `want` keys lie below.  Keys are distinct, so the search ends as soon as the
   // count is exact — about log2(m) + 2 steps of two compares and a handful of scalar instructions.
   uint64_t sel[kS];
-#if defined(OSG_DIAG_NOTHR)  // measurement only: an arbitrary subset instead of the exact half
-#pragma unroll
-  for (int j = 0; j < kS; ++j) sel[j] = __ballot((key[j] >> 20) & 1ull) & empty[j];
-#elif OSG_THR_MODE == 0
-  uint64_t thr = 0ull;
-  if (want > 0) {
-    uint64_t step = 1ull << (kBits - 1);
-    bool exact;
-    do {  // straight-line body: one select, no inner branch
-      const uint64_t probe = thr | step;
-      int below = 0;
-#pragma unroll
-      for (int j = 0; j < kS; ++j) below += __builtin_popcountll(__ballot(key[j] < probe) & empty[j]);
-      thr = below <= want ? probe : thr;
-      exact = below == want;
-      step >>= 1;
-    } while (!exact && step != 0ull);
-  }
-#pragma unroll
-  for (int j = 0; j < kS; ++j) sel[j] = __ballot(key[j] < thr) & empty[j];
-#else
   // The search runs on the VECTOR unit (the kernel is bound by scalar issue): threshold and step live in
   // vector registers holding the same value in every lane, occupied cells carry the key 2^64 - 1 so that
   // the ballots need no masking, and only the counting and the loop branch are left to the scalar unit.
   const uint32_t vz = vector_zero();
-#if OSG_THR_MODE == 3
   // First on the keys' 32 mixed bits alone (32-bit compares and selects; the cell-id bits below them only break ties):
   // a threshold with exactly `want` of those words under it selects the same cells as the full keys do.  Where two
   // empty cells share their 32 bits across the threshold (~m^2 / 2^33 of the playouts), or the largest word is all
@@ -867,31 +811,27 @@ OSG_D int hex_fill_winner(const HexWT<kS>& s, uint64_t base, const HexLaneT<kS>&
     for (int j = 0; j < kS; ++j) sel[j] = __ballot(h[j] < t32);
   }
   if (!found) {
-#endif
-  uint64_t k[kS];
+    uint64_t k[kS];
 #pragma unroll
-  for (int j = 0; j < kS; ++j) k[j] = __builtin_amdgcn_inverse_ballot_w64(empty[j]) ? key[j] : ~0ull;
-  uint64_t thr = vz;
-  if (want > 0) {
-    uint64_t step = (1ull << (kBits - 1)) | vz;
-    const uint32_t want_v = static_cast<uint32_t>(want) | vz;
-    for (int it = 0; it < kBits; ++it) {
-      const uint64_t probe = thr | step;
-      int below = 0;
+    for (int j = 0; j < kS; ++j) k[j] = __builtin_amdgcn_inverse_ballot_w64(empty[j]) ? key[j] : ~0ull;
+    uint64_t thr = vz;
+    if (want > 0) {
+      uint64_t step = (1ull << (kBits - 1)) | vz;
+      const uint32_t want_v = static_cast<uint32_t>(want) | vz;
+      for (int it = 0; it < kBits; ++it) {
+        const uint64_t probe = thr | step;
+        int below = 0;
 #pragma unroll
-      for (int j = 0; j < kS; ++j) below += __builtin_popcountll(__ballot(k[j] < probe));
-      const uint32_t below_v = static_cast<uint32_t>(below) | vz;
-      thr = below_v <= want_v ? probe : thr;
-      step >>= 1;
-      if (below == want) break;
+        for (int j = 0; j < kS; ++j) below += __builtin_popcountll(__ballot(k[j] < probe));
+        const uint32_t below_v = static_cast<uint32_t>(below) | vz;
+        thr = below_v <= want_v ? probe : thr;
+        step >>= 1;
+        if (below == want) break;
+      }
     }
-  }
 #pragma unroll
-  for (int j = 0; j < kS; ++j) sel[j] = __ballot(k[j] < thr);
-#if OSG_THR_MODE == 3
+    for (int j = 0; j < kS; ++j) sel[j] = __ballot(k[j] < thr);
   }
-#endif
-#endif
   PT_MARK(4);
   // The filled board: the mover's new stones are `sel`, the opponent's the other empty cells.
   const bool black_moves = (s.meta & 1u) == 0;
@@ -901,56 +841,6 @@ OSG_D int hex_fill_winner(const HexWT<kS>& s, uint64_t base, const HexLaneT<kS>&
   // Black wins iff its stones join the first row to the last row (hex.cc:108-171 edge labels).
   // Lane-parallel flood: a black cell joins the region when one of its neighbours is in it.
   // Stops as soon as the last row is reached.
-#if defined(OSG_DIAG_NOFLOOD)  // measurement only
-  return static_cast<int>((blk[0] ^ blk[1] ^ (blk[0] >> 17)) & 1ull);
-#elif OSG_FLOOD_MODE == 0
-  uint64_t reach[kS];
-#pragma unroll
-  for (int j = 0; j < kS; ++j) reach[j] = blk[j] & hl.first_row[j];
-#pragma unroll 4  // measured: 1 -> 7.80e8, compiler's choice (2) -> 7.93e8, 4 -> 8.01e8 sims/s
-  for (int it = 0; it < 64 * kS; ++it) {
-    if (sets_meet<kS>(reach, hl.last_row)) return 0;  // black
-    uint64_t g[kS];
-#pragma unroll
-    for (int j = 0; j < kS; ++j) g[j] = __ballot(hex_touch<kS>(hl, j, reach) != 0u) & blk[j] & ~reach[j];
-    if (!sets_any<kS>(g)) break;
-#pragma unroll
-    for (int j = 0; j < kS; ++j) reach[j] |= g[j];
-  }
-#elif OSG_FLOOD_MODE == 2
-  static_assert(kS == 2, "flood mode 2 (a measurement variant) is written for boards of up to 128 cells");
-  // As mode 1, with the two exits decided on the VECTOR unit too and only once per TWO steps: every lane remembers
-  // whether one of its cells that joined lies on the last row (the "black arrived" exit) and whether its cells joined
-  // in the second step (the "nothing new" exit); each exit is one compare into vcc and one branch.  Running one step
-  // past either condition is harmless: an empty frontier stays empty, and a last-row cell that joined stays remembered.
-  uint64_t front[2] = {blk[0] & hl.first_row[0], blk[1] & hl.first_row[1]};
-  uint32_t avail0 = __builtin_amdgcn_inverse_ballot_w64(blk[0] & ~front[0]) ? ~0u : 0u;
-  uint32_t avail1 = __builtin_amdgcn_inverse_ballot_w64(blk[1] & ~front[1]) ? ~0u : 0u;
-  if (sets_meet<kS>(front, hl.last_row)) return 0;  // a one-row chain
-  // all ones where the lane's cell is on the last row (edge bit 1 of cell l, bit 5 of cell l + 64)
-  const uint32_t last0 = static_cast<uint32_t>(static_cast<int32_t>(hl.edge << 30) >> 31);
-  const uint32_t last1 = static_cast<uint32_t>(static_cast<int32_t>(hl.edge << 26) >> 31);
-  uint32_t hit;  // (lane-local) one of the lane's cells that joined in this pair of steps lies on the last row
-  for (;;) {
-    const uint32_t ja0 = hex_touch<kS>(hl, 0, front) & avail0;
-    const uint32_t ja1 = hex_touch<kS>(hl, 1, front) & avail1;
-    const uint64_t mid[2] = {__ballot(ja0 != 0u), __ballot(ja1 != 0u)};
-    avail0 = ja0 != 0u ? 0u : avail0;
-    avail1 = ja1 != 0u ? 0u : avail1;
-    const uint32_t jb0 = hex_touch<kS>(hl, 0, mid) & avail0;
-    const uint32_t jb1 = hex_touch<kS>(hl, 1, mid) & avail1;
-    front[0] = __ballot(jb0 != 0u);
-    front[1] = __ballot(jb1 != 0u);
-    avail0 = jb0 != 0u ? 0u : avail0;
-    avail1 = jb1 != 0u ? 0u : avail1;
-    // (both exits lead to the same place and the answer is read off `hit` there: the loop stays two compares into
-    // vcc and two branches, no exit-code bookkeeping on the scalar unit)
-    hit = ((ja0 | jb0) & last0) | ((ja1 | jb1) & last1);
-    if (__ballot(hit != 0u) != 0ull) break;            // black reached its last row
-    if (__ballot((jb0 | jb1) != 0u) == 0ull) break;    // nothing new: black's region is closed
-  }
-  return __ballot(hit != 0u) != 0ull ? 0 : 1;
-#else
   if constexpr (hex_packed<kS>()) {  // packed flags (see HexLaneT): a step costs six cross-lane reads whatever kS is
     const uint32_t black = hex_pack<kS>(blk);
     uint32_t front = black & hl.fl_edge[0];
@@ -976,10 +866,7 @@ OSG_D int hex_fill_winner(const HexWT<kS>& s, uint64_t base, const HexLaneT<kS>&
     avail[j] = __builtin_amdgcn_inverse_ballot_w64(blk[j] & ~front[j]) ? ~0u : 0u;
   }
   if (sets_meet<kS>(front, hl.last_row)) return 0;  // a one-row chain
-#ifndef OSG_FLOOD_UNROLL
-#define OSG_FLOOD_UNROLL 2
-#endif
-#pragma unroll OSG_FLOOD_UNROLL
+#pragma unroll kFloodUnroll
   for (int it = 0; it < 64 * kS; ++it) {
     uint32_t jn[kS];
 #pragma unroll
@@ -991,7 +878,6 @@ OSG_D int hex_fill_winner(const HexWT<kS>& s, uint64_t base, const HexLaneT<kS>&
 #pragma unroll
     for (int j = 0; j < kS; ++j) avail[j] = jn[j] != 0u ? 0u : avail[j];
   }
-#endif
   return 1;  // white: on a filled board exactly one side connects
 }
 
@@ -1001,10 +887,7 @@ OSG_D int hex_fill_winner(const HexWT<kS>& s, uint64_t base, const HexLaneT<kS>&
 // tree level, no memory and nothing for the scalar unit; the backup has lane d own path node d anyway); entries
 // 64 ... kMaxPath - 1 — reachable only in games longer than 64 plies — live in LDS.  Entry 0 is the root, whose
 // statistics persist in lane 0 from one simulation to the next.
-#ifndef OSG_PATH_REGS
-#define OSG_PATH_REGS 64  // (a test build with 2 sends every deeper entry through the LDS part)
-#endif
-constexpr int kPathRegs = OSG_PATH_REGS;
+constexpr int kPathRegs = 64;
 struct VisitPath {
   uint32_t node, cnt;
   double tot;
@@ -1028,24 +911,12 @@ struct VisitPath {
   }
 };
 
-#ifndef OSG_HEX_WPE
-#define OSG_HEX_WPE 7
-#endif
 // Wavefronts per SIMD the hex fill kernel is compiled for, by the number of cell sets of the position (the boards above
 // 128 cells hold kS sets per colour in scalar registers and kS child slots per lane: fewer, fatter wavefronts).
-#ifndef OSG_HEX_WPE_3
-#define OSG_HEX_WPE_3 5
-#endif
-#ifndef OSG_HEX_WPE_4
-#define OSG_HEX_WPE_4 5
-#endif
-#ifndef OSG_HEX_WPE_6
-#define OSG_HEX_WPE_6 4
-#endif
 template <class G, bool kHexFill>
 constexpr int wave_wpe() {
   if (!kHexFill) return 4;
-  return wave_sets<G>() <= 2 ? OSG_HEX_WPE : (wave_sets<G>() == 3 ? OSG_HEX_WPE_3 : (wave_sets<G>() == 4 ? OSG_HEX_WPE_4 : OSG_HEX_WPE_6));
+  return wave_sets<G>() <= 2 ? 7 : (wave_sets<G>() == 3 ? 5 : (wave_sets<G>() == 4 ? 5 : 4));
 }
 
 // The hex fill kernel at 7 waves per SIMD.  What the code object says (tools/kernel_resources.py ->
@@ -1111,11 +982,7 @@ OSG_D void wave_search(const typename G::Params& p, const typename G::word_t* ba
   int sims_done = 0;
   // Hash chains whose value is the same in every lane (the path hash behind the sibling order, the playout's
   // fill base) run on the vector unit: the kernel is bound by scalar issue, and their consumers are per-lane anyway.
-#if OSG_HASH_VALU
   const uint32_t vz = vector_zero();
-#else
-  const uint32_t vz = 0u;
-#endif
   const uint32_t fill_word = kHexFill ? fill_root(cfg.seed, gr) : 0u;
   PT_DECL
 
@@ -1153,7 +1020,7 @@ OSG_D void wave_search(const typename G::Params& p, const typename G::word_t* ba
         // Children in action order.  Lane l looks at actions l, l + 64, ...: a legal action's slot is its
         // rank among the legal ones (popcount of the mask below it) — the cheap direction of the
         // k <-> action mapping — so the writes are still one compacted, coalesced span.
-        if constexpr (kHexFill && (kWide || OSG_EXPAND_SETS)) {  // the legal set as lane masks: a rank is a running count + the lanes below
+        if constexpr (kHexFill) {  // the legal set as lane masks: a rank is a running count + the lanes below
           int before = 0;
 #pragma unroll
           for (int j = 0; j < kS; ++j) {

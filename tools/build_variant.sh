@@ -1,7 +1,9 @@
 #!/bin/bash
 # Builds tools/variants/libosg_<name>.so: the product library with osg_mcts_wave.hip (or the file named
-# by SRC=) compiled with extra -D flags, for A/B measurements of kernel variants on the GPU box.
-#   tools/build_variant.sh thr2 -DOSG_THR_MODE=2
+# by SRC=) compiled with extra -D flags.  The sources keep two instrumentation builds, which leave results unchanged:
+#   tools/build_variant.sh pt -DOSG_PHASE_TIMING                            (phase cycles of the wave search)
+#   SRC=osg_mcts_step tools/build_variant.sh prof -DOSG_MCTS_PROFILE        (phase cycles of the one-root search)
+# Any other A/B (e.g. before / after a kernel change) is two libraries for OSG_VARIANT_LIB and the probe_*_variants tools.
 set -e
 cd "$(dirname "$0")/../open_spiel_amd/csrc"
 name=$1; shift
