@@ -278,8 +278,6 @@ struct ResidentTree {
 
 constexpr int kMaxOsDepth = 32;
 
-template <class T> struct TypeTag { using type = T; };
-
 template <class T>
 int upload(const std::vector<T>& v, T** d, hipStream_t stream) {
   const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);

@@ -1146,29 +1146,24 @@ static int mccfr_sample_impl(osg_cfr* s, uint64_t seed, int64_t first_trajectory
       OSG_HIP(hipMalloc(reinterpret_cast<void**>(&d_stamps), sizeof(unsigned long long) * 4));
     const dim3 grid(static_cast<unsigned>(groups)), block(threads);
     const size_t shmem = shmem_bytes;
-#define OSG_MCCFR_RES(KA)                                                                                          \
-  do {                                                                                                             \
-    if (s->cfg.solver == 2)                                                                                        \
-      k_os_mccfr_resident<KA><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), dreg, \
-                                                          dpol, seed, first_trajectory, sampled,             \
-                                                          s->cfg.epsilon);                                        \
-    else if (split == 1 && KA >= 2)                                                                                \
-      k_mccfr_resident<(KA >= 2 ? KA : 2), 1><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), \
-                                                       dreg, dpol, seed, first_trajectory, sampled, d_stamps);   \
-    else if (split == 2 && KA >= 2)                                                                                \
-      k_mccfr_resident<(KA >= 2 ? KA : 2), 2><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), \
-                                                       dreg, dpol, seed, first_trajectory, sampled, d_stamps);   \
-    else                                                                                                           \
-      k_mccfr_resident_flat<KA><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), dreg, \
-                                                            dpol, seed, first_trajectory, sampled);            \
-  } while (0)
-    switch (s->A) {
-      case 1: OSG_MCCFR_RES(1); break;
-      case 2: OSG_MCCFR_RES(2); break;
-      case 3: OSG_MCCFR_RES(3); break;
-      default: OSG_MCCFR_RES(4); break;
-    }
-#undef OSG_MCCFR_RES
+    with_int<1, 2, 3, 4>(s->A, [&](auto ka) {
+      constexpr int KA = decltype(ka)::value;
+      const auto resident = [&](auto sp) {   // (the split forms exist from two actions on)
+        if constexpr (KA >= 2)
+          k_mccfr_resident<KA, decltype(sp)::value><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(),
+                                                                                dreg, dpol, seed, first_trajectory, sampled, d_stamps);
+      };
+      if (s->cfg.solver == 2)
+        k_os_mccfr_resident<KA><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), dreg,
+                                                            dpol, seed, first_trajectory, sampled,
+                                                            s->cfg.epsilon);
+      else if (split == 1 && KA >= 2) resident(std::integral_constant<int, 1>{});
+      else if (split == 2 && KA >= 2) resident(std::integral_constant<int, 2>{});
+      else
+        k_mccfr_resident_flat<KA><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), dreg,
+                                                              dpol, seed, first_trajectory, sampled);
+      return OSG_OK;
+    });
     OSG_HIP(hipGetLastError());
     s->last_kernel = s->cfg.solver == 2 ? "k_os_mccfr_resident"
                                         : (split == 2 && s->A >= 2 ? "k_mccfr_resident<split 2>"

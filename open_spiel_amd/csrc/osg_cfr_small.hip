@@ -534,12 +534,13 @@ int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, int threads, unsigned gr
     st.L0 = s->first_decision_level;
     SmallGlobal sg{s->d_value, s->d_node_delta, s->d_node_delta + static_cast<size_t>(M) * s->A, s->d_skip,
                    s->d_meta32, s->d_info_player32};
-#define OSG_CFR_SMALL(LDS, OWNER, THREADS, SHMEM)                                                                  \
-  do {                                                                                                              \
-    if (s->P == 2) k_cfr_small<LDS, OWNER, 3><<<dim3(grid_b), dim3(THREADS), SHMEM, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg); \
-    else if (s->P == 3) k_cfr_small<LDS, OWNER, 4><<<dim3(grid_b), dim3(THREADS), SHMEM, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg); \
-    else k_cfr_small<LDS, OWNER, kMaxPlayers + 1><<<dim3(grid_b), dim3(THREADS), SHMEM, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg); \
-  } while (0)
+    const auto small = [&](auto lds, auto owner, int block, size_t shmem) {   // the reach block: 3, 4 or all players + 1
+      with_int<3, 4, kMaxPlayers + 1>(s->P + 1, [&](auto p1) {
+        k_cfr_small<decltype(lds)::value, decltype(owner)::value, decltype(p1)::value><<<dim3(grid_b), dim3(block), shmem, s->ctx->stream>>>(
+            s->tree(), st, sg, tb, iters, s->iteration, s->cfg);
+        return OSG_OK;
+      });
+    };
     if (s->small_tree && s->H <= 1024 && s->A <= kMaxA) {  // one thread per history: descriptors live in registers
       const int owner_threads = std::max(64, ((s->H + 63) / 64) * 64);
       if (s->P == 2 && s->max_path_decisions <= 2 && s->A == 2 && s->cfg.alternating_updates)   // kuhn_poker
@@ -549,16 +550,15 @@ int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, int threads, unsigned gr
       else if (s->P == 2 && s->max_path_decisions <= 4)
         k_cfr_small<true, true, 3, 4><<<dim3(grid_b), dim3(owner_threads), s->small_lds_bytes, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg);
       else
-        OSG_CFR_SMALL(true, true, owner_threads, s->small_lds_bytes);
+        small(std::true_type{}, std::true_type{}, owner_threads, s->small_lds_bytes);
       s->last_kernel = "k_cfr_small<lds, owner>";
     } else if (s->small_tree) {
-      OSG_CFR_SMALL(true, false, threads, s->small_lds_bytes);
+      small(std::true_type{}, std::false_type{}, threads, s->small_lds_bytes);
       s->last_kernel = "k_cfr_small<lds>";
     } else {
-      OSG_CFR_SMALL(false, false, threads, 0);
+      small(std::false_type{}, std::false_type{}, threads, 0);
       s->last_kernel = "k_cfr_small<global>";
     }
-#undef OSG_CFR_SMALL
   } else if (s->B > 1) {
     return set_error(OSG_ERR_UNSUPPORTED, "replicas > 1 are not available with the general kernel");
   } else if (s->lds_resident) {

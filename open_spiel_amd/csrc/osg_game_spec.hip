@@ -218,18 +218,11 @@ int parse_game(const char* game_string, GameSpec* out) {
     d.state_words = out->hex_fold ? 4 * out->hex_nw : 4 * out->hex_nw + 1; d.state_word_bytes = 4;
     // only the variant that holds the board: Bits::w has NW words, a larger board would write past it
     out->hex1 = {}; out->hex2 = {}; out->hex3 = {}; out->hex4 = {}; out->hex6 = {}; out->hex8 = {}; out->hex12 = {};
-    switch (out->hex_nw) {
-      case 1: fill_hex<1>(&out->hex1, cols, rows, swap, plain); break;
-      case 2: fill_hex<2>(&out->hex2, cols, rows, swap, plain); break;
-      case 3: fill_hex<3>(&out->hex3, cols, rows, swap, plain); break;
-      case 4: fill_hex<4>(&out->hex4, cols, rows, swap, plain); break;
-      case 6: fill_hex<6>(&out->hex6, cols, rows, swap, plain); break;
-      case 8: fill_hex<8>(&out->hex8, cols, rows, swap, plain); break;
-      default: fill_hex<12>(&out->hex12, cols, rows, swap, plain); break;
-    }
-    if (out->hex_fold)
-      out->hex1.words = out->hex2.words = out->hex3.words = out->hex4.words = out->hex6.words = out->hex8.words = out->hex12.words =
-          4 * out->hex_nw;   // (only the variant in use is ever read)
+    for_hex(*out, [&](auto nw, auto& p) {
+      fill_hex<decltype(nw)::value>(&p, cols, rows, swap, plain);
+      if (out->hex_fold) p.words = 4 * out->hex_nw;
+      return 0;
+    });
   } else if (name == "kuhn_poker") {
     int n = rd.get_int("players", 2);
     if (!rd.finish()) return set_error(OSG_ERR_INVALID, rd.err);

@@ -7,6 +7,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -45,6 +46,55 @@ struct GameSpec {
 
 int set_error(int code, const std::string& msg);
 
+template <class T> struct TypeTag { using type = T; };
+
+// Run-time value -> template argument, as ordinary calls: each hands the visitor `f` a tag whose type carries the
+// constant and returns f's int.  A visitor is instantiated for every tag it can be handed; where a kernel exists for a
+// part of the range only, the visitor guards the rest with `if constexpr`.
+template <class F>
+int with_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+// `v` among the listed constants; a value that is none of them takes the last.
+template <int First, int... Rest, class F>
+int with_int(int v, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, First>{});
+  else return v == First ? f(std::integral_constant<int, First>{}) : with_int<Rest...>(v, f);
+}
+// The hex layout in use: f(integral_constant<int, NW>, its HexT<NW>::Params).  The one place that pairs hex_nw with
+// the members of GameSpec (parse_game fills through it, hence the deduced Spec).
+template <class Spec, class F>
+int for_hex(Spec& spec, F&& f) {
+  switch (spec.hex_nw) {
+    case 1: return f(std::integral_constant<int, 1>{}, spec.hex1);
+    case 2: return f(std::integral_constant<int, 2>{}, spec.hex2);
+    case 3: return f(std::integral_constant<int, 3>{}, spec.hex3);
+    case 4: return f(std::integral_constant<int, 4>{}, spec.hex4);
+    case 6: return f(std::integral_constant<int, 6>{}, spec.hex6);
+    case 8: return f(std::integral_constant<int, 8>{}, spec.hex8);
+    default: return f(std::integral_constant<int, 12>{}, spec.hex12);
+  }
+}
+// The concrete game type a spec names: f(TypeTag<G>, its G::Params).  Every layout is here (the hex boards above 128
+// actions, connect_four above 64 board bits and leduc_poker with 4+ players included): the batch entry points of
+// osg_kernels.hip — states, masks, steps, tensors, random steps, rollouts, environment steps — and the lane-per-root
+// searches of osg_mcts.hip / osg_mcts_step.hip go through it.  The wave-per-root search and the solvers' tree builder
+// serve fewer layouts and keep switches of their own.
+template <class F>
+int for_game(const GameSpec& spec, F&& f) {
+  switch (spec.desc.game_kind) {
+    case kTtt: return f(TypeTag<Ttt>{}, spec.ttt);
+    case kC4:
+      if (spec.c4_std) return f(TypeTag<C4Std>{}, spec.c4);
+      if (spec.c4_wide) return f(TypeTag<C4Wide>{}, spec.c4);
+      return f(TypeTag<C4>{}, spec.c4);
+    case kKuhn: return f(TypeTag<Kuhn>{}, spec.kuhn);
+    case kLeduc:
+      if (spec.leduc_big) return f(TypeTag<LeducBig>{}, spec.leduc);
+      return f(TypeTag<Leduc>{}, spec.leduc);
+    case kHex: return for_hex(spec, [&](auto nw, const auto& p) { return f(TypeTag<HexT<nw.value>>{}, p); });
+    default: return set_error(OSG_ERR_INVALID, "bad game kind");
+  }
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is one value per KERNEL, not per solver / tree: a second user with a
 // smaller footprint must not lower the cap under a first one that is still in use.  Raises only; asked of the runtime
 // once per (device, kernel) and size step, not per launch.
@@ -67,15 +117,7 @@ inline hipError_t raise_lds_cap(const void* kernel, int bytes) {
 // RandomRolloutEvaluator would index an empty LegalActions() there.)  Entry points that play out refuse these
 // boards instead of hanging the device.
 inline void hex_dims(const GameSpec& spec, int* rows, int* cols, int* cells) {
-  switch (spec.hex_nw) {
-    case 1: *rows = spec.hex1.rows; *cols = spec.hex1.cols; *cells = spec.hex1.cells; break;
-    case 2: *rows = spec.hex2.rows; *cols = spec.hex2.cols; *cells = spec.hex2.cells; break;
-    case 3: *rows = spec.hex3.rows; *cols = spec.hex3.cols; *cells = spec.hex3.cells; break;
-    case 4: *rows = spec.hex4.rows; *cols = spec.hex4.cols; *cells = spec.hex4.cells; break;
-    case 6: *rows = spec.hex6.rows; *cols = spec.hex6.cols; *cells = spec.hex6.cells; break;
-    case 8: *rows = spec.hex8.rows; *cols = spec.hex8.cols; *cells = spec.hex8.cells; break;
-    default: *rows = spec.hex12.rows; *cols = spec.hex12.cols; *cells = spec.hex12.cells; break;
-  }
+  for_hex(spec, [&](auto, const auto& p) { *rows = p.rows; *cols = p.cols; *cells = p.cells; return 0; });
 }
 inline int refuse_endless_playouts(const GameSpec& spec, const char* who) {
   if (spec.desc.game_kind != kHex) return OSG_OK;
@@ -129,70 +171,6 @@ struct osg_batch {
     hipError_t e__ = (call);                                                       \
     if (e__ != hipSuccess)                                                         \
       return osg::set_error(OSG_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-  } while (0)
-
-// Dispatch a generic lambda-like macro body over the concrete game type.
-// Inside the body: `G` is the game struct and `P` its Params instance.
-// OSG_DISPATCH serves the games whose legal mask is the engine's 4-word Mask and whose record is the two-word one (the
-// wave-per-root search and the solvers' tree builder); OSG_DISPATCH_WIDE adds the hex boards above 128 actions,
-// connect_four above 64 board bits and leduc_poker with 4+ players (the batch entry points of osg_kernels.hip — states,
-// masks, steps, tensors, random steps, rollouts, environment steps — and the lane-per-root searches of osg_mcts.hip /
-// osg_mcts_step.hip).
-#define OSG_DISPATCH(spec, ...)                                                   \
-  do {                                                                             \
-    switch ((spec).desc.game_kind) {                                               \
-      case osg::kTtt: { using G = osg::Ttt; const G::Params& P = (spec).ttt; __VA_ARGS__; } break; \
-      case osg::kC4:                                                               \
-        if ((spec).c4_std) { using G = osg::C4Std; const G::Params& P = (spec).c4; __VA_ARGS__; } \
-        else if ((spec).c4_wide) return osg::set_error(OSG_ERR_UNSUPPORTED, "connect_four boards above 64 bits are served by " \
-                                                       "the batch entry points and the lane-per-root searches, not by this one"); \
-        else { using G = osg::C4; const G::Params& P = (spec).c4; __VA_ARGS__; }   \
-        break;                                                                     \
-      case osg::kKuhn: { using G = osg::Kuhn; const G::Params& P = (spec).kuhn; __VA_ARGS__; } break; \
-      case osg::kLeduc:                                                            \
-        if ((spec).leduc_big) return osg::set_error(OSG_ERR_UNSUPPORTED, "leduc_poker with more than 3 players is served by the " \
-                                                    "batch entry points and the lane-per-root searches, not by this one"); \
-        { using G = osg::Leduc; const G::Params& P = (spec).leduc; __VA_ARGS__; } break; \
-      case osg::kHex:                                                              \
-        switch ((spec).hex_nw) {                                                   \
-          case 1: { using G = osg::HexT<1>; const G::Params& P = (spec).hex1; __VA_ARGS__; } break; \
-          case 2: { using G = osg::HexT<2>; const G::Params& P = (spec).hex2; __VA_ARGS__; } break; \
-          case 3: { using G = osg::HexT<3>; const G::Params& P = (spec).hex3; __VA_ARGS__; } break; \
-          case 4: { using G = osg::HexT<4>; const G::Params& P = (spec).hex4; __VA_ARGS__; } break; \
-          default: return osg::set_error(OSG_ERR_UNSUPPORTED, "hex boards above 128 actions are served by the batch entry " \
-                                         "points and the lane-per-root searches, not by this one"); \
-        }                                                                          \
-        break;                                                                     \
-      default: return osg::set_error(OSG_ERR_INVALID, "bad game kind");            \
-    }                                                                              \
-  } while (0)
-#define OSG_DISPATCH_WIDE(spec, ...)                                              \
-  do {                                                                             \
-    switch ((spec).desc.game_kind) {                                               \
-      case osg::kTtt: { using G = osg::Ttt; const G::Params& P = (spec).ttt; __VA_ARGS__; } break; \
-      case osg::kC4:                                                               \
-        if ((spec).c4_std) { using G = osg::C4Std; const G::Params& P = (spec).c4; __VA_ARGS__; } \
-        else if ((spec).c4_wide) { using G = osg::C4Wide; const G::Params& P = (spec).c4; __VA_ARGS__; } \
-        else { using G = osg::C4; const G::Params& P = (spec).c4; __VA_ARGS__; }   \
-        break;                                                                     \
-      case osg::kKuhn: { using G = osg::Kuhn; const G::Params& P = (spec).kuhn; __VA_ARGS__; } break; \
-      case osg::kLeduc:                                                            \
-        if ((spec).leduc_big) { using G = osg::LeducBig; const G::Params& P = (spec).leduc; __VA_ARGS__; } \
-        else { using G = osg::Leduc; const G::Params& P = (spec).leduc; __VA_ARGS__; } \
-        break;                                                                     \
-      case osg::kHex:                                                              \
-        switch ((spec).hex_nw) {                                                   \
-          case 1: { using G = osg::HexT<1>; const G::Params& P = (spec).hex1; __VA_ARGS__; } break; \
-          case 2: { using G = osg::HexT<2>; const G::Params& P = (spec).hex2; __VA_ARGS__; } break; \
-          case 3: { using G = osg::HexT<3>; const G::Params& P = (spec).hex3; __VA_ARGS__; } break; \
-          case 4: { using G = osg::HexT<4>; const G::Params& P = (spec).hex4; __VA_ARGS__; } break; \
-          case 6: { using G = osg::HexT<6>; const G::Params& P = (spec).hex6; __VA_ARGS__; } break; \
-          case 8: { using G = osg::HexT<8>; const G::Params& P = (spec).hex8; __VA_ARGS__; } break; \
-          default: { using G = osg::HexT<12>; const G::Params& P = (spec).hex12; __VA_ARGS__; } break; \
-        }                                                                          \
-        break;                                                                     \
-      default: return osg::set_error(OSG_ERR_INVALID, "bad game kind");            \
-    }                                                                              \
   } while (0)
 
 // Scratch helpers (device + pinned host staging owned by the context).

@@ -1590,10 +1590,6 @@ k_rollout_fold(const double* __restrict__ part, const int32_t* __restrict__ part
 // ---------------------------------------------------------------------------
 // host helpers
 // ---------------------------------------------------------------------------
-struct Staged {  // an argument that may live on the host: staged through ctx scratch
-  void* dev = nullptr;
-};
-
 int stage_in(osg_ctx* ctx, const void* ptr, size_t bytes, int on_host, size_t scratch_offset, const void** dev) {
   if (!on_host) { *dev = ptr; return OSG_OK; }
   void* scratch = nullptr;
@@ -1761,8 +1757,12 @@ int osg_batch_describe(const osg_batch* b, osg_game_desc* out) { *out = b->spec.
 void* osg_batch_device_ptr(osg_batch* b) { return b->d_words; }
 
 int osg_batch_reset(osg_batch* b) {
-  OSG_DISPATCH_WIDE(b->spec, k_init<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, b->ctx->stream>>>(P,
-                                            static_cast<typename G::word_t*>(b->d_words), b->n));
+  if (int rc = for_game(b->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_init<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, b->ctx->stream>>>(P,
+            static_cast<typename G::word_t*>(b->d_words), b->n);
+        return OSG_OK;
+      })) return rc;
   OSG_HIP(hipGetLastError());
   return OSG_OK;
 }
@@ -1787,10 +1787,14 @@ int osg_batch_gather(osg_batch* dst, const osg_batch* src, const int64_t* index,
   const void* d_index = nullptr;
   int rc = stage_in(dst->ctx, index, sizeof(int64_t) * dst->n, on_host, 0, &d_index);
   if (rc) return rc;
-  OSG_DISPATCH_WIDE(dst->spec, k_gather<G><<<dim3(grid_for(dst->n)), dim3(kBlock), 0, dst->ctx->stream>>>(P,
-                                              static_cast<typename G::word_t*>(dst->d_words), dst->n,
-                                              static_cast<const typename G::word_t*>(src->d_words), src->n,
-                                              static_cast<const int64_t*>(d_index), dst->ctx->d_illegal));
+  if (int rc = for_game(dst->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_gather<G><<<dim3(grid_for(dst->n)), dim3(kBlock), 0, dst->ctx->stream>>>(P,
+            static_cast<typename G::word_t*>(dst->d_words), dst->n,
+            static_cast<const typename G::word_t*>(src->d_words), src->n,
+            static_cast<const int64_t*>(d_index), dst->ctx->d_illegal);
+        return OSG_OK;
+      })) return rc;
   OSG_HIP(hipGetLastError());
   if (on_host) OSG_HIP(hipStreamSynchronize(dst->ctx->stream));
   return OSG_OK;
@@ -1828,27 +1832,17 @@ int osg_batch_set_cells(osg_batch* b, int64_t index, const char* cells, int n_ce
   unsigned char* d_cells = static_cast<unsigned char*>(scratch);
   int* d_err = reinterpret_cast<int*>(d_cells + 4096);
   OSG_HIP(hipMemcpyAsync(d_cells, cells, static_cast<size_t>(n_cells), hipMemcpyHostToDevice, ctx->stream));
-  const osg::GameSpec& spec = b->spec;
-  switch (spec.desc.game_kind) {
-    case osg::kTtt:
-      k_set_cells<osg::Ttt><<<dim3(1), dim3(64), 0, ctx->stream>>>(spec.ttt, static_cast<osg::Ttt::word_t*>(b->d_words), b->n, index,
-                                                                   d_cells, n_cells, d_err);
-      break;
-    case osg::kC4:
-      if (spec.c4_std)
-        k_set_cells<osg::C4Std><<<dim3(1), dim3(64), 0, ctx->stream>>>(spec.c4, static_cast<osg::C4Std::word_t*>(b->d_words), b->n, index,
-                                                                       d_cells, n_cells, d_err);
-      else if (spec.c4_wide)
-        k_set_cells<osg::C4Wide><<<dim3(1), dim3(64), 0, ctx->stream>>>(spec.c4, static_cast<osg::C4Wide::word_t*>(b->d_words), b->n, index,
-                                                                        d_cells, n_cells, d_err);
-      else
-        k_set_cells<osg::C4><<<dim3(1), dim3(64), 0, ctx->stream>>>(spec.c4, static_cast<osg::C4::word_t*>(b->d_words), b->n, index,
-                                                                    d_cells, n_cells, d_err);
-      break;
-    default:
-      return osg::set_error(OSG_ERR_UNSUPPORTED, "osg_batch_set_cells: tic_tac_toe and connect_four positions (the games whose "
-                                                 "reference State has a constructor from a board)");
-  }
+  if (int rc = for_game(b->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        if constexpr (std::is_same_v<G, Ttt> || std::is_same_v<typename G::Params, C4::Params>) {
+          k_set_cells<G><<<dim3(1), dim3(64), 0, ctx->stream>>>(P, static_cast<typename G::word_t*>(b->d_words), b->n, index,
+                                                                d_cells, n_cells, d_err);
+          return OSG_OK;
+        } else {
+          return osg::set_error(OSG_ERR_UNSUPPORTED, "osg_batch_set_cells: tic_tac_toe and connect_four positions (the games whose "
+                                                     "reference State has a constructor from a board)");
+        }
+      })) return rc;
   OSG_HIP(hipGetLastError());
   int err = 0;
   OSG_HIP(hipMemcpyAsync(&err, d_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -1873,8 +1867,12 @@ int osg_legal_mask(const osg_batch* b, uint32_t* mask, int on_host) {
     if (rc) return rc;
     d_mask = static_cast<uint32_t*>(scratch);
   }
-  OSG_DISPATCH_WIDE(b->spec, k_legal_mask<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
-                                            static_cast<const typename G::word_t*>(b->d_words), b->n, d_mask, W));
+  if (int rc = for_game(b->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_legal_mask<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
+            static_cast<const typename G::word_t*>(b->d_words), b->n, d_mask, W);
+        return OSG_OK;
+      })) return rc;
   OSG_HIP(hipGetLastError());
   if (on_host) {
     OSG_HIP(hipMemcpyAsync(mask, d_mask, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1888,9 +1886,13 @@ int osg_apply(osg_batch* b, const int32_t* actions, int on_host, int64_t* h_ille
   const void* d_actions = nullptr;
   int rc = stage_in(ctx, actions, sizeof(int32_t) * b->n, on_host, 0, &d_actions);
   if (rc) return rc;
-  OSG_DISPATCH_WIDE(b->spec, k_apply<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
-                                            static_cast<typename G::word_t*>(b->d_words), b->n,
-                                            static_cast<const int32_t*>(d_actions), ctx->d_illegal));
+  if (int rc = for_game(b->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_apply<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
+            static_cast<typename G::word_t*>(b->d_words), b->n,
+            static_cast<const int32_t*>(d_actions), ctx->d_illegal);
+        return OSG_OK;
+      })) return rc;
   OSG_HIP(hipGetLastError());
   if (on_host || h_illegal) return check_illegal(ctx, h_illegal);
   return OSG_OK;
@@ -1912,9 +1914,13 @@ int osg_status_query(const osg_batch* b, int8_t* cur_player, uint8_t* terminal, 
     d_term = terminal ? reinterpret_cast<uint8_t*>(sc + off_term) : nullptr;
     d_ret = returns ? reinterpret_cast<double*>(sc + off_ret) : nullptr;
   }
-  OSG_DISPATCH_WIDE(b->spec, k_status<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
-                                            static_cast<const typename G::word_t*>(b->d_words), b->n, P_, d_cur,
-                                            d_term, d_ret));
+  if (int rc = for_game(b->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_status<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
+            static_cast<const typename G::word_t*>(b->d_words), b->n, P_, d_cur,
+            d_term, d_ret);
+        return OSG_OK;
+      })) return rc;
   OSG_HIP(hipGetLastError());
   if (on_host) {
     if (cur_player) OSG_HIP(hipMemcpyAsync(cur_player, d_cur, b->n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1937,8 +1943,12 @@ int osg_chance_probs(const osg_batch* b, double* probs, int on_host) {
     if (rc) return rc;
     d_probs = static_cast<double*>(scratch);
   }
-  OSG_DISPATCH_WIDE(b->spec, k_chance_probs<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
-                                            static_cast<const typename G::word_t*>(b->d_words), b->n, C, d_probs));
+  if (int rc = for_game(b->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_chance_probs<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
+            static_cast<const typename G::word_t*>(b->d_words), b->n, C, d_probs);
+        return OSG_OK;
+      })) return rc;
   OSG_HIP(hipGetLastError());
   if (on_host) {
     OSG_HIP(hipMemcpyAsync(probs, d_probs, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -2031,29 +2041,21 @@ int osg_step(const osg_batch* src, osg_batch* dst, const uint8_t* d_actions, voi
       const auto* s32 = static_cast<const uint32_t*>(src->d_words);
       auto* d32 = static_cast<uint32_t*>(dst->d_words);
       auto* m32 = static_cast<uint32_t*>(d_mask);
-#define OSG_HEXVEC(NWV, VV, NTV, MASKV, FOLDV, member)                                                                              \
-  k_step_hexvec<NWV, VV, NTV, MASKV, FOLDV><<<dim3(grid_for(n / VV)), dim3(kBlock), 0, ctx->stream>>>(src->spec.member, s32, d32, n, \
-                                                                                                    d_actions, m32, d_status)
-#define OSG_HEXVEC_MASK(NWV, FOLDV, member)                                   \
-  do {                                                                        \
-    if (nt && m32) OSG_HEXVEC(NWV, 2, true, true, FOLDV, member);             \
-    else if (nt) OSG_HEXVEC(NWV, 2, true, false, FOLDV, member);              \
-    else if (m32) OSG_HEXVEC(NWV, 2, false, true, FOLDV, member);             \
-    else OSG_HEXVEC(NWV, 2, false, false, FOLDV, member);                     \
-  } while (0)
-#define OSG_HEXVEC_NW(NWV, member)                                                                          \
-  do {                                                                                                      \
-    if (src->spec.hex_fold) OSG_HEXVEC_MASK(NWV, true, member); else OSG_HEXVEC_MASK(NWV, false, member);   \
-  } while (0)
-      switch (src->spec.hex_nw) {
-        case 1: OSG_HEXVEC_NW(1, hex1); break;
-        case 2: OSG_HEXVEC_NW(2, hex2); break;
-        case 3: OSG_HEXVEC_NW(3, hex3); break;
-        default: OSG_HEXVEC_NW(4, hex4); break;
-      }
-#undef OSG_HEXVEC_MASK
-#undef OSG_HEXVEC_NW
-#undef OSG_HEXVEC
+      if (int rc = for_hex(src->spec, [&](auto nw, const auto& P) -> int {
+            constexpr int NW = decltype(nw)::value;
+            if constexpr (NW <= 4) {   // (the test above: W <= 4)
+              return with_bool(src->spec.hex_fold, [&](auto fold) {
+                return with_bool(nt != 0, [&](auto ntv) {
+                  return with_bool(m32 != nullptr, [&](auto mask) {
+                    k_step_hexvec<NW, 2, decltype(ntv)::value, decltype(mask)::value, decltype(fold)::value>
+                        <<<dim3(grid_for(n / 2)), dim3(kBlock), 0, ctx->stream>>>(P, s32, d32, n, d_actions, m32, d_status);
+                    return OSG_OK;
+                  });
+                });
+              });
+            }
+            return OSG_OK;
+          })) return rc;
       OSG_HIP(hipGetLastError());
       return OSG_OK;
     }
@@ -2062,19 +2064,17 @@ int osg_step(const osg_batch* src, osg_batch* dst, const uint8_t* d_actions, voi
     return set_error(OSG_ERR_UNSUPPORTED, "osg_step: d_mask may be NULL only for hex boards of up to 128 cells stepped two states per "
                                           "thread (an even batch, 2-byte aligned side arrays): there the successor's mask is ~occupied "
                                           "of the record written; every other game's mask is computed by the step itself");
-  if (cmb == 1) {
-    OSG_DISPATCH_WIDE(src->spec, k_step<G, uint8_t><<<dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream>>>(P, static_cast<const typename G::word_t*>(src->d_words),
-                                                static_cast<typename G::word_t*>(dst->d_words), n, d_actions,
-                                                static_cast<uint8_t*>(d_mask), 1, d_status));
-  } else if (cmb == 2) {
-    OSG_DISPATCH_WIDE(src->spec, k_step<G, uint16_t><<<dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream>>>(P, static_cast<const typename G::word_t*>(src->d_words),
-                                                static_cast<typename G::word_t*>(dst->d_words), n, d_actions,
-                                                static_cast<uint16_t*>(d_mask), 1, d_status));
-  } else {
-    OSG_DISPATCH_WIDE(src->spec, k_step<G, uint32_t><<<dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream>>>(P, static_cast<const typename G::word_t*>(src->d_words),
-                                                static_cast<typename G::word_t*>(dst->d_words), n, d_actions,
-                                                static_cast<uint32_t*>(d_mask), W, d_status));
-  }
+  const auto step = [&](auto m, int mask_stride) {   // m: one element of the compact mask
+    using M = decltype(m);
+    return for_game(src->spec, [&](auto g, const auto& P) {
+      using G = typename decltype(g)::type;
+      k_step<G, M><<<dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream>>>(P, static_cast<const typename G::word_t*>(src->d_words),
+          static_cast<typename G::word_t*>(dst->d_words), n, d_actions,
+          static_cast<M*>(d_mask), mask_stride, d_status);
+      return OSG_OK;
+    });
+  };
+  if (int rc = cmb == 1 ? step(uint8_t{}, 1) : cmb == 2 ? step(uint16_t{}, 1) : step(uint32_t{}, W)) return rc;
   OSG_HIP(hipGetLastError());
   return OSG_OK;
 }
@@ -2108,12 +2108,24 @@ int osg_observation(const osg_batch* b, int player, int which, float* out, int o
   static const int obs_lds_env = std::getenv("OSG_OBS_LDS") ? std::atoi(std::getenv("OSG_OBS_LDS")) : -1;
   const int obs_lds = obs_lds_env >= 0 ? obs_lds_env : (b->spec.desc.game_kind == kTtt ? 8 : 4);
   const unsigned piece_grid = static_cast<unsigned>(((total + 1023) / 1024 + 3) / 4);   // four 1 KiB-piece spans per workgroup
+  // the piece form of a game whose rows come from a functor f, `spans` 1 KiB-piece spans per thread
+  const auto row_pieces = [&](auto f, auto spans, unsigned grid) {
+    uint32_t magic = 0, shift = 0;
+    find_div_magic(static_cast<uint32_t>(size), static_cast<uint32_t>(size) + 1024u, &magic, &shift);
+    return with_bool(nt, [&](auto ntv) {
+      k_observation_row_pieces<decltype(f), decltype(ntv)::value, decltype(spans)::value><<<dim3(grid), dim3(kPieceBlock), 0, ctx->stream>>>(
+          f, static_cast<uint32_t>(b->n), make_fast_div(static_cast<uint32_t>(size)), magic, shift, static_cast<uint32_t>(total), d_out);
+      return OSG_OK;
+    });
+  };
   if (pieces && b->spec.desc.game_kind == kC4 && b->spec.c4_std) {
-#define OSG_C4P(NT, EGO) k_observation_c4std_pieces<NT, EGO, 4><<<dim3(piece_grid), dim3(kPieceBlock), 0, ctx->stream>>>( \
-      b->spec.c4, static_cast<const uint64_t*>(b->d_words), static_cast<uint32_t>(b->n), static_cast<uint32_t>(total), player, d_out)
-    if (b->spec.c4.ego) { if (nt) OSG_C4P(true, true); else OSG_C4P(false, true); }
-    else { if (nt) OSG_C4P(true, false); else OSG_C4P(false, false); }
-#undef OSG_C4P
+    with_bool(b->spec.c4.ego, [&](auto ego) {
+      return with_bool(nt, [&](auto ntv) {
+        k_observation_c4std_pieces<decltype(ntv)::value, decltype(ego)::value, 4><<<dim3(piece_grid), dim3(kPieceBlock), 0, ctx->stream>>>(
+            b->spec.c4, static_cast<const uint64_t*>(b->d_words), static_cast<uint32_t>(b->n), static_cast<uint32_t>(total), player, d_out);
+        return OSG_OK;
+      });
+    });
   } else if (pieces && obs_lds && (b->spec.desc.game_kind == kTtt || (b->spec.desc.game_kind == kLeduc && d.num_players == 2))) {
     // the rows' images staged in LDS (k_observation_row_pieces_lds)
     uint32_t magic = 0, shift = 0, cmagic = 0, cshift = 0;
@@ -2123,61 +2135,36 @@ int osg_observation(const osg_batch* b, int player, int which, float* out, int o
       return set_error(OSG_ERR_INVALID, "osg_observation: no multiply-shift pair for this row size");
     const FastDiv fd = make_fast_div(static_cast<uint32_t>(size));
     const uint32_t nn = static_cast<uint32_t>(b->n), tot = static_cast<uint32_t>(total);
-#define OSG_ROWL(F, f, SP) do {                                                                                              \
-      const unsigned g = static_cast<unsigned>(((total + 1023) / 1024 + (SP) - 1) / (SP));                                     \
-      const size_t lds = sizeof(typename F::Img) * (SP) * cap;                                                                 \
-      if (nt) k_observation_row_pieces_lds<F, true, SP><<<dim3(g), dim3(kPieceBlock), lds, ctx->stream>>>(f, nn, fd, magic, shift, cap, cmagic, cshift, tot, d_out); \
-      else k_observation_row_pieces_lds<F, false, SP><<<dim3(g), dim3(kPieceBlock), lds, ctx->stream>>>(f, nn, fd, magic, shift, cap, cmagic, cshift, tot, d_out);  \
-    } while (0)
+    const auto rows_lds = [&](auto f) {   // f: the game's piece functor
+      return with_int<8, 4>(obs_lds, [&](auto sp) {
+        return with_bool(nt, [&](auto ntv) {
+          constexpr int SP = decltype(sp)::value;
+          const unsigned g = static_cast<unsigned>(((total + 1023) / 1024 + SP - 1) / SP);
+          const size_t lds = sizeof(typename decltype(f)::Img) * SP * cap;
+          k_observation_row_pieces_lds<decltype(f), decltype(ntv)::value, SP><<<dim3(g), dim3(kPieceBlock), lds, ctx->stream>>>(
+              f, nn, fd, magic, shift, cap, cmagic, cshift, tot, d_out);
+          return OSG_OK;
+        });
+      });
+    };
     if (b->spec.desc.game_kind == kTtt) {
-      TttPieces f{static_cast<const uint32_t*>(b->d_words)};
-      if (obs_lds == 8) OSG_ROWL(TttPieces, f, 8); else OSG_ROWL(TttPieces, f, 4);
+      rows_lds(TttPieces{static_cast<const uint32_t*>(b->d_words)});
     } else {
       const int K = b->spec.leduc.iso ? b->spec.leduc.cards / 2 : b->spec.leduc.cards;
-      if (which == 0) {
-        Leduc2Pieces<0> f{static_cast<const uint64_t*>(b->d_words), nn, player, K, b->spec.leduc};
-        if (obs_lds == 8) OSG_ROWL(Leduc2Pieces<0>, f, 8); else OSG_ROWL(Leduc2Pieces<0>, f, 4);
-      } else {
-        Leduc2Pieces<1> f{static_cast<const uint64_t*>(b->d_words), nn, player, K, b->spec.leduc};
-        if (obs_lds == 8) OSG_ROWL(Leduc2Pieces<1>, f, 8); else OSG_ROWL(Leduc2Pieces<1>, f, 4);
-      }
+      if (which == 0) rows_lds(Leduc2Pieces<0>{static_cast<const uint64_t*>(b->d_words), nn, player, K, b->spec.leduc});
+      else rows_lds(Leduc2Pieces<1>{static_cast<const uint64_t*>(b->d_words), nn, player, K, b->spec.leduc});
     }
-#undef OSG_ROWL
   } else if (pieces && b->spec.desc.game_kind == kTtt) {
-    uint32_t magic = 0, shift = 0;
-    find_div_magic(static_cast<uint32_t>(size), static_cast<uint32_t>(size) + 1024u, &magic, &shift);
-    TttPieces f{static_cast<const uint32_t*>(b->d_words)};
     // eight spans per thread here (27-float rows: 0.74 with four, 0.76 with eight; the round-3 kernel: 0.69)
-    const unsigned g8 = (piece_grid + 1) / 2;
-    if (nt) k_observation_row_pieces<TttPieces, true, 8><<<dim3(g8), dim3(kPieceBlock), 0, ctx->stream>>>(
-        f, static_cast<uint32_t>(b->n), make_fast_div(static_cast<uint32_t>(size)), magic, shift, static_cast<uint32_t>(total), d_out);
-    else k_observation_row_pieces<TttPieces, false, 8><<<dim3(g8), dim3(kPieceBlock), 0, ctx->stream>>>(
-        f, static_cast<uint32_t>(b->n), make_fast_div(static_cast<uint32_t>(size)), magic, shift, static_cast<uint32_t>(total), d_out);
+    row_pieces(TttPieces{static_cast<const uint32_t*>(b->d_words)}, std::integral_constant<int, 8>{}, (piece_grid + 1) / 2);
   } else if (pieces && b->spec.desc.game_kind == kKuhn && d.num_players == 2) {
-    uint32_t magic = 0, shift = 0;
-    find_div_magic(static_cast<uint32_t>(size), static_cast<uint32_t>(size) + 1024u, &magic, &shift);
-#define OSG_KUHNP(W) do {                                                                                               \
-      Kuhn2Pieces<W> f{static_cast<const uint64_t*>(b->d_words), player};                                               \
-      if (nt) k_observation_row_pieces<Kuhn2Pieces<W>, true, 4><<<dim3(piece_grid), dim3(kPieceBlock), 0, ctx->stream>>>( \
-          f, static_cast<uint32_t>(b->n), make_fast_div(static_cast<uint32_t>(size)), magic, shift, static_cast<uint32_t>(total), d_out); \
-      else k_observation_row_pieces<Kuhn2Pieces<W>, false, 4><<<dim3(piece_grid), dim3(kPieceBlock), 0, ctx->stream>>>(  \
-          f, static_cast<uint32_t>(b->n), make_fast_div(static_cast<uint32_t>(size)), magic, shift, static_cast<uint32_t>(total), d_out); \
-    } while (0)
-    if (which == 0) OSG_KUHNP(0); else OSG_KUHNP(1);
-#undef OSG_KUHNP
+    if (which == 0) row_pieces(Kuhn2Pieces<0>{static_cast<const uint64_t*>(b->d_words), player}, std::integral_constant<int, 4>{}, piece_grid);
+    else row_pieces(Kuhn2Pieces<1>{static_cast<const uint64_t*>(b->d_words), player}, std::integral_constant<int, 4>{}, piece_grid);
   } else if (pieces && b->spec.desc.game_kind == kLeduc && d.num_players == 2) {
-    uint32_t magic = 0, shift = 0;
-    find_div_magic(static_cast<uint32_t>(size), static_cast<uint32_t>(size) + 1024u, &magic, &shift);
     const int K = b->spec.leduc.iso ? b->spec.leduc.cards / 2 : b->spec.leduc.cards;
-#define OSG_LEDUCP(W) do {                                                                                              \
-      Leduc2Pieces<W> f{static_cast<const uint64_t*>(b->d_words), static_cast<uint32_t>(b->n), player, K, b->spec.leduc}; \
-      if (nt) k_observation_row_pieces<Leduc2Pieces<W>, true, 4><<<dim3(piece_grid), dim3(kPieceBlock), 0, ctx->stream>>>( \
-          f, static_cast<uint32_t>(b->n), make_fast_div(static_cast<uint32_t>(size)), magic, shift, static_cast<uint32_t>(total), d_out); \
-      else k_observation_row_pieces<Leduc2Pieces<W>, false, 4><<<dim3(piece_grid), dim3(kPieceBlock), 0, ctx->stream>>>(  \
-          f, static_cast<uint32_t>(b->n), make_fast_div(static_cast<uint32_t>(size)), magic, shift, static_cast<uint32_t>(total), d_out); \
-    } while (0)
-    if (which == 0) OSG_LEDUCP(0); else OSG_LEDUCP(1);
-#undef OSG_LEDUCP
+    const uint32_t nn = static_cast<uint32_t>(b->n);
+    if (which == 0) row_pieces(Leduc2Pieces<0>{static_cast<const uint64_t*>(b->d_words), nn, player, K, b->spec.leduc}, std::integral_constant<int, 4>{}, piece_grid);
+    else row_pieces(Leduc2Pieces<1>{static_cast<const uint64_t*>(b->d_words), nn, player, K, b->spec.leduc}, std::integral_constant<int, 4>{}, piece_grid);
   } else if (pieces && b->spec.desc.game_kind == kHex && which == 0 && d.obs_shape[0] == 9 &&
              d.obs_shape[1] * d.obs_shape[2] >= 29) {   // (a span of 4096 floats then touches at most 18 states)
     const uint32_t cells = static_cast<uint32_t>(d.obs_shape[1] * d.obs_shape[2]);
@@ -2185,19 +2172,14 @@ int osg_observation(const osg_batch* b, int player, int which, float* out, int o
     if (!find_div_magic(cells, 9u * cells, &cm, &cs) || !find_div_magic(9u * cells, 9u * cells + kHexLdsSpan, &lm, &ls))
       return set_error(OSG_ERR_INVALID, "osg_observation: no multiply-shift pair for this hex board");
     const unsigned g = static_cast<unsigned>(((total + kHexLdsSpan - 1) / kHexLdsSpan + 3) / 4);
-#define OSG_HEXL(NW, NT) k_observation_hex_pieces_lds<NW, NT, 4><<<dim3(g), dim3(kPieceBlock), 0, ctx->stream>>>(               \
-      static_cast<const uint32_t*>(b->d_words), static_cast<uint32_t>(b->n), cells, cm, cs, make_fast_div(9u * cells), lm, ls,    \
-      static_cast<uint32_t>(total), d_out, b->spec.hex_fold ? 0x07FFFFFFu : 0xFFFFFFFFu)
-    switch (b->spec.hex_nw) {
-      case 1: if (nt) OSG_HEXL(1, true); else OSG_HEXL(1, false); break;
-      case 2: if (nt) OSG_HEXL(2, true); else OSG_HEXL(2, false); break;
-      case 3: if (nt) OSG_HEXL(3, true); else OSG_HEXL(3, false); break;
-      case 4: if (nt) OSG_HEXL(4, true); else OSG_HEXL(4, false); break;
-      case 6: if (nt) OSG_HEXL(6, true); else OSG_HEXL(6, false); break;
-      case 8: if (nt) OSG_HEXL(8, true); else OSG_HEXL(8, false); break;
-      default: if (nt) OSG_HEXL(12, true); else OSG_HEXL(12, false); break;
-    }
-#undef OSG_HEXL
+    for_hex(b->spec, [&](auto nw, const auto&) {
+      return with_bool(nt, [&](auto ntv) {
+        k_observation_hex_pieces_lds<decltype(nw)::value, decltype(ntv)::value, 4><<<dim3(g), dim3(kPieceBlock), 0, ctx->stream>>>(
+            static_cast<const uint32_t*>(b->d_words), static_cast<uint32_t>(b->n), cells, cm, cs, make_fast_div(9u * cells), lm, ls,
+            static_cast<uint32_t>(total), d_out, b->spec.hex_fold ? 0x07FFFFFFu : 0xFFFFFFFFu);
+        return OSG_OK;
+      });
+    });
   } else if (b->spec.desc.game_kind == kC4 && b->spec.c4_std) {
     if ((reinterpret_cast<uintptr_t>(d_out) & 15u) == 0 && b->n >= (int64_t{1} << 22))
       k_observation_c4std_planes<true><<<dim3(static_cast<unsigned>((b->n * 3 + kC4ObsBlock - 1) / kC4ObsBlock)),
@@ -2214,16 +2196,12 @@ int osg_observation(const osg_batch* b, int player, int which, float* out, int o
              (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0) {   // (its LDS stage is 256 B per cell: the big boards go below)
     const size_t shmem = sizeof(float) * kHexObsBlock * static_cast<size_t>(d.obs_shape[1] * d.obs_shape[2]);
     const unsigned grid = static_cast<unsigned>((b->n * 9 + kHexObsBlock - 1) / kHexObsBlock);
-#define OSG_HEX_OBS(NW, member)                                                                        \
-  k_observation_hex_planes<HexT<NW>><<<dim3(grid), dim3(kHexObsBlock), shmem, ctx->stream>>>(          \
-      b->spec.member, static_cast<const uint32_t*>(b->d_words), b->n, 9, d_out)
-    switch (b->spec.hex_nw) {
-      case 1: OSG_HEX_OBS(1, hex1); break;
-      case 2: OSG_HEX_OBS(2, hex2); break;
-      case 3: OSG_HEX_OBS(3, hex3); break;
-      default: OSG_HEX_OBS(4, hex4); break;
-    }
-#undef OSG_HEX_OBS
+    for_hex(b->spec, [&](auto nw, const auto& P) {
+      if constexpr (decltype(nw)::value <= 4)
+        k_observation_hex_planes<HexT<decltype(nw)::value>><<<dim3(grid), dim3(kHexObsBlock), shmem, ctx->stream>>>(
+            P, static_cast<const uint32_t*>(b->d_words), b->n, 9, d_out);
+      return OSG_OK;
+    });
   } else if (size <= kRowsMaxSize && b->spec.desc.game_kind != kHex && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0) {
     // short rows: one lane per state, LDS-staged aligned float4 stores
     // states per lane: two for the shortest rows (measured at 2^24 states, 1 / 2 / 4 per lane: kuhn [n, 7] 124.8 / 103.5 /
@@ -2232,12 +2210,14 @@ int osg_observation(const osg_batch* b, int player, int which, float* out, int o
     const int kr = size <= 12 ? 2 : 1;
     const size_t shmem = sizeof(float) * (kRowsBlock / 64) * 64 * kr * static_cast<size_t>(size | 1);
     const unsigned grid = static_cast<unsigned>((b->n + kRowsBlock * kr - 1) / (kRowsBlock * kr));
-#define OSG_ROWS(KR)                                                                                               \
-  OSG_DISPATCH_WIDE(b->spec, k_observation_rows<G, KR><<<dim3(grid), dim3(kRowsBlock), shmem, ctx->stream>>>(           \
-                            P, static_cast<const typename G::word_t*>(b->d_words), b->n, size, player, which, d_out))
-    if (kr == 2) OSG_ROWS(2);
-    else OSG_ROWS(1);
-#undef OSG_ROWS
+    if (int rc = with_int<2, 1>(kr, [&](auto krv) {
+          return for_game(b->spec, [&](auto g, const auto& P) {
+            using G = typename decltype(g)::type;
+            k_observation_rows<G, decltype(krv)::value><<<dim3(grid), dim3(kRowsBlock), shmem, ctx->stream>>>(
+                P, static_cast<const typename G::word_t*>(b->d_words), b->n, size, player, which, d_out);
+            return OSG_OK;
+          });
+        })) return rc;
   } else {
     // Segment = one tensor plane for hex's 9-plane layout (the cursor's mask is per plane), else the row.
     int seg_len = size;
@@ -2249,13 +2229,15 @@ int osg_observation(const osg_batch* b, int player, int which, float* out, int o
     const int F = wide ? 16 : 4;
     const int cps = (seg_len + F - 1) / F;
     const int64_t lanes = b->n * (size / seg_len) * cps;
-#define OSG_OBS_LAUNCH(FF)                                                                                          \
-  OSG_DISPATCH_WIDE(b->spec, k_observation<G, FF><<<dim3(grid_for(lanes)), dim3(kBlock), 0, ctx->stream>>>(P,            \
-                                            static_cast<const typename G::word_t*>(b->d_words), b->n, size, seg_len, \
-                                            cps, player, which, d_out))
-    if (F == 16) OSG_OBS_LAUNCH(16);
-    else OSG_OBS_LAUNCH(4);
-#undef OSG_OBS_LAUNCH
+    if (int rc = with_int<16, 4>(F, [&](auto ff) {
+          return for_game(b->spec, [&](auto g, const auto& P) {
+            using G = typename decltype(g)::type;
+            k_observation<G, decltype(ff)::value><<<dim3(grid_for(lanes)), dim3(kBlock), 0, ctx->stream>>>(P,
+                static_cast<const typename G::word_t*>(b->d_words), b->n, size, seg_len,
+                cps, player, which, d_out);
+            return OSG_OK;
+          });
+        })) return rc;
   }
   OSG_HIP(hipGetLastError());
   if (on_host) {
@@ -2271,9 +2253,13 @@ int osg_random_steps(osg_batch* b, uint64_t seed, int64_t index_offset, int step
   int64_t blocks = (b->n + kBlock - 1) / kBlock;
   constexpr int64_t kMaxBlocks = 4096;
   if (blocks > kMaxBlocks) blocks = kMaxBlocks;  // 16 workgroups per CU (4096 measured 4 % faster than 2048), grid-strided beyond
-  OSG_DISPATCH_WIDE(b->spec, k_random_steps<G><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, ctx->stream>>>(P,
-                                            static_cast<typename G::word_t*>(b->d_words), b->n, seed, index_offset,
-                                            steps, partials));
+  if (int rc = for_game(b->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_random_steps<G><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, ctx->stream>>>(P,
+            static_cast<typename G::word_t*>(b->d_words), b->n, seed, index_offset,
+            steps, partials);
+        return OSG_OK;
+      })) return rc;
   k_fold_counters<<<dim3(1), dim3(64), 0, ctx->stream>>>(partials, d_counters);
   OSG_HIP(hipGetLastError());
   return OSG_OK;
@@ -2289,9 +2275,13 @@ int osg_synth_batch(osg_batch* b, uint64_t seed, int64_t index_offset, int depth
     return set_error(OSG_ERR_UNSUPPORTED, "osg_synth_batch: d_actions holds one byte per action; pass NULL for games with more "
                                           "than 255 actions");
   osg_ctx* ctx = b->ctx;
-  OSG_DISPATCH_WIDE(b->spec, k_synth<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
-                                     static_cast<typename G::word_t*>(b->d_words), b->n, seed, index_offset, depth_mod,
-                                     d_actions, d_depth));
+  if (int rc = for_game(b->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_synth<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
+            static_cast<typename G::word_t*>(b->d_words), b->n, seed, index_offset, depth_mod,
+            d_actions, d_depth);
+        return OSG_OK;
+      })) return rc;
   OSG_HIP(hipGetLastError());
   return OSG_OK;
 }
@@ -2329,13 +2319,21 @@ int osg_rollout(const osg_batch* roots, uint64_t seed, int64_t index_offset, int
   int64_t blocks = (total + kBlock - 1) / kBlock;
   if (blocks > 2048) blocks = 2048;
   if (!steps && roots->spec.desc.game_kind == kHex) {
-    OSG_DISPATCH_WIDE(roots->spec, launch_rollout_hexfill<G>(P, roots->d_words, n, seed, index_offset, n_rollouts,
-                                                             static_cast<int>(group), d_part, static_cast<unsigned>(blocks), ctx->stream));
+    if (int rc = for_game(roots->spec, [&](auto g, const auto& P) {
+          using G = typename decltype(g)::type;
+          launch_rollout_hexfill<G>(P, roots->d_words, n, seed, index_offset, n_rollouts,
+              static_cast<int>(group), d_part, static_cast<unsigned>(blocks), ctx->stream);
+          return OSG_OK;
+        })) return rc;
   } else {
-  OSG_DISPATCH_WIDE(roots->spec, k_rollout<G><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, ctx->stream>>>(P,
-                                                static_cast<const typename G::word_t*>(roots->d_words), n, P_, seed,
-                                                index_offset, n_rollouts, static_cast<int>(group), d_part,
-                                                d_part_steps));
+  if (int rc = for_game(roots->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_rollout<G><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, ctx->stream>>>(P,
+            static_cast<const typename G::word_t*>(roots->d_words), n, P_, seed,
+            index_offset, n_rollouts, static_cast<int>(group), d_part,
+            d_part_steps);
+        return OSG_OK;
+      })) return rc;
   }
   if (group > 1)
     k_rollout_fold<<<dim3(grid_for(n * P_)), dim3(kBlock), 0, ctx->stream>>>(d_part, d_part_steps, n, P_,
@@ -2375,11 +2373,15 @@ int osg_env_step(osg_batch* b, const int32_t* d_actions, uint8_t* d_should_reset
       return OSG_OK;
     }
   }
-  OSG_DISPATCH_WIDE(b->spec, k_env_step<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
-                                            static_cast<typename G::word_t*>(b->d_words), b->n,
-                                            b->spec.desc.num_players, d_actions, d_should_reset, seed, index_offset,
-                                            step_index, d_cur_player, d_step_type, d_rewards, d_mask,
-                                            b->spec.desc.mask_words, ctx->d_illegal));
+  if (int rc = for_game(b->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_env_step<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
+            static_cast<typename G::word_t*>(b->d_words), b->n,
+            b->spec.desc.num_players, d_actions, d_should_reset, seed, index_offset,
+            step_index, d_cur_player, d_step_type, d_rewards, d_mask,
+            b->spec.desc.mask_words, ctx->d_illegal);
+        return OSG_OK;
+      })) return rc;
   OSG_HIP(hipGetLastError());
   return OSG_OK;
 }
@@ -2410,10 +2412,14 @@ int osg_env_step_compact(osg_batch* b, const uint8_t* d_actions, uint8_t* d_flag
       return OSG_OK;
     }
   }
-  OSG_DISPATCH_WIDE(b->spec, k_env_step_compact<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
-                                            static_cast<typename G::word_t*>(b->d_words), b->n, b->spec.desc.num_players, d_actions,
-                                            d_flags, seed, index_offset, step_index, d_rewards_x2, d_mask, b->spec.desc.mask_words,
-                                            ctx->d_illegal));
+  if (int rc = for_game(b->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_env_step_compact<G><<<dim3(grid_for(b->n)), dim3(kBlock), 0, ctx->stream>>>(P,
+            static_cast<typename G::word_t*>(b->d_words), b->n, b->spec.desc.num_players, d_actions,
+            d_flags, seed, index_offset, step_index, d_rewards_x2, d_mask, b->spec.desc.mask_words,
+            ctx->d_illegal);
+        return OSG_OK;
+      })) return rc;
   OSG_HIP(hipGetLastError());
   return OSG_OK;
 }

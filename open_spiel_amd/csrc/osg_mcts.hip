@@ -470,15 +470,15 @@ extern "C" int osg_mcts_search(const osg_batch* roots, const osg_mcts_cfg* cfg_i
     const unsigned grid = static_cast<unsigned>((n + kBlockM - 1) / kBlockM);
     // the expansion's shuffle stage: one entry per child of the widest node and lane (two bytes above 255 actions)
     const size_t shuffle_lds = A > 32 * 6 ? 0 : static_cast<size_t>(widest) * kBlockM;   // (HexT<8>, HexT<12> shuffle on the pool)
-    if (board) {
-      OSG_DISPATCH_WIDE(roots->spec, k_mcts<G, true><<<dim3(grid), dim3(kBlockM), shuffle_lds, ctx->stream>>>(
-                                    P, static_cast<const typename G::word_t*>(roots->d_words), n, d.num_players, A, cfg,
-                                    d.max_utility, d_logs, pool, d_best, d_vis, d_rew, d_out, d_stats));
-    } else {
-      OSG_DISPATCH_WIDE(roots->spec, k_mcts<G, false><<<dim3(grid), dim3(kBlockM), shuffle_lds, ctx->stream>>>(
-                                    P, static_cast<const typename G::word_t*>(roots->d_words), n, d.num_players, A, cfg,
-                                    d.max_utility, d_logs, pool, d_best, d_vis, d_rew, d_out, d_stats));
-    }
+    if (int rc = with_bool(board, [&](auto brd) {
+          return for_game(roots->spec, [&](auto g, const auto& P) {
+            using G = typename decltype(g)::type;
+            k_mcts<G, decltype(brd)::value><<<dim3(grid), dim3(kBlockM), shuffle_lds, ctx->stream>>>(
+                P, static_cast<const typename G::word_t*>(roots->d_words), n, d.num_players, A, cfg,
+                d.max_utility, d_logs, pool, d_best, d_vis, d_rew, d_out, d_stats);
+            return OSG_OK;
+          });
+        })) return rc;
     OSG_HIP(hipGetLastError());
   }
   if (on_host) {

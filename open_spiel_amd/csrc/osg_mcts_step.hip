@@ -1005,42 +1005,34 @@ int osg_mcts_tree_advance(osg_mcts_tree* t, osg_batch* leaf, const double* d_pri
     // the LDS part of the tree is 144 KiB of dynamic shared memory: above the default limit, asked for once per
     // (device, kernel) (raise_lds_cap); a device that cannot grant it keeps the one-lane form below
     hipError_t e = hipSuccess;
-    if (t->board) OSG_DISPATCH_WIDE(t->roots->spec, e = raise_lds_cap(reinterpret_cast<const void*>(&k_mcts_advance<G, true, true>),
-                                                                      static_cast<int>(kLdsTreeBytes)));
-    else OSG_DISPATCH_WIDE(t->roots->spec, e = raise_lds_cap(reinterpret_cast<const void*>(&k_mcts_advance<G, false, true>),
-                                                             static_cast<int>(kLdsTreeBytes)));
+    if (int rc = with_bool(t->board, [&](auto board) {
+          return for_game(t->roots->spec, [&](auto g, const auto&) {
+            using G = typename decltype(g)::type;
+            e = raise_lds_cap(reinterpret_cast<const void*>(&k_mcts_advance<G, decltype(board)::value, true>),
+                              static_cast<int>(kLdsTreeBytes));
+            return OSG_OK;
+          });
+        })) return rc;
     if (e != hipSuccess) {
       (void)hipGetLastError();
       coop = false;
     }
   }
-  if (coop) {
-    if (t->board) {
-      OSG_DISPATCH_WIDE(t->roots->spec, k_mcts_advance<G, true, true><<<dim3(1), dim3(2 * kBlockM), kLdsTreeBytes, st>>>(
-                                       P, static_cast<const typename G::word_t*>(t->roots->d_words),
-                                       static_cast<typename G::word_t*>(leaf->d_words), t->n, d.num_players, t->A, t->cfg,
-                                       t->flags, t->max_utility, t->d_logs, pool, d_prior, d_value, d_request,
-                                       max_new_simulations, 1));
-    } else {
-      OSG_DISPATCH_WIDE(t->roots->spec, k_mcts_advance<G, false, true><<<dim3(1), dim3(2 * kBlockM), kLdsTreeBytes, st>>>(
-                                       P, static_cast<const typename G::word_t*>(t->roots->d_words),
-                                       static_cast<typename G::word_t*>(leaf->d_words), t->n, d.num_players, t->A, t->cfg,
-                                       t->flags, t->max_utility, t->d_logs, pool, d_prior, d_value, d_request,
-                                       max_new_simulations, 1));
-    }
-  } else if (t->board) {
-    OSG_DISPATCH_WIDE(t->roots->spec, k_mcts_advance<G, true><<<dim3(grid), dim3(kBlockM), 0, st>>>(
-                                     P, static_cast<const typename G::word_t*>(t->roots->d_words),
-                                     static_cast<typename G::word_t*>(leaf->d_words), t->n, d.num_players, t->A, t->cfg,
-                                     t->flags, t->max_utility, t->d_logs, pool, d_prior, d_value, d_request,
-                                     max_new_simulations, lane_stride));
-  } else {
-    OSG_DISPATCH_WIDE(t->roots->spec, k_mcts_advance<G, false><<<dim3(grid), dim3(kBlockM), 0, st>>>(
-                                     P, static_cast<const typename G::word_t*>(t->roots->d_words),
-                                     static_cast<typename G::word_t*>(leaf->d_words), t->n, d.num_players, t->A, t->cfg,
-                                     t->flags, t->max_utility, t->d_logs, pool, d_prior, d_value, d_request,
-                                     max_new_simulations, lane_stride));
-  }
+  const auto advance = [&](auto co, unsigned blocks, unsigned threads, size_t lds, int stride) {
+    return with_bool(t->board, [&](auto board) {
+      return for_game(t->roots->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_mcts_advance<G, decltype(board)::value, decltype(co)::value><<<dim3(blocks), dim3(threads), lds, st>>>(
+            P, static_cast<const typename G::word_t*>(t->roots->d_words),
+            static_cast<typename G::word_t*>(leaf->d_words), t->n, d.num_players, t->A, t->cfg,
+            t->flags, t->max_utility, t->d_logs, pool, d_prior, d_value, d_request,
+            max_new_simulations, stride);
+        return OSG_OK;
+      });
+    });
+  };
+  if (int rc = coop ? advance(std::true_type{}, 1, 2 * kBlockM, kLdsTreeBytes, 1)
+                    : advance(std::false_type{}, grid, kBlockM, 0, lane_stride)) return rc;
   OSG_HIP(hipGetLastError());
   if (h_counts) {  // how many searches are finished / want a prior / want a value / were paused by max_new_simulations
     std::vector<uint8_t> req(static_cast<size_t>(t->n));
@@ -1097,9 +1089,13 @@ int osg_mcts_tree_rollout_values(osg_mcts_tree* t, const osg_batch* leaf, double
   const int lane_stride = lane_stride_for(t->ctx, t->n);
   const unsigned grid = static_cast<unsigned>((t->n * lane_stride + kBlockM - 1) / kBlockM);
   const StepPool pool = make_pool(t);
-  OSG_DISPATCH_WIDE(t->roots->spec, k_mcts_tree_rollout<G><<<dim3(grid), dim3(kBlockM), 0, t->ctx->stream>>>(
-                                   P, static_cast<const typename G::word_t*>(leaf->d_words), t->n, t->P, t->cfg, pool.phase,
-                                   pool.sims, d_value, lane_stride));
+  if (int rc = for_game(t->roots->spec, [&](auto g, const auto& P) {
+        using G = typename decltype(g)::type;
+        k_mcts_tree_rollout<G><<<dim3(grid), dim3(kBlockM), 0, t->ctx->stream>>>(
+            P, static_cast<const typename G::word_t*>(leaf->d_words), t->n, t->P, t->cfg, pool.phase,
+            pool.sims, d_value, lane_stride);
+        return OSG_OK;
+      })) return rc;
   OSG_HIP(hipGetLastError());
   return OSG_OK;
 }

@@ -1539,32 +1539,23 @@ int launch_mcts_wave(const osg_batch* roots, const osg_mcts_cfg& cfg, const doub
       break;
     case kKuhn: rc = launch<Kuhn, false, false>(spec.kuhn, roots, cfg, d_logs, pool, out); break;
     case kLeduc: rc = launch<Leduc, false, false>(spec.leduc, roots, cfg, d_logs, pool, out); break;
-    case kHex: {
-      // The random-fill playout needs "legal moves == empty cells": not with the swap rule.  The search's own
-      // position (HexW) needs two distinct edges per colour.
-#define OSG_HEX_CASE(NW, member)                                                             \
-  if (spec.member.swap || spec.member.rows < 2 || spec.member.cols < 2)                      \
-    rc = launch<HexT<NW>, true, false>(spec.member, roots, cfg, d_logs, pool, out);          \
-  else rc = launch<HexT<NW>, true, true>(spec.member, roots, cfg, d_logs, pool, out)
-      // The boards above 128 cells (six / eight / twelve plane words) are searched in the fill form only (the caller,
-      // osg_mcts_search, has checked: no swap rule, two rows and columns at least, at most 64 columns).
-#define OSG_HEX_WIDE_CASE(NW, member)                                                        \
-  if (spec.member.swap || spec.member.rows < 2 || spec.member.cols < 2 || spec.member.cols > 64) \
-    return set_error(OSG_ERR_UNSUPPORTED, "wave-per-root search of a board above 128 cells: hex without the swap rule, 2 ... 64 columns"); \
-  rc = launch<HexT<NW>, true, true>(spec.member, roots, cfg, d_logs, pool, out)
-      switch (spec.hex_nw) {   // (a folded record — HexT::folded — differs in the root load only)
-        case 1: OSG_HEX_CASE(1, hex1); break;
-        case 2: OSG_HEX_CASE(2, hex2); break;
-        case 3: OSG_HEX_CASE(3, hex3); break;
-        case 4: OSG_HEX_CASE(4, hex4); break;
-        case 6: OSG_HEX_WIDE_CASE(6, hex6); break;
-        case 8: OSG_HEX_WIDE_CASE(8, hex8); break;
-        default: OSG_HEX_WIDE_CASE(12, hex12); break;
-      }
-#undef OSG_HEX_WIDE_CASE
-#undef OSG_HEX_CASE
+    case kHex:   // (a folded record — HexT::folded — differs in the root load only)
+      rc = for_hex(spec, [&](auto nw, const auto& P) {
+        using G = HexT<decltype(nw)::value>;
+        // The random-fill playout needs "legal moves == empty cells": not with the swap rule.  The search's own
+        // position (HexW) needs two distinct edges per colour.
+        const bool no_fill = P.swap || P.rows < 2 || P.cols < 2;
+        if constexpr (decltype(nw)::value <= 4) {
+          if (no_fill) return launch<G, true, false>(P, roots, cfg, d_logs, pool, out);
+        } else {
+          // The boards above 128 cells (six / eight / twelve plane words) are searched in the fill form only (the caller,
+          // osg_mcts_search, has checked: no swap rule, two rows and columns at least, at most 64 columns).
+          if (no_fill || P.cols > 64)
+            return set_error(OSG_ERR_UNSUPPORTED, "wave-per-root search of a board above 128 cells: hex without the swap rule, 2 ... 64 columns");
+        }
+        return launch<G, true, true>(P, roots, cfg, d_logs, pool, out);
+      });
       break;
-    }
     default: return set_error(OSG_ERR_INVALID, "bad game kind");
   }
   if (rc) return rc;
