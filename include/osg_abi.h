@@ -422,6 +422,18 @@ int osg_cfr_replicas(const osg_cfr* s);
 int osg_cfr_select_replica(osg_cfr* s, int replica);
 /* Restores the iteration counter of a deserialised solver (cfr.h:318-323 deserialisation ctor). */
 int osg_cfr_set_iteration(osg_cfr* s, int iteration);
+/* Discounted CFR (Brown & Sandholm 2019; discounted_cfr.py:93-209, DCFRSolver(alpha = 3/2, beta = 0, gamma = 2), LCFRSolver =
+ * (1, 1, 1)) for the osg_cfr_iterate calls that follow: in iteration t, after player p's pass, every cumulative regret of
+ * p's infostates is multiplied by t^alpha / (t^alpha + 1) if it is >= 0 and by t^beta / (t^beta + 1) otherwise, and with
+ * linear_averaging the cumulative-policy term is reach * prob * t^gamma.  enabled = 0 turns it off again.  OSG_ERR_INVALID
+ * for enabling it on an MCCFR solver, with regret_matching_plus or with simultaneous updates, and for a negative or
+ * non-finite exponent whatever `enabled` says; osg_cfr_br_iterate
+ * refuses a discounting solver.  osg_cfr_reset keeps the setting; a checkpoint is restored by osg_cfr_create,
+ * osg_cfr_set_discounting, osg_cfr_upload_tables, osg_cfr_set_iteration.  osg_cfr_last_kernel carries a `dcfr` tag. */
+int osg_cfr_set_discounting(osg_cfr* s, int enabled, double alpha, double beta, double gamma);
+/* The three factors of iteration t >= 1 exactly as the kernels use them (formed on the host in double precision with
+ * std::pow, handed to a launch as a table): out = {t^alpha / (t^alpha + 1), t^beta / (t^beta + 1), t^gamma}.  Needs no device. */
+int osg_cfr_discount_factors(double alpha, double beta, double gamma, int iteration, double out[3]);
 /* ExternalSamplingMCCFRSolver::FullUpdateAverage (external_sampling_mccfr.cc:188-231) — AverageType::kFull:
  * one full-tree pass adding weight * reach_probs[cur_player] * sigma(I)[a] to the cumulative policy of every
  * decision history, sigma = regret matching of the regrets as they are now.  weight = 1 after each

@@ -130,6 +130,8 @@ SIGNATURES = {
     "osg_cfr_last_kernel": (C.c_char_p, [VP]),
     "osg_cfr_last_eval_kernel": (C.c_char_p, [VP]),
     "osg_cfr_set_iteration": (INT, [VP, INT]),
+    "osg_cfr_set_discounting": (INT, [VP, INT, C.c_double, C.c_double, C.c_double]),
+    "osg_cfr_discount_factors": (INT, [C.c_double, C.c_double, C.c_double, INT, C.POINTER(C.c_double)]),
     "osg_cfr_replicas": (INT, [VP]),
     "osg_cfr_select_replica": (INT, [VP, INT]),
     "osg_mccfr_sample": (INT, [VP, U64, I64, I64]),

@@ -333,6 +333,38 @@ int cfr_sub_error(const osg_cfr* s) {
   return OSG_OK;
 }
 
+// The factors of iteration t as every kernel uses them (Discount in osg_cfr_internal.h): Python's `t**a / (t**a + 1)` and
+// `t**g` of discounted_cfr.py:184,203-208 — float pow is libm's pow, and so is std::pow here, in the same order.
+void discount_factors(double alpha, double beta, double gamma, int iteration, double out[3]) {
+  const double t = static_cast<double>(iteration);
+  const double ta = std::pow(t, alpha), tb = std::pow(t, beta);
+  out[0] = ta / (ta + 1.0);
+  out[1] = tb / (tb + 1.0);
+  out[2] = std::pow(t, gamma);
+}
+
+int cfr_discount_table(osg_cfr* s, int iteration0, int iters, const double** d_table) {
+  *d_table = nullptr;
+  if (!s->dcfr) return OSG_OK;
+  const size_t n = 3 * static_cast<size_t>(iters);
+  hipStream_t st = s->ctx->stream;
+  // (the stream may still be copying from h_disc or reading d_disc for the previous call)
+  if (n > s->disc_cap || n * sizeof(double) > (64u << 10)) OSG_HIP(hipStreamSynchronize(st));
+  if (n > s->disc_cap) {
+    if (s->d_disc) OSG_HIP(hipFree(s->d_disc));
+    s->d_disc = nullptr; s->disc_cap = 0;
+    OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_disc), sizeof(double) * n));
+    s->disc_cap = n;
+  }
+  s->h_disc.resize(n);
+  for (int it = 0; it < iters; ++it)
+    discount_factors(s->dcfr_alpha, s->dcfr_beta, s->dcfr_gamma, iteration0 + it + 1, &s->h_disc[3 * static_cast<size_t>(it)]);
+  OSG_HIP(hipMemcpyAsync(s->d_disc, s->h_disc.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+  if (n * sizeof(double) > (64u << 10)) OSG_HIP(hipStreamSynchronize(st));   // (as upload(): a large pageable copy may outlive the call)
+  *d_table = s->d_disc;
+  return OSG_OK;
+}
+
 }  // namespace osg_cfr_impl
 
 extern "C" {
@@ -453,7 +485,7 @@ int osg_cfr_destroy(osg_cfr* s) {
                   s->d_sub_info_off, s->d_sub_info_list, s->d_sub_bar, s->d_sub_ndec, s->d_sub_dec_row, s->d_sub_rec,
                   s->d_sub_stamps, s->d_mccfr_stamps, s->d_sub_recbuf, s->d_sub_chance_prob, s->d_sub_term_val, s->d_sub_dec_off, s->d_sub_fold_info, s->d_sub_fold_off, s->d_sub_nroot, s->d_sub_root_loc, s->d_sub_root_idx, s->d_sub_upper_rec, s->d_sub_root_value,
                   s->d_jobs_job, s->d_jobs_level, s->d_jobs_desc, s->d_jobs_fc, s->d_jobs_row, s->d_jobs_glob, s->d_jobs_info,
-                  s->d_jobs_mem, s->d_jobs_deal, s->d_jobs_ticket};
+                  s->d_jobs_mem, s->d_jobs_deal, s->d_jobs_ticket, s->d_disc};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (s->h_sub_err) (void)hipHostFree(s->h_sub_err);
@@ -487,7 +519,7 @@ int osg_cfr_iterate(osg_cfr* s, int iters) {
   const bool grid_path = s->path_kernel && s->B == 1 && (s->cfg.kernel == 2 || (s->cfg.kernel == 0 && s->H > 65536));
   // Trees too big for one workgroup: the persistent cooperative launch with a workgroup per deal subtree where the
   // tree has that shape (kernel == 5 forces it, 2 forces the per-phase launches), else a launch per phase.
-  const bool sub_path = s->sub_ok && s->B == 1 && (s->cfg.kernel == 5 || (s->cfg.kernel == 0 && grid_path));
+  const bool sub_path = s->sub_ok && (!s->dcfr || s->sub_dcfr_ok) && s->B == 1 && (s->cfg.kernel == 5 || (s->cfg.kernel == 0 && grid_path));
   if (sub_path) return cfr_sub_iterate(s, tb, iters);     // osg_cfr_sub.hip
   if (grid_path) return cfr_grid_iterate(s, tb, iters);   // osg_cfr_sub.hip
   if (s->split_ok && (s->cfg.kernel == 0 || s->cfg.kernel == 4)) {
@@ -499,13 +531,16 @@ int osg_cfr_iterate(osg_cfr* s, int iters) {
                  s->d_split_terms, s->d_split_bar, s->h_sub_err};
     const int passes = s->cfg.alternating_updates ? s->P : 1;
     const int per_launch = std::max(1, (1 << 30) / std::max(1, passes * s->split_G));  // the arrival counter is 32 bits
+    const double* disc = nullptr;
+    if (int rc = cfr_discount_table(s, s->iteration, iters, &disc)) return rc;
     for (int done = 0; done < iters; done += per_launch) {
-      const int rc = launch_split(s, stree, sp, tb, std::min(per_launch, iters - done), s->iteration + done, s->cfg, false);
+      const int rc = launch_split(s, stree, sp, tb, std::min(per_launch, iters - done), s->iteration + done, s->cfg, false,
+                                  disc ? disc + 3 * static_cast<size_t>(done) : nullptr);
       if (rc) return rc;
     }
     OSG_HIP(hipGetLastError());
     s->iteration += iters;
-    s->last_kernel = "k_cfr_split";
+    s->last_kernel = s->dcfr ? "k_cfr_split<dcfr>" : "k_cfr_split";
     return OSG_OK;
   }
   if (int rc = cfr_small_iterate(s, tb, iters, threads, grid_b)) return rc;   // osg_cfr_small.hip
@@ -516,6 +551,7 @@ int osg_cfr_iterate(osg_cfr* s, int iters) {
 int osg_cfr_br_iterate(osg_cfr* s, int iters) {
   if (!s || iters < 0) return set_error(OSG_ERR_INVALID, "osg_cfr_br_iterate: bad argument");
   if (s->cfg.solver != 0) return set_error(OSG_ERR_INVALID, "osg_cfr_br_iterate: needs a CFRSolverBase table (solver 0)");
+  if (s->dcfr) return set_error(OSG_ERR_INVALID, "osg_cfr_br_iterate: CFRBRSolver is plain CFR, this solver discounts (osg_cfr_set_discounting)");
   if (s->cfg.linear_averaging || s->cfg.regret_matching_plus)
     return set_error(OSG_ERR_INVALID, "osg_cfr_br_iterate: CFRBRSolver is plain CFR (cfr_br.cc:23-29)");
   if (s->B != 1) return set_error(OSG_ERR_UNSUPPORTED, "osg_cfr_br_iterate: one solver per object");
@@ -635,6 +671,35 @@ int osg_cfr_select_replica(osg_cfr* s, int replica) {
 int osg_cfr_set_iteration(osg_cfr* s, int iteration) {
   if (!s || iteration < 0) return set_error(OSG_ERR_INVALID, "osg_cfr_set_iteration: bad argument");
   s->iteration = iteration;
+  return OSG_OK;
+}
+
+int osg_cfr_set_discounting(osg_cfr* s, int enabled, double alpha, double beta, double gamma) {
+  if (!s) return set_error(OSG_ERR_INVALID, "osg_cfr_set_discounting: null solver");
+  // (enabled == 0 on a solver that could not discount anyway is accepted: off stays off)
+  if (enabled && s->cfg.solver != 0) return set_error(OSG_ERR_INVALID, "osg_cfr_set_discounting: CFR family only (solver 0), not the MCCFR samplers");
+  if (enabled && s->cfg.regret_matching_plus)
+    return set_error(OSG_ERR_INVALID, "osg_cfr_set_discounting: not with regret_matching_plus (the reference never combines discounting with RM+)");
+  if (enabled && !s->cfg.alternating_updates)
+    return set_error(OSG_ERR_INVALID, "osg_cfr_set_discounting: needs alternating_updates (the reference's _DCFRSolver does nothing with simultaneous updates)");
+  const double e[3] = {alpha, beta, gamma};
+  for (double v : e)
+    if (!std::isfinite(v) || v < 0.0)
+      return set_error(OSG_ERR_INVALID, "osg_cfr_set_discounting: alpha, beta and gamma must be finite and non-negative");
+  if (s->dcfr && !enabled) s->last_kernel = "";   // (a tag of the discounting kernels must not outlive them)
+  s->dcfr = enabled != 0;
+  s->dcfr_alpha = alpha; s->dcfr_beta = beta; s->dcfr_gamma = gamma;
+  return OSG_OK;
+}
+
+int osg_cfr_discount_factors(double alpha, double beta, double gamma, int iteration, double out[3]) {
+  if (!out) return set_error(OSG_ERR_INVALID, "osg_cfr_discount_factors: null output");
+  const double e[3] = {alpha, beta, gamma};
+  for (double v : e)
+    if (!std::isfinite(v) || v < 0.0)
+      return set_error(OSG_ERR_INVALID, "osg_cfr_discount_factors: alpha, beta and gamma must be finite and non-negative");
+  if (iteration < 1) return set_error(OSG_ERR_INVALID, "osg_cfr_discount_factors: iterations count from 1");
+  discount_factors(alpha, beta, gamma, iteration, out);
   return OSG_OK;
 }
 

@@ -12,6 +12,7 @@
 // external_sampling_mccfr.{h,cc}, outcome_sampling_mccfr.cc, cfr_br.cc, expected_returns.cc, best_response.cc.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -71,6 +72,23 @@ OSG_D void regret_match_row(const double* regrets, double* policy, int n) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Discounted CFR (discounted_cfr.py:190-209): the factors of one iteration t — t^alpha / (t^alpha + 1) for a regret
+// that is >= 0 after the pass's terms were added, t^beta / (t^beta + 1) for a negative one, and the averaging weight
+// t^gamma.  They are formed on the host (discount_factors: std::pow in double precision, what the reference's `**`
+// calls) and reach a launch as a table of three doubles per iteration of that launch: the index is the launch's loop
+// counter, so the three loads are wave-uniform.  The kernels take discounting as a template parameter (kDcfr): the
+// plain CFR / CFR+ instantiations hold none of it.
+// ---------------------------------------------------------------------------
+struct Discount { double pos, neg, weight; };
+OSG_D Discount discount_of(const double* __restrict__ table, int it) {
+  Discount f{table[3 * it], table[3 * it + 1], table[3 * it + 2]};
+  // (fetched by scalar loads, then kept in vector registers: six more scalar registers held across an iteration were
+  // parked in vector lanes by kernels that already sit at the scalar file's limit)
+  asm volatile("" : "+v"(f.pos), "+v"(f.neg), "+v"(f.weight));
+  return f;
+}
+OSG_D double discounted(double regret, const Discount& f) { return regret * (regret >= 0 ? f.pos : f.neg); }
 
 struct SmallTree {  // device pointers to the extra host-built arrays
   const int32_t* path_off;    // [M+1] per decision history (member order)
@@ -304,6 +322,12 @@ struct osg_cfr {
   int max_level_width = 0;
   int average_type = 0;  // ES-MCCFR AverageType: 0 kSimple, 1 kFull (external_sampling_mccfr.h:48)
   int iteration = 0;
+  // Discounted CFR (osg_cfr_set_discounting): the exponents, and the factor table of the latest launch
+  bool dcfr = false;
+  double dcfr_alpha = 0.0, dcfr_beta = 0.0, dcfr_gamma = 0.0;
+  std::vector<double> h_disc;
+  double* d_disc = nullptr;
+  size_t disc_cap = 0;   // doubles
   const char* last_kernel = "";  // the kernel family the last iterate / sample call launched (osg_cfr_last_kernel)
   // host tree
   std::vector<int32_t> level_off, parent, first_child, info, mem_off, mem, nact, legal;
@@ -348,6 +372,7 @@ struct osg_cfr {
   // one cooperative launch, a workgroup per deal subtree of any size (k_cfr_sub)
   bool sub_ok = false;
   bool sub_br_ok = false;           // k_cfr_sub<., kBr> (the CFR-BR pass set) fits the same grid
+  bool sub_dcfr_ok = false;         // k_cfr_sub<., false, kDcfr> (Discounted CFR) fits the same grid
   int sub_G = 0, sub_L = 0, sub_NL = 0, sub_K = 0, sub_grid = 0;
   size_t sub_lds_bytes = 0;
   int sub_ND = 0, sub_PL = 0;
@@ -417,13 +442,17 @@ struct osg_cfr {
 namespace osg_cfr_impl {
 // ---- osg_cfr.hip ----
 int cfr_sub_error(const osg_cfr* s);   // a grid barrier timed out in an earlier launch: the solver refuses further work
+void discount_factors(double alpha, double beta, double gamma, int iteration, double out[3]);
+// The factor table of iterations iteration0 + 1 ... iteration0 + iters on the device (null where the solver does not discount).
+int cfr_discount_table(osg_cfr* s, int iteration0, int iters, const double** d_table);
 // ---- osg_cfr_small.hip ----
 void cfr_small_prepare(osg_cfr* s);    // LDS caps of k_cfr<true> / k_cfr_small (clears lds_resident / small_tree where refused)
 int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, int threads, unsigned grid_b);   // k_cfr_small / k_cfr
 void cfr_general_br_pass(osg_cfr* s, Tables tb, int threads, osg_cfr_cfg cfg);           // k_cfr<false, kBr> x 1
 // ---- osg_cfr_split.hip ----
 int build_split(osg_cfr* s);
-int launch_split(osg_cfr* s, SmallTree stree, SplitTree sp, Tables tb, int iters, int iteration0, osg_cfr_cfg cfg, bool br);
+int launch_split(osg_cfr* s, SmallTree stree, SplitTree sp, Tables tb, int iters, int iteration0, osg_cfr_cfg cfg, bool br,
+                 const double* disc = nullptr);
 // ---- osg_cfr_sub.hip ----
 int build_sub(osg_cfr* s);
 int cfr_sub_iterate(osg_cfr* s, Tables tb, int iters);      // k_cfr_sub

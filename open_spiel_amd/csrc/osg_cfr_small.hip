@@ -10,10 +10,12 @@ namespace {
 // kBr: one CFRBRSolver::EvaluateAndUpdatePolicy pass set (cfr_br.cc:48-83): P passes, pass p updates
 // player p while every other player follows its best-response action best[i] (policy_overrides,
 // cfr.cc:365-372) instead of the current policy.
-template <bool kLds, bool kBr = false>
+// kDcfr: Discounted CFR (discounted_cfr.py:176-209) — the policy term is (reach * prob) * t^gamma, and every regret of the
+// updating player is multiplied by its factor between the fold and regret matching; `disc` holds the launch's factors.
+template <bool kLds, bool kBr = false, bool kDcfr = false>
 __global__ void __launch_bounds__(1024)
 k_cfr(Tree t, Tables tb, double* g_reach, double* g_value, int iters, int iteration0, osg_cfr_cfg cfg,
-      const int32_t* __restrict__ best = nullptr) {
+      const int32_t* __restrict__ best = nullptr, const double* __restrict__ disc = nullptr) {
   extern __shared__ double smem[];
   const int P = t.P, S = t.P + 1, A = t.A;
   double* reach = kLds ? smem : g_reach;                       // [H, P+1], chance last (cfr.cc:196,201)
@@ -37,6 +39,8 @@ k_cfr(Tree t, Tables tb, double* g_reach, double* g_value, int iters, int iterat
   const int passes = (kBr || cfg.alternating_updates) ? P : 1;
   for (int it = 0; it < iters; ++it) {
     const int iteration = iteration0 + it + 1;  // ++iteration_ (cfr.cc:264)
+    Discount df{};
+    if constexpr (kDcfr) df = discount_of(disc, it);
     for (int pass = 0; pass < passes; ++pass) {
       const int upd = (kBr || cfg.alternating_updates) ? pass : -1;
       // probability of action index a at infostate i in this pass
@@ -112,13 +116,17 @@ k_cfr(Tree t, Tables tb, double* g_reach, double* g_value, int iters, int iterat
             const double cfr_regret = cf_reach * (value[(fc + a) * P + pl] - vh);
             regrets[i * A + a] += cfr_regret;
             const double pol = cur[i * A + a];
-            if (cfg.linear_averaging) cum[i * A + a] += iteration * self_reach * pol;
+            if constexpr (kDcfr) cum[i * A + a] += cfg.linear_averaging ? (self_reach * pol) * df.weight : self_reach * pol;
+            else if (cfg.linear_averaging) cum[i * A + a] += iteration * self_reach * pol;
             else cum[i * A + a] += self_reach * pol;
           }
         }
-        if (cfg.regret_matching_plus)
+        if constexpr (kDcfr) {
+          for (int a = 0; a < n; ++a) regrets[i * A + a] = discounted(regrets[i * A + a], df);
+        } else if (cfg.regret_matching_plus) {
           for (int a = 0; a < n; ++a)
             if (regrets[i * A + a] < 0) regrets[i * A + a] = 0;
+        }
         regret_match_row(regrets + i * A, cur + i * A, n);
       }
       __syncthreads();
@@ -159,9 +167,11 @@ k_cfr(Tree t, Tables tb, double* g_reach, double* g_value, int iters, int iterat
 // kW > 0 (owner form, alternating updates): every decision node has at most kW actions — the loops over a row's
 // actions are unrolled and predicated instead of running as lane-masked loops (a third of the kernel's instructions
 // were loop control: scalar mask bookkeeping and branches, which a lone wavefront issues one at a time like any other).
-template <bool kLds, bool kOwner, int kSlots, int kPath = 8, int kW = 0>  // kSlots >= P + 1 reach slots kept in registers
+// kDcfr: Discounted CFR, as in k_cfr (the member's policy term carries the weight; phase C discounts the folded row).
+template <bool kLds, bool kOwner, int kSlots, int kPath = 8, int kW = 0, bool kDcfr = false>  // kSlots >= P + 1 reach slots kept in registers
 __global__ void __launch_bounds__(1024)
-k_cfr_small(Tree t, SmallTree st, SmallGlobal sg, Tables tb, int iters, int iteration0, osg_cfr_cfg cfg) {
+k_cfr_small(Tree t, SmallTree st, SmallGlobal sg, Tables tb, int iters, int iteration0, osg_cfr_cfg cfg,
+            const double* __restrict__ disc = nullptr) {
   extern __shared__ double smem[];
   const int P = t.P, A = t.A, H = t.H, I = t.I, M = st.M, IA = t.I * t.A;
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -287,6 +297,13 @@ k_cfr_small(Tree t, SmallTree st, SmallGlobal sg, Tables tb, int iters, int iter
   const int passes = (kW > 0 || cfg.alternating_updates) ? P : 1;
   for (int it = 0; it < iters; ++it) {
     const int iteration = iteration0 + it + 1;
+    Discount df{};
+    if constexpr (kDcfr) df = discount_of(disc, it);
+    // the average-policy term of a member (cfr.cc:398-404; discounted_cfr.py:182-186 under kDcfr)
+    auto policy_term = [&](double self_reach, double pol) -> double {
+      if constexpr (kDcfr) return cfg.linear_averaging ? (self_reach * pol) * df.weight : self_reach * pol;
+      else return cfg.linear_averaging ? iteration * self_reach * pol : self_reach * pol;
+    };
     for (int pass = 0; pass < passes; ++pass) {
       const int upd = (kW > 0 || cfg.alternating_updates) ? pass : -1;
       const int q0 = upd >= 0 ? upd : 0, q1 = upd >= 0 ? upd + 1 : P;
@@ -370,14 +387,14 @@ k_cfr_small(Tree t, SmallTree st, SmallGlobal sg, Tables tb, int iters, int iter
           for (int a = 0; a < kW; ++a)
             if (a < n) {
               dreg[m * A + a] = cf_reach * (cv[a] - vh);
-              dpol[m * A + a] = cfg.linear_averaging ? iteration * self_reach * pol[a] : self_reach * pol[a];
+              dpol[m * A + a] = policy_term(self_reach, pol[a]);
             }
           return;
         }
         for (int a = 0; a < n; ++a) {
           dreg[m * A + a] = cf_reach * (value[(fc + a) * P + pl] - vh);
           const double pol = cur[i * A + a];
-          dpol[m * A + a] = cfg.linear_averaging ? iteration * self_reach * pol : self_reach * pol;
+          dpol[m * A + a] = policy_term(self_reach, pol);
         }
       };
       // one infostate: fold its members' terms in DFS order, RM+ clamp, regret matching
@@ -390,9 +407,12 @@ k_cfr_small(Tree t, SmallTree st, SmallGlobal sg, Tables tb, int iters, int iter
             cum[i * A + a] += dpol[m * A + a];
           }
         }
-        if (cfg.regret_matching_plus)
+        if constexpr (kDcfr) {
+          for (int a = 0; a < n; ++a) regrets[i * A + a] = discounted(regrets[i * A + a], df);
+        } else if (cfg.regret_matching_plus) {
           for (int a = 0; a < n; ++a)
             if (regrets[i * A + a] < 0) regrets[i * A + a] = 0;
+        }
         regret_match_row(regrets + i * A, cur + i * A, n);
       };
       // the same for the owner form with rows of up to kMaxA actions: the row in registers for the whole fold (one LDS
@@ -440,7 +460,8 @@ k_cfr_small(Tree t, SmallTree st, SmallGlobal sg, Tables tb, int iters, int iter
         double sum_pos = 0.0;
 #pragma unroll
         for (int a = 0; a < kFW; ++a) {
-          if (cfg.regret_matching_plus && r_reg[a] < 0) r_reg[a] = 0;
+          if constexpr (kDcfr) r_reg[a] = discounted(r_reg[a], df);
+          else if (cfg.regret_matching_plus && r_reg[a] < 0) r_reg[a] = 0;
           if (a < n && r_reg[a] > 0) sum_pos += r_reg[a];
         }
         const double inv_n = n == 1 ? 1.0 : (n == 2 ? 0.5 : (n == 3 ? 1.0 / 3.0 : 0.25));
@@ -504,6 +525,7 @@ namespace osg_cfr_impl {
 void cfr_small_prepare(osg_cfr* s) {
   if (s->lds_resident) {
     hipError_t e = raise_lds_cap(reinterpret_cast<const void*>(&k_cfr<true>), static_cast<int>(s->lds_bytes));
+    if (e == hipSuccess) e = raise_lds_cap(reinterpret_cast<const void*>(&k_cfr<true, false, true>), static_cast<int>(s->lds_bytes));
     if (e != hipSuccess) { (void)hipGetLastError(); s->lds_resident = false; }
   }
   if (s->small_tree) {
@@ -515,7 +537,16 @@ void cfr_small_prepare(osg_cfr* s) {
                                 reinterpret_cast<const void*>(&k_cfr_small<true, true, 3, 2, 2>),
                                 reinterpret_cast<const void*>(&k_cfr_small<true, true, 3, 4>),
                                 reinterpret_cast<const void*>(&k_cfr_small<true, true, 4>),
-                                reinterpret_cast<const void*>(&k_cfr_small<true, true, kMaxPlayers + 1>)};
+                                reinterpret_cast<const void*>(&k_cfr_small<true, true, kMaxPlayers + 1>),
+                                reinterpret_cast<const void*>(&k_cfr_small<true, false, 3, 8, 0, true>),
+                                reinterpret_cast<const void*>(&k_cfr_small<true, false, 4, 8, 0, true>),
+                                reinterpret_cast<const void*>(&k_cfr_small<true, false, kMaxPlayers + 1, 8, 0, true>),
+                                reinterpret_cast<const void*>(&k_cfr_small<true, true, 3, 8, 0, true>),
+                                reinterpret_cast<const void*>(&k_cfr_small<true, true, 3, 2, 0, true>),
+                                reinterpret_cast<const void*>(&k_cfr_small<true, true, 3, 2, 2, true>),
+                                reinterpret_cast<const void*>(&k_cfr_small<true, true, 3, 4, 0, true>),
+                                reinterpret_cast<const void*>(&k_cfr_small<true, true, 4, 8, 0, true>),
+                                reinterpret_cast<const void*>(&k_cfr_small<true, true, kMaxPlayers + 1, 8, 0, true>)};
     hipError_t e = hipSuccess;
       for (const void* f : variants)
         if (e == hipSuccess)
@@ -527,6 +558,8 @@ void cfr_small_prepare(osg_cfr* s) {
 // The one-workgroup kernels (osg_cfr_iterate's last branch): the path-based kernel, all-in-LDS when the tree is small
 // enough, else the general kernel.
 int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, int threads, unsigned grid_b) {
+  const double* disc = nullptr;
+  if (int rc = cfr_discount_table(s, s->iteration, iters, &disc)) return rc;
   if (s->path_kernel && s->cfg.kernel != 1) {
     // Path-based kernel: no top-down reach pass; all-in-LDS when the tree is small enough.
     const int M = static_cast<int>(s->mem.size());
@@ -536,37 +569,50 @@ int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, int threads, unsigned gr
                    s->d_meta32, s->d_info_player32};
     const auto small = [&](auto lds, auto owner, int block, size_t shmem) {   // the reach block: 3, 4 or all players + 1
       with_int<3, 4, kMaxPlayers + 1>(s->P + 1, [&](auto p1) {
-        k_cfr_small<decltype(lds)::value, decltype(owner)::value, decltype(p1)::value><<<dim3(grid_b), dim3(block), shmem, s->ctx->stream>>>(
-            s->tree(), st, sg, tb, iters, s->iteration, s->cfg);
+        return with_bool(s->dcfr, [&](auto dcfr) {
+          k_cfr_small<decltype(lds)::value, decltype(owner)::value, decltype(p1)::value, 8, 0, decltype(dcfr)::value>
+              <<<dim3(grid_b), dim3(block), shmem, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg, disc);
+          return OSG_OK;
+        });
+      });
+    };
+    // the owner forms of two-player trees with short root paths (kPath entries in registers, rows of kW actions unrolled)
+    const auto owner2 = [&](auto path, auto width, int block) {
+      with_bool(s->dcfr, [&](auto dcfr) {
+        k_cfr_small<true, true, 3, decltype(path)::value, decltype(width)::value, decltype(dcfr)::value>
+            <<<dim3(grid_b), dim3(block), s->small_lds_bytes, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg, disc);
         return OSG_OK;
       });
     };
     if (s->small_tree && s->H <= 1024 && s->A <= kMaxA) {  // one thread per history: descriptors live in registers
       const int owner_threads = std::max(64, ((s->H + 63) / 64) * 64);
       if (s->P == 2 && s->max_path_decisions <= 2 && s->A == 2 && s->cfg.alternating_updates)   // kuhn_poker
-        k_cfr_small<true, true, 3, 2, 2><<<dim3(grid_b), dim3(owner_threads), s->small_lds_bytes, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg);
+        owner2(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}, owner_threads);
       else if (s->P == 2 && s->max_path_decisions <= 2)   // two players, short paths: the 2-entry reach block
-        k_cfr_small<true, true, 3, 2><<<dim3(grid_b), dim3(owner_threads), s->small_lds_bytes, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg);
+        owner2(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}, owner_threads);
       else if (s->P == 2 && s->max_path_decisions <= 4)
-        k_cfr_small<true, true, 3, 4><<<dim3(grid_b), dim3(owner_threads), s->small_lds_bytes, s->ctx->stream>>>(s->tree(), st, sg, tb, iters, s->iteration, s->cfg);
+        owner2(std::integral_constant<int, 4>{}, std::integral_constant<int, 0>{}, owner_threads);
       else
         small(std::true_type{}, std::true_type{}, owner_threads, s->small_lds_bytes);
-      s->last_kernel = "k_cfr_small<lds, owner>";
+      s->last_kernel = s->dcfr ? "k_cfr_small<lds, owner, dcfr>" : "k_cfr_small<lds, owner>";
     } else if (s->small_tree) {
       small(std::true_type{}, std::false_type{}, threads, s->small_lds_bytes);
-      s->last_kernel = "k_cfr_small<lds>";
+      s->last_kernel = s->dcfr ? "k_cfr_small<lds, dcfr>" : "k_cfr_small<lds>";
     } else {
       small(std::false_type{}, std::false_type{}, threads, 0);
-      s->last_kernel = "k_cfr_small<global>";
+      s->last_kernel = s->dcfr ? "k_cfr_small<global, dcfr>" : "k_cfr_small<global>";
     }
   } else if (s->B > 1) {
     return set_error(OSG_ERR_UNSUPPORTED, "replicas > 1 are not available with the general kernel");
-  } else if (s->lds_resident) {
-    k_cfr<true><<<dim3(1), dim3(threads), s->lds_bytes, s->ctx->stream>>>(s->tree(), tb, s->d_reach, s->d_value, iters,
-                                                                         s->iteration, s->cfg);
   } else {
-    k_cfr<false><<<dim3(1), dim3(threads), 0, s->ctx->stream>>>(s->tree(), tb, s->d_reach, s->d_value, iters,
-                                                                s->iteration, s->cfg);
+    with_bool(s->lds_resident, [&](auto lds) {
+      return with_bool(s->dcfr, [&](auto dcfr) {
+        k_cfr<decltype(lds)::value, false, decltype(dcfr)::value><<<dim3(1), dim3(threads), decltype(lds)::value ? s->lds_bytes : size_t{0}, s->ctx->stream>>>(
+            s->tree(), tb, s->d_reach, s->d_value, iters, s->iteration, s->cfg, nullptr, disc);
+        return OSG_OK;
+      });
+    });
+    if (s->dcfr) s->last_kernel = "k_cfr<dcfr>";
   }
   OSG_HIP(hipGetLastError());
   return OSG_OK;

@@ -39,10 +39,13 @@ namespace {
 // everything in registers.  split_kernel() picks the instantiation by the launch size.
 // kW > 0 (alternating updates or kBr: one value per history): decision rows of at most kW actions are walked unrolled
 // and predicated instead of as lane-masked loops (as in k_cfr_small).
-template <int kSlots, bool kBr = false, int kBound = 1024, int kW = 0>  // kSlots >= P + 1
+// kDcfr: Discounted CFR (discounted_cfr.py:176-209).  A record carries the plain own reach and the fold forms the policy
+// term as (own reach x policy) x t^gamma, then multiplies every regret of the row by its factor before regret matching:
+// every workgroup that keeps the row does the same, so the copies stay bit-identical.  `disc`: the launch's factors.
+template <int kSlots, bool kBr = false, int kBound = 1024, int kW = 0, bool kDcfr = false>  // kSlots >= P + 1
 __global__ void __launch_bounds__(kBound)
 k_cfr_split(Tree t, SmallTree st, SplitTree sp, Tables tb, int iters, int iteration0, osg_cfr_cfg cfg,
-            const int32_t* __restrict__ best = nullptr) {
+            const int32_t* __restrict__ best = nullptr, const double* __restrict__ disc = nullptr) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int P = t.P, A = t.A, IA = t.I * t.A, M = st.M;
   const int tid = threadIdx.x, g = blockIdx.x;
@@ -116,6 +119,8 @@ k_cfr_split(Tree t, SmallTree st, SplitTree sp, Tables tb, int iters, int iterat
   unsigned int epoch = 0;
   for (int it = 0; it < iters; ++it) {
     const int iteration = iteration0 + it + 1;
+    Discount df{};
+    if constexpr (kDcfr) df = discount_of(disc, it);
     for (int pass = 0; pass < passes; ++pass) {
       const int upd = (kW > 0 || kBr || cfg.alternating_updates) ? pass : -1;
       const int q0 = upd >= 0 ? upd : 0, q1 = upd >= 0 ? upd + 1 : P;
@@ -190,7 +195,7 @@ k_cfr_split(Tree t, SmallTree st, SplitTree sp, Tables tb, int iters, int iterat
         if (pruned) {
           store_through(rec, -1.0);
         } else {
-          store_through(rec, cfg.linear_averaging ? iteration * self_reach : self_reach);
+          store_through(rec, (!kDcfr && cfg.linear_averaging) ? iteration * self_reach : self_reach);
           const double vh = value[b_h * P + b_pl];
           for (int a = 0; a < b_n; ++a) store_through(rec + 1 + a, cf_reach * (value[(b_fc + a) * P + b_pl] - vh));
         }
@@ -247,7 +252,8 @@ k_cfr_split(Tree t, SmallTree st, SplitTree sp, Tables tb, int iters, int iterat
 #pragma unroll
             for (int a = 0; a < kSplitMaxA; ++a) {
               r_reg[a] += rt[j][a];
-              r_cum[a] += own[j] * r_cur[a];
+              if constexpr (kDcfr) r_cum[a] += cfg.linear_averaging ? (own[j] * r_cur[a]) * df.weight : own[j] * r_cur[a];
+              else r_cum[a] += own[j] * r_cur[a];
             }
           }
         }
@@ -257,7 +263,8 @@ k_cfr_split(Tree t, SmallTree st, SplitTree sp, Tables tb, int iters, int iterat
         double sum_pos = 0.0;
 #pragma unroll
         for (int a = 0; a < kSplitMaxA; ++a) {
-          if (cfg.regret_matching_plus && r_reg[a] < 0) r_reg[a] = 0;
+          if constexpr (kDcfr) r_reg[a] = discounted(r_reg[a], df);
+          else if (cfg.regret_matching_plus && r_reg[a] < 0) r_reg[a] = 0;
           if (a < c_n && r_reg[a] > 0) sum_pos += r_reg[a];
         }
 #pragma unroll
@@ -293,9 +300,15 @@ k_cfr_split(Tree t, SmallTree st, SplitTree sp, Tables tb, int iters, int iterat
 }
 
 // (the row-width instantiation: two players, rows of exactly up to 3 actions — leduc_poker — with one value per history)
-static const void* split_kernel_w3() { return reinterpret_cast<const void*>(&k_cfr_split<3, false, 512, 3>); }
+static const void* split_kernel_w3(bool dcfr) {
+  return dcfr ? reinterpret_cast<const void*>(&k_cfr_split<3, false, 512, 3, true>) : reinterpret_cast<const void*>(&k_cfr_split<3, false, 512, 3>);
+}
 template <int kBound>
-static const void* split_kernel_bound(int P, bool br) {
+static const void* split_kernel_bound(int P, bool br, bool dcfr) {
+  if (dcfr)   // (never with br: CFR-BR is plain CFR)
+    return P == 2 ? reinterpret_cast<const void*>(&k_cfr_split<3, false, kBound, 0, true>)
+                  : (P == 3 ? reinterpret_cast<const void*>(&k_cfr_split<4, false, kBound, 0, true>)
+                            : reinterpret_cast<const void*>(&k_cfr_split<kMaxPlayers + 1, false, kBound, 0, true>));
   if (br) return P == 2 ? reinterpret_cast<const void*>(&k_cfr_split<3, true, kBound>)
                         : (P == 3 ? reinterpret_cast<const void*>(&k_cfr_split<4, true, kBound>)
                                   : reinterpret_cast<const void*>(&k_cfr_split<kMaxPlayers + 1, true, kBound>));
@@ -304,10 +317,10 @@ static const void* split_kernel_bound(int P, bool br) {
                           : reinterpret_cast<const void*>(&k_cfr_split<kMaxPlayers + 1, false, kBound>));
 }
 // The instantiation for a launch of `threads` threads per workgroup (see kBound above).
-static const void* split_kernel(int P, bool br, int threads, int A = 0, bool one_value = false) {
+static const void* split_kernel(int P, bool br, int threads, int A = 0, bool one_value = false, bool dcfr = false) {
   // (the CFR-BR pass set keeps the loop form: its row-width instantiation parks five scalar registers in vector lanes)
-  if (threads <= 512 && P == 2 && A == 3 && one_value && !br && !std::getenv("OSG_CFR_SPLIT_W0")) return split_kernel_w3();
-  return threads <= 512 ? split_kernel_bound<512>(P, br) : split_kernel_bound<1024>(P, br);
+  if (threads <= 512 && P == 2 && A == 3 && one_value && !br && !std::getenv("OSG_CFR_SPLIT_W0")) return split_kernel_w3(dcfr);
+  return threads <= 512 ? split_kernel_bound<512>(P, br, dcfr) : split_kernel_bound<1024>(P, br, dcfr);
 }
 
 
@@ -407,7 +420,9 @@ int build_split(osg_cfr* s) {
   OSG_HIP(hipMemsetAsync(s->d_split_bar, 0, sizeof(unsigned int) * 4, st));
   OSG_HIP(hipMemsetAsync(s->d_split_terms, 0, sizeof(double) * 2 * kSplitRec * std::max<size_t>(M, 1), st));
   if (raise_lds_cap(split_kernel(s->P, false, threads), static_cast<int>(lds)) != hipSuccess ||
-      raise_lds_cap(split_kernel(s->P, false, threads, s->A, true), static_cast<int>(lds)) != hipSuccess) {
+      raise_lds_cap(split_kernel(s->P, false, threads, s->A, true), static_cast<int>(lds)) != hipSuccess ||
+      raise_lds_cap(split_kernel(s->P, false, threads, 0, false, true), static_cast<int>(lds)) != hipSuccess ||
+      raise_lds_cap(split_kernel(s->P, false, threads, s->A, true, true), static_cast<int>(lds)) != hipSuccess) {
     (void)hipGetLastError();
     return OSG_OK;
   }
@@ -428,15 +443,16 @@ int build_split(osg_cfr* s) {
 // together — with another stream keeping the device busy (a network's forward pass beside the solver) a plain launch
 // can start some workgroups while the others queue behind foreign work, and the barrier's bound then turns a slowdown
 // into an error.  The cooperative launch waits until the whole grid fits.  br: the CFR-BR pass set (d_best overrides).
-int launch_split(osg_cfr* s, SmallTree stree, SplitTree sp, Tables tb, int iters, int iteration0, osg_cfr_cfg cfg, bool br) {
+int launch_split(osg_cfr* s, SmallTree stree, SplitTree sp, Tables tb, int iters, int iteration0, osg_cfr_cfg cfg, bool br,
+                 const double* disc) {
   hipStream_t st = s->ctx->stream;
   // (the barrier's counters are zero: build_split zeroed them and every launch leaves them so; a launch that timed out
   // does not — and makes the solver unusable, cfr_sub_error)
   const dim3 grid(static_cast<unsigned>(s->split_G)), block(static_cast<unsigned>(s->split_threads));
   Tree tr = s->tree();
   const int32_t* best = br ? s->d_best : nullptr;
-  void* args[] = {&tr, &stree, &sp, &tb, &iters, &iteration0, &cfg, &best};
-  const void* kern = split_kernel(s->P, br, s->split_threads, s->A, br || cfg.alternating_updates);
+  void* args[] = {&tr, &stree, &sp, &tb, &iters, &iteration0, &cfg, &best, &disc};
+  const void* kern = split_kernel(s->P, br, s->split_threads, s->A, br || cfg.alternating_updates, disc != nullptr);
   const size_t lds = s->split_lds_bytes + (br ? sizeof(double) * static_cast<size_t>(s->I) * s->A : 0);
   // OSG_CFR_PLAIN_LAUNCH=1: an ordinary launch, for hosts that run the solver alone on the device — the cooperative
   // launch costs 20 us per call (47.6 vs 27.6 us per one-iteration launch, CFR-BR 1.30e4 vs 1.82e4 it/s), which only the

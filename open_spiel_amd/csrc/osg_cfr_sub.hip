@@ -36,7 +36,10 @@ __global__ void __launch_bounds__(256) k_gcfr_level(GridCfr g, int begin, int en
   }
 }
 
-__global__ void __launch_bounds__(256) k_gcfr_members(GridCfr g, int upd, int iteration, osg_cfr_cfg cfg) {
+// kDcfr (k_gcfr_members, k_gcfr_fold): Discounted CFR (discounted_cfr.py:176-209); `disc` points at the three factors of the
+// launch's iteration (one address for the whole grid).
+template <bool kDcfr>
+__global__ void __launch_bounds__(256) k_gcfr_members(GridCfr g, int upd, int iteration, osg_cfr_cfg cfg, const double* __restrict__ disc) {
   const int m = blockIdx.x * 256 + threadIdx.x;
   if (m >= g.M) return;
   const int P = g.t.P, A = g.t.A;
@@ -65,10 +68,13 @@ __global__ void __launch_bounds__(256) k_gcfr_members(GridCfr g, int upd, int it
   if (pruned) return;
   const int i = g.t.info[h], n = g.t.nact[i], fc = g.t.first_child[h];
   const double vh = g.value[h * P + pl];
+  Discount df{};
+  if constexpr (kDcfr) df = discount_of(disc, 0);
   for (int a = 0; a < n; ++a) {
     g.dreg[m * A + a] = cf_reach * (g.value[(fc + a) * P + pl] - vh);
     const double pol = g.pol[i * A + a];   // (the member's own row: the current policy also under CFR-BR's overrides)
-    g.dpol[m * A + a] = cfg.linear_averaging ? iteration * self_reach * pol : self_reach * pol;
+    if constexpr (kDcfr) g.dpol[m * A + a] = cfg.linear_averaging ? (self_reach * pol) * df.weight : self_reach * pol;
+    else g.dpol[m * A + a] = cfg.linear_averaging ? iteration * self_reach * pol : self_reach * pol;
   }
 }
 // CFR-BR on large trees (cfr_br.cc:70-81, policy_overrides cfr.cc:365-372): the policy pass `upd` plays — the updating
@@ -85,7 +91,8 @@ __global__ void __launch_bounds__(256) k_gcfr_effpol(GridCfr g, int upd, const i
 // in member order from the lanes' registers (readlane with a uniform index, pruned members stepped over through the
 // ballot of the live ones) — a thread per infostate had walked its ~40 members one dependent load after the other.  The
 // additions are cfr.cc:379-405's in its order: bit-identical with every other CFR kernel here.
-__global__ void __launch_bounds__(256) k_gcfr_fold(GridCfr g, int upd, osg_cfr_cfg cfg) {
+template <bool kDcfr>
+__global__ void __launch_bounds__(256) k_gcfr_fold(GridCfr g, int upd, osg_cfr_cfg cfg, const double* __restrict__ disc) {
   const int i = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
   if (i >= g.t.I) return;                                   // (wave-uniform)
   if (upd >= 0 && g.info_player[i] != upd) return;
@@ -107,9 +114,13 @@ __global__ void __launch_bounds__(256) k_gcfr_fold(GridCfr g, int upd, osg_cfr_c
     if (lane == 0) { g.tb.regrets[i * A + a] = reg; g.tb.cum[i * A + a] = cum; }
   }
   if (lane != 0) return;
-  if (cfg.regret_matching_plus)
+  if constexpr (kDcfr) {
+    const Discount df = discount_of(disc, 0);
+    for (int a = 0; a < n; ++a) g.tb.regrets[i * A + a] = discounted(g.tb.regrets[i * A + a], df);
+  } else if (cfg.regret_matching_plus) {
     for (int a = 0; a < n; ++a)
       if (g.tb.regrets[i * A + a] < 0) g.tb.regrets[i * A + a] = 0;
+  }
   regret_match_row(g.tb.regrets + i * A, g.tb.cur + i * A, n);
 }
 
@@ -160,9 +171,13 @@ OSG_D void quad_store(__amdgpu_buffer_rsrc_t rec_buf, const unsigned int (&own)[
 // policy and, for every other player, the one-hot row of the best-response action the evaluation left in sp.br_best
 // (policy_overrides, cfr.cc:365-372): every pass stages all its rows, nothing else changes.  A template argument so that
 // the plain CFR kernel's code object is what it was.
-template <int kK, bool kBr = false>   // histories per thread: NL <= kK * 1024
+// kDcfr: Discounted CFR (discounted_cfr.py:176-209) — a record's policy terms are (own reach x policy) x t^gamma and the fold
+// multiplies the row's regrets by their factors before regret matching; `disc` holds the launch's factors, three per
+// iteration.  A template argument for the same reason.
+template <int kK, bool kBr = false, bool kDcfr = false>   // histories per thread: NL <= kK * 1024
 __global__ void __launch_bounds__(kSubThreads)
-k_cfr_sub(Tree t, SmallTree st, SubTree sp, Tables tb, int iters, int iteration0, osg_cfr_cfg cfg) {
+k_cfr_sub(Tree t, SmallTree st, SubTree sp, Tables tb, int iters, int iteration0, osg_cfr_cfg cfg,
+          const double* __restrict__ disc = nullptr) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
   double* s_pol = s_dyn;                                             // [ND, A] the current policy of the bin's rows (ND * A even)
   double* s_cp = s_pol + sp.ND * t.A;                                // [NCP] outcome probabilities of the bin's chance histories
@@ -264,6 +279,8 @@ k_cfr_sub(Tree t, SmallTree st, SubTree sp, Tables tb, int iters, int iteration0
   if (one_bin && static_cast<int>(blockIdx.x) < sp.G) load_descriptors(blockIdx.x, sp.nloc[blockIdx.x]);
   for (int it = 0; it < iters; ++it) {
     const int iteration = iteration0 + it + 1;
+    Discount df{};
+    if constexpr (kDcfr) df = discount_of(disc, it);
     for (int upd = 0; upd < P; ++upd) {
       const bool stamp = sp.stamps && it == iters - 1 && static_cast<int>(blockIdx.x) == sp.stamp_wg && tid == 0;
       if (stamp) sp.stamps[upd * 5 + 0] = wall_clock64();
@@ -452,7 +469,8 @@ k_cfr_sub(Tree t, SmallTree st, SubTree sp, Tables tb, int iters, int iteration0
               if (live[u] && !pruned[u] && a < n) {
                 dr[a] = cf * (s_value[lfc + a] - vh);
                 const double pol = s_pol[d * A + a];
-                dp[a] = cfg.linear_averaging ? iteration * self_reach[u] * pol : self_reach[u] * pol;
+                if constexpr (kDcfr) dp[a] = cfg.linear_averaging ? (self_reach[u] * pol) * df.weight : self_reach[u] * pol;
+                else dp[a] = cfg.linear_averaging ? iteration * self_reach[u] * pol : self_reach[u] * pol;
               }
             }
             if (pruned[u]) {   // the flag record: a quiet NaN whose low word is 1 in the first word, nothing else is read
@@ -623,7 +641,8 @@ k_cfr_sub(Tree t, SmallTree st, SubTree sp, Tables tb, int iters, int iteration0
                 r[a] = 0.0; r[kSplitMaxA + a] = 0.0;
                 if (a < xn[u]) {
                   r[a] = cf_reach * (va[a] - vh);
-                  r[kSplitMaxA + a] = cfg.linear_averaging ? iteration * self_reach * pa[a] : self_reach * pa[a];
+                  if constexpr (kDcfr) r[kSplitMaxA + a] = cfg.linear_averaging ? (self_reach * pa[a]) * df.weight : self_reach * pa[a];
+                  else r[kSplitMaxA + a] = cfg.linear_averaging ? iteration * self_reach * pa[a] : self_reach * pa[a];
                 }
               }
             }
@@ -655,7 +674,8 @@ k_cfr_sub(Tree t, SmallTree st, SubTree sp, Tables tb, int iters, int iteration0
             double sum_pos = 0.0;
 #pragma unroll
             for (int a = 0; a < kSplitMaxA; ++a) {
-              if (cfg.regret_matching_plus && reg[a] < 0) reg[a] = 0;
+              if constexpr (kDcfr) reg[a] = discounted(reg[a], df);
+              else if (cfg.regret_matching_plus && reg[a] < 0) reg[a] = 0;
               if (a < n && reg[a] > 0) sum_pos += reg[a];
             }
 #pragma unroll
@@ -710,8 +730,9 @@ namespace osg_cfr_impl {
 // histories each.  Round 5, forest form: with more subtrees than compute units the bins of the workgroups are packed —
 // whole subtrees if they fit, else the pieces one level below the cut (SubTree's comment) — so that every workgroup
 // sweeps one bin per pass.  OSG_CFR_SUB_PACK=0 keeps a subtree per bin.
-template <int kK, bool kBr = false> const void* cfr_sub_kernel() { return reinterpret_cast<const void*>(&k_cfr_sub<kK, kBr>); }
-const void* cfr_sub_kernel_of(int K, bool br) {
+template <int kK, bool kBr = false, bool kDcfr = false> const void* cfr_sub_kernel() { return reinterpret_cast<const void*>(&k_cfr_sub<kK, kBr, kDcfr>); }
+const void* cfr_sub_kernel_of(int K, bool br, bool dcfr = false) {
+  if (dcfr) return K == 2 ? cfr_sub_kernel<2, false, true>() : (K == 4 ? cfr_sub_kernel<4, false, true>() : cfr_sub_kernel<8, false, true>());   // (never with br)
   if (br) return K == 2 ? cfr_sub_kernel<2, true>() : (K == 4 ? cfr_sub_kernel<4, true>() : cfr_sub_kernel<8, true>());
   return K == 2 ? cfr_sub_kernel<2>() : (K == 4 ? cfr_sub_kernel<4>() : cfr_sub_kernel<8>());
 }
@@ -1016,6 +1037,18 @@ int build_sub(osg_cfr* s) {
   } else {
     (void)hipGetLastError();
   }
+  // the discounting form likewise (else a discounting solver keeps the launches per phase)
+  s->sub_dcfr_ok = false;
+  int per_cu_d = 0;
+  if (raise_lds_cap(cfr_sub_kernel_of(K, false, true), static_cast<int>(lds)) == hipSuccess) {
+    hipError_t ed;
+    if (K == 2) ed = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, k_cfr_sub<2, false, true>, kSubThreads, lds);
+    else if (K == 4) ed = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, k_cfr_sub<4, false, true>, kSubThreads, lds);
+    else ed = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, k_cfr_sub<8, false, true>, kSubThreads, lds);
+    if (ed != hipSuccess) { (void)hipGetLastError(); per_cu_d = 0; }
+  } else {
+    (void)hipGetLastError();
+  }
   int per_cu = 0;
   hipError_t e;
   if (K == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_cfr_sub<2>, kSubThreads, lds);
@@ -1027,6 +1060,7 @@ int build_sub(osg_cfr* s) {
     return OSG_OK;
   }
   const int grid = std::min(G, per_cu * prop.multiProcessorCount);
+  s->sub_dcfr_ok = per_cu_d >= 1 && std::min(G, per_cu_d * prop.multiProcessorCount) >= grid;   // resident on the same grid
   // the fold's shares: a workgroup's run of the updating player's infostates (info_list order), balanced by members
   std::vector<int32_t> fold_info(info_list.size() * 4), fold_off(static_cast<size_t>(s->P) * (grid + 1), 0);
   for (size_t e = 0; e < info_list.size(); ++e) {
@@ -1143,11 +1177,15 @@ static int cfr_sub_run(osg_cfr* s, Tables tb, int iters, const int32_t* br_best,
   }
   hipStream_t st = s->ctx->stream;
   const int per_launch = std::max(1, (1 << 30) / std::max(1, 2 * s->P * s->sub_grid));  // the arrival counter is 32 bits
+  const double* disc0 = nullptr;
+  if (!br_best)
+    if (int rc = cfr_discount_table(s, s->iteration, iters, &disc0)) return rc;
   for (int done = 0; done < iters; done += per_launch) {
     int now = std::min(per_launch, iters - done), it0 = s->iteration + done;
     OSG_HIP(hipMemsetAsync(s->d_sub_bar, 0, sizeof(unsigned int) * kSubBarWords, st));
-    void* args[] = {&tr, &stree, &sp, &tb, &now, &it0, &cfg};
-    const void* kern = cfr_sub_kernel_of(s->sub_K, br_best != nullptr);
+    const double* disc = disc0 ? disc0 + 3 * static_cast<size_t>(done) : nullptr;
+    void* args[] = {&tr, &stree, &sp, &tb, &now, &it0, &cfg, &disc};
+    const void* kern = cfr_sub_kernel_of(s->sub_K, br_best != nullptr, disc != nullptr);
     // (OSG_CFR_PLAIN_LAUNCH=1 as for k_cfr_split: an ordinary launch, for hosts that own the device — and for runs under
     // rocprofv3 --kernel-trace, where a process that made a cooperative launch crashes in an exit handler)
     static const bool plain = std::getenv("OSG_CFR_PLAIN_LAUNCH") && std::getenv("OSG_CFR_PLAIN_LAUNCH")[0] == '1';
@@ -1185,6 +1223,7 @@ static int cfr_sub_run(osg_cfr* s, Tables tb, int iters, const int32_t* br_best,
   }
   s->iteration += iters;
   if (br_best) s->last_kernel = s->sub_forest ? "k_cfr_sub<forest,br>" : (s->sub_G < s->sub_G0 ? "k_cfr_sub<packed,br>" : "k_cfr_sub<br>");
+  else if (disc0) s->last_kernel = s->sub_forest ? "k_cfr_sub<forest,dcfr>" : (s->sub_G < s->sub_G0 ? "k_cfr_sub<packed,dcfr>" : "k_cfr_sub<dcfr>");
   else s->last_kernel = s->sub_forest ? "k_cfr_sub<forest>" : (s->sub_G < s->sub_G0 ? "k_cfr_sub<packed>" : "k_cfr_sub");
   return OSG_OK;
 }
@@ -1204,7 +1243,9 @@ int cfr_sub_br_iterate(osg_cfr* s, Tables tb, const EvalArrays& ea, osg_cfr_cfg 
 
 // A launch per tree level and phase (osg_cfr_iterate's grid_path).
 int cfr_grid_iterate(osg_cfr* s, Tables tb, int iters) {
-  s->last_kernel = "k_gcfr";
+  s->last_kernel = s->dcfr ? "k_gcfr<dcfr>" : "k_gcfr";
+  const double* disc = nullptr;
+  if (int rc = cfr_discount_table(s, s->iteration, iters, &disc)) return rc;
   const int M = static_cast<int>(s->mem.size());
   GridCfr g;
   g.t = s->tree(); g.path_off = s->d_path_off; g.path = s->d_path; g.meta = s->d_meta32;
@@ -1223,8 +1264,12 @@ int cfr_grid_iterate(osg_cfr* s, Tables tb, int iters) {
         const int begin = s->level_off[l], end = s->level_off[l + 1];
         k_gcfr_level<<<blocks(end - begin), dim3(256), 0, st>>>(g, begin, end, q0, q1);
       }
-      k_gcfr_members<<<blocks(M), dim3(256), 0, st>>>(g, upd, s->iteration + it + 1, s->cfg);
-      k_gcfr_fold<<<blocks(s->I * 64), dim3(256), 0, st>>>(g, upd, s->cfg);
+      with_bool(s->dcfr, [&](auto dcfr) {
+        const double* factors = disc ? disc + 3 * static_cast<size_t>(it) : nullptr;
+        k_gcfr_members<decltype(dcfr)::value><<<blocks(M), dim3(256), 0, st>>>(g, upd, s->iteration + it + 1, s->cfg, factors);
+        k_gcfr_fold<decltype(dcfr)::value><<<blocks(s->I * 64), dim3(256), 0, st>>>(g, upd, s->cfg, factors);
+        return OSG_OK;
+      });
     }
   }
   OSG_HIP(hipGetLastError());
@@ -1254,8 +1299,8 @@ int cfr_grid_br_iterate(osg_cfr* s, Tables tb, const EvalArrays& ea, osg_cfr_cfg
         const int begin = s->level_off[l], end = s->level_off[l + 1];
         k_gcfr_level<<<blocks(end - begin), dim3(256), 0, st>>>(g, begin, end, upd, upd + 1);
       }
-      k_gcfr_members<<<blocks(static_cast<int>(M)), dim3(256), 0, st>>>(g, upd, s->iteration + 1, cfg);
-      k_gcfr_fold<<<blocks(s->I * 64), dim3(256), 0, st>>>(g, upd, cfg);
+      k_gcfr_members<false><<<blocks(static_cast<int>(M)), dim3(256), 0, st>>>(g, upd, s->iteration + 1, cfg, nullptr);
+      k_gcfr_fold<false><<<blocks(s->I * 64), dim3(256), 0, st>>>(g, upd, cfg, nullptr);
     }
     ++s->iteration;
   }

@@ -445,8 +445,9 @@ class TabularSolver:
 
     def __init__(self, ctx, game_string, alternating_updates=True, linear_averaging=False,
                  regret_matching_plus=False, mccfr=False, general_kernel=False, epsilon=0.6, replicas=1,
-                 random_initial_regrets=False, seed=0, replica_offset=0):
-        """mccfr: False (CFR family), True / "external" (ES-MCCFR) or "outcome" (OS-MCCFR, `epsilon`)."""
+                 random_initial_regrets=False, seed=0, replica_offset=0, discounting=None):
+        """mccfr: False (CFR family), True / "external" (ES-MCCFR) or "outcome" (OS-MCCFR, `epsilon`).
+        discounting: None, or (alpha, beta, gamma) of Discounted CFR (see set_discounting)."""
         self.ctx = ctx
         self.game_string = game_string
         solver = {False: 0, True: 1, "external": 1, "outcome": 2}[mccfr]
@@ -461,6 +462,16 @@ class TabularSolver:
         check(lib().osg_cfr_sizes(self._h, sizes))
         (self.num_histories, self.num_chance, self.num_decision, self.num_terminal,
          self.num_infostates, self.amax) = [int(v) for v in sizes]
+        self.discounting = None
+        if discounting is not None:
+            self.set_discounting(*discounting)
+
+    def set_discounting(self, alpha=1.5, beta=0, gamma=2, enabled=True):
+        """Discounted CFR (discounted_cfr.py:190-209) for the iterations that follow: after each player's pass of
+        iteration t its regrets are multiplied by t**alpha / (t**alpha + 1) (>= 0) or t**beta / (t**beta + 1) (< 0), and
+        with linear_averaging the average-policy term is weighted by t**gamma.  Needs alternating updates and no RM+."""
+        check(lib().osg_cfr_set_discounting(self._h, 1 if enabled else 0, float(alpha), float(beta), float(gamma)))
+        self.discounting = (alpha, beta, gamma) if enabled else None
 
     def __del__(self):
         try:
@@ -624,3 +635,19 @@ class TabularSolver:
         t = self.tables()
         return {k: [(int(t["legal"][i, a]), float(t["avg_policy"][i, a])) for a in range(t["nact"][i])]
                 for i, k in enumerate(t["keys"])}
+
+
+class DCFRSolver(TabularSolver):
+    """discounted_cfr.DCFRSolver(game, alpha=3/2, beta=0, gamma=2) on the device: alternating updates, linear
+    averaging, no RM+, regrets discounted after every player's pass (Brown & Sandholm 2019)."""
+
+    def __init__(self, ctx, game_string, alpha=1.5, beta=0, gamma=2, **kw):
+        super().__init__(ctx, game_string, alternating_updates=True, linear_averaging=True, regret_matching_plus=False,
+                         discounting=(alpha, beta, gamma), **kw)
+
+
+class LCFRSolver(DCFRSolver):
+    """discounted_cfr.LCFRSolver(game): Linear CFR = DCFR with alpha = beta = gamma = 1."""
+
+    def __init__(self, ctx, game_string, **kw):
+        super().__init__(ctx, game_string, alpha=1, beta=1, gamma=1, **kw)

@@ -31,12 +31,14 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 # KNOWN with the measurement that justified keeping it as it is.
 HOT = [
     "k_step_c4std2", "k_step_c4std<", "k_step_hexvec<3, 2",
-    "k_cfr_small<true, true, 3, 2, 2>", "k_cfr_split<3, false, 512, 3>", "k_cfr_split<3, false, 512, 0>", "k_cfr_split<3, true, 512, 0>",
+    "k_cfr_small<true, true, 3, 2, 2, false>", "k_cfr_split<3, false, 512, 3, false>", "k_cfr_split<3, false, 512, 0, false>", "k_cfr_split<3, true, 512, 0, false>",
+    # their Discounted CFR instantiations (the last template argument)
+    "k_cfr_small<true, true, 3, 2, 2, true>", "k_cfr_split<3, false, 512, 3, true>", "k_cfr_split<3, false, 512, 0, true>", "k_cfr_sub<8, false, true>",
     "k_env_step_x2<osg::C4T<6, 7, 4, unsigned long> >",
     "k_env_step<osg::C4T<6, 7, 4, unsigned long> >",
     "k_env_step_compact_x2<osg::C4T<6, 7, 4, unsigned long> >",
     "k_random_steps<osg::C4T<6, 7, 4, unsigned long> >",
-    "k_cfr_sub<8, false>", "k_cfr_sub<8, true>", "k_mccfr_resident_flat<3>", "k_mcts_advance<osg::Ttt, true, true>", "k_mcts_wave<osg::HexT<3>, true, true, false>",
+    "k_cfr_sub<8, false, false>", "k_cfr_sub<8, true, false>", "k_mccfr_resident_flat<3>", "k_mcts_advance<osg::Ttt, true, true>", "k_mcts_wave<osg::HexT<3>, true, true, false>",
     "k_rollout<osg::HexT<3> >", "k_eval_jobs", "k_geval_", "k_policy_eval", "k_oneshot_allreduce<double>",
     "k_observation_rows<osg::C4T<6, 7, 4, unsigned long>", "k_fold_deltas",
 ]
@@ -49,10 +51,13 @@ KNOWN = {
     "k_geval_persist":
         "opt-in cross-check form of the large-tree evaluation (OSG_EVAL_PERSIST=1; the default is a launch per level, which "
         "measured faster: profiles/r06u_*): 16 scalar registers parked in vector lanes, no scratch",
-    "k_cfr_sub<8, true>":
-        "the CFR-BR pass set of the same kernel (round 6): the code of k_cfr_sub<8, false> with the effective-policy rows staged "
+    "k_cfr_sub<8, false, true>":
+        "the Discounted CFR form of the same kernel: the code of k_cfr_sub<8, false, false> with the iteration's three factors in "
+        "vector registers, a multiply per policy term and a select and a multiply per folded regret; same registers, same reasons",
+    "k_cfr_sub<8, true, false>":
+        "the CFR-BR pass set of the same kernel (round 6): the code of k_cfr_sub<8, false, false> with the effective-policy rows staged "
         "every pass; same registers, same reasons",
-    "k_cfr_sub<8, false>":
+    "k_cfr_sub<8, false, false>":
         "the bin's 24 history descriptors stay in registers across the passes of a launch (round 6): that pushes 52 vector "
         "registers into scratch around the fold and still measured 9 730 -> 10 240 iterations/s against fetching them every "
         "pass with no scratch (profiles/r06p_*); ~180 scalar registers (the kernel's ~40 argument pointers) are parked in "
