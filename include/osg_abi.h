@@ -310,6 +310,43 @@ int osg_mcts_search(const osg_batch* roots, const osg_mcts_cfg* cfg, int32_t* be
                     int32_t* child_visits, double* child_reward, int8_t* child_outcome,
                     double* root_stats, int on_host);
 
+/* algorithms::AlphaBetaSearch (open_spiel/algorithms/minimax.cc:49-137 _alpha_beta, 222-256 the entry; its Python twin
+ * python/algorithms/minimax.py:26-149) for every root of the batch: one deterministic search per root, node for node
+ * the reference's — children in ascending action order (LegalActions()), window (-inf, +inf) at the root
+ * (minimax.cc:250-253), the maximiser replaces on child > value and the minimiser on child < value (minimax.cc:88,122),
+ * cut-off on alpha >= beta (minimax.cc:95-98,129-132), the best action recorded at the root only (minimax.cc:90-92).
+ * tic_tac_toe, connect_four (boards above 64 bits included) and hex of up to 128 cells, with and without swap;
+ * OSG_ERR_UNSUPPORTED for kuhn_poker and leduc_poker (not deterministic: minimax.cc:232) and for larger hex boards.
+ *   depth_limit        < 0: unlimited (the reference's tests pass -1); a node at depth 0 that is not terminal takes
+ *                      the leaf value (minimax.cc:57-65)
+ *   maximizing_player  -1: the player to move at each root (kInvalidPlayer, minimax.cc:244-246; at a terminal root,
+ *                      where the reference has no player to name, the player who would be to move); 0 or 1: that
+ *                      player at every root
+ *   leaf_mode          the reference's value_function is a host callback; the device offers OSG_AB_LEAF_NONE (its
+ *                      absence: the fatal error of minimax.cc:57-61 becomes status 1 of that root) and
+ *                      OSG_AB_LEAF_CONSTANT (value_function = a constant, leaf_value) — with depth_limit D that answers
+ *                      "can the maximiser force a result within D plies?"
+ *   max_nodes          > 0: node budget per root; a root that would need more stops with status 2, so no search
+ *                      holds the device for longer than the caller allowed
+ * OSG_ERR_INVALID: max_nodes <= 0, maximizing_player outside -1..1, an unknown leaf mode.
+ * Outputs (host or device by on_host; all required), per root:
+ *   value [n] f64        the reference's first result: only ever copied from the game's returns or leaf_value, bit for bit
+ *   best_action [n] i32  its second; -1 (kInvalidAction) at a terminal root or at depth_limit 0
+ *   nodes [n] i64        the number of _alpha_beta invocations, the root's included
+ *   status [n] u8        0 done; 1 reached the depth limit with no leaf value; 2 node budget exhausted.  For a status
+ *                        other than 0, value is NaN, best_action -1 and nodes unspecified. */
+#define OSG_AB_LEAF_NONE 0
+#define OSG_AB_LEAF_CONSTANT 1
+typedef struct {
+  int32_t depth_limit;
+  int32_t maximizing_player;
+  int32_t leaf_mode;
+  double leaf_value;
+  int64_t max_nodes;
+} osg_ab_cfg;
+int osg_alpha_beta_search(const osg_batch* roots, const osg_ab_cfg* cfg, double* value, int32_t* best_action,
+                          int64_t* nodes, uint8_t* status, int on_host);
+
 /* ---- MCTS with the Evaluator outside the kernel (Evaluator interface mcts.h:83-92; the batched shape of
  * alpha_zero_torch/vpevaluator.{h,cc}) ------------------------------------------------------------------
  * Search trees for every root of a batch that persist between calls.  osg_mcts_tree_advance runs every

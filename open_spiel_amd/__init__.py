@@ -3,7 +3,7 @@
 A from-scratch HIP (gfx950) implementation of OpenSpiel's data-parallel hot
 path: batched LegalActions / ApplyAction / IsTerminal / Returns /
 ObservationTensor for tic_tac_toe, connect_four, hex, kuhn_poker and
-leduc_poker, random-rollout evaluation and MCTS over batches of roots, and
+leduc_poker, random-rollout evaluation, MCTS and alpha-beta search over batches of roots, and
 tabular CFR / Discounted CFR / external-sampling MCCFR.  The C-ABI is include/osg_abi.h.
 """
 from ._abi import OsgError, describe, lib  # noqa: F401

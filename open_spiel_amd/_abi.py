@@ -54,6 +54,16 @@ class MctsCfg(C.Structure):
     ]
 
 
+class AbCfg(C.Structure):
+    _fields_ = [
+        ("depth_limit", C.c_int32),
+        ("maximizing_player", C.c_int32),
+        ("leaf_mode", C.c_int32),
+        ("leaf_value", C.c_double),
+        ("max_nodes", C.c_int64),
+    ]
+
+
 class CfrCfg(C.Structure):
     _fields_ = [
         ("alternating_updates", C.c_int32),
@@ -112,6 +122,7 @@ SIGNATURES = {
     "osg_synth_batch": (INT, [VP, U64, I64, INT, VP, VP]),
     "osg_rollout": (INT, [VP, U64, I64, INT, VP, VP, INT]),
     "osg_mcts_search": (INT, [VP, C.POINTER(MctsCfg), VP, VP, VP, VP, VP, INT]),
+    "osg_alpha_beta_search": (INT, [VP, C.POINTER(AbCfg), VP, VP, VP, VP, INT]),
     "osg_mcts_tree_create": (INT, [VP, C.POINTER(MctsCfg), INT, C.POINTER(VP)]),
     "osg_mcts_tree_destroy": (INT, [VP]),
     "osg_mcts_tree_advance": (INT, [VP, VP, VP, VP, VP, INT, C.POINTER(I64)]),

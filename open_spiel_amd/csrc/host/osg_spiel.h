@@ -2914,6 +2914,82 @@ inline std::vector<std::unique_ptr<State>> GetAllHistories(const Game& game, int
   return all;
 }
 
+// algorithms/minimax.h:25-50, minimax.cc:222-256: AlphaBetaSearch with the reference's signature and game-type checks
+// (minimax.cc:226-235).  Without a value_function the search is ONE device search of the root (osg_alpha_beta_search,
+// node for node the reference's) under a finite node budget — the extra trailing parameter; 2^26 is a choice, not a
+// measurement: a search that runs away must not hold a shared device —; the reference's fatal error at the depth limit
+// (minimax.cc:57-61) is raised with its message, an exhausted budget with one that names the budget.  With a
+// value_function — a host callback no kernel can call — the recursion of minimax.cc:49-137 runs on the host over mirror
+// states: one device round trip per State call, compatibility speed, for small trees and shallow depths only.
+// ExpectiminimaxSearch stays undeclared: no device game is both perfect-information and stochastic.
+inline constexpr int64_t kDefaultAlphaBetaNodeBudget = int64_t{1} << 26;
+namespace internal {
+inline double AlphaBetaOnHost(State* state, int depth, double alpha, double beta,
+                              const std::function<double(const State&)>& value_function, Player maximizing_player,
+                              Action* best_action, bool use_undo) {
+  if (state->IsTerminal()) return state->PlayerReturn(maximizing_player);
+  if (depth == 0) return value_function(*state);
+  const Player player = state->CurrentPlayer();
+  const bool maximizing = player == maximizing_player;
+  double value = maximizing ? -std::numeric_limits<double>::infinity() : std::numeric_limits<double>::infinity();
+  for (Action action : state->LegalActions()) {
+    double child_value;
+    if (use_undo) {
+      state->ApplyAction(action);
+      child_value = AlphaBetaOnHost(state, depth - 1, alpha, beta, value_function, maximizing_player, nullptr, use_undo);
+      state->UndoAction(player, action);
+    } else {
+      std::unique_ptr<State> child = state->Child(action);
+      child_value = AlphaBetaOnHost(child.get(), depth - 1, alpha, beta, value_function, maximizing_player, nullptr, use_undo);
+    }
+    if (maximizing ? child_value > value : child_value < value) {
+      value = child_value;
+      if (best_action != nullptr) *best_action = action;
+    }
+    if (maximizing) alpha = std::max(alpha, value); else beta = std::min(beta, value);
+    if (alpha >= beta) break;
+  }
+  return value;
+}
+}  // namespace internal
+inline std::pair<double, Action> AlphaBetaSearch(const Game& game, const State* state,
+                                                 std::function<double(const State&)> value_function, int depth_limit,
+                                                 Player maximizing_player, bool use_undo = true,
+                                                 int64_t max_nodes = kDefaultAlphaBetaNodeBudget) {
+  if (game.NumPlayers() > 2) SpielFatalError("AlphaBetaSearch: game.NumPlayers() <= 2");
+  const GameType game_info = game.GetType();
+  if (game_info.chance_mode != GameType::ChanceMode::kDeterministic) SpielFatalError("AlphaBetaSearch: the game must be deterministic");
+  if (game_info.dynamics != GameType::Dynamics::kSequential) SpielFatalError("AlphaBetaSearch: the game must be sequential");
+  if (game_info.utility != GameType::Utility::kZeroSum) SpielFatalError("AlphaBetaSearch: the game must be zero-sum");
+  if (game_info.reward_model != GameType::RewardModel::kTerminal) SpielFatalError("AlphaBetaSearch: the game must have terminal rewards");
+  const std::unique_ptr<State> search_root = state == nullptr ? game.NewInitialState() : state->Clone();
+  if (value_function) {
+    if (maximizing_player == kInvalidPlayer) maximizing_player = search_root->CurrentPlayer();
+    Action best_action = kInvalidAction;
+    const double infinity = std::numeric_limits<double>::infinity();
+    const double value = internal::AlphaBetaOnHost(search_root.get(), depth_limit, -infinity, infinity, value_function,
+                                                   maximizing_player, &best_action, use_undo);
+    return {value, best_action};
+  }
+  osg_ab_cfg cfg;
+  cfg.depth_limit = depth_limit;
+  cfg.maximizing_player = maximizing_player == kInvalidPlayer ? -1 : maximizing_player;
+  cfg.leaf_mode = OSG_AB_LEAF_NONE;
+  cfg.leaf_value = 0.0;
+  cfg.max_nodes = max_nodes;
+  double value = 0.0;
+  int32_t best_action = -1;
+  int64_t nodes = 0;
+  uint8_t status = 0;
+  Check(osg_alpha_beta_search(search_root->Batch().handle(), &cfg, &value, &best_action, &nodes, &status, 1));
+  if (status == 1)
+    SpielFatalError("We assume we can walk the full depth of the tree. Try increasing depth or provide a value_function.");
+  if (status != 0)
+    SpielFatalError("AlphaBetaSearch: the search needs more than its node budget of " + std::to_string(max_nodes) +
+                    " nodes (the trailing max_nodes parameter)");
+  return {value, best_action < 0 ? kInvalidAction : static_cast<Action>(best_action)};
+}
+
 enum class AverageType { kSimple, kFull };
 
 // The MCCFR solvers' text checkpoints (external_sampling_mccfr.cc:82-120,233-288;

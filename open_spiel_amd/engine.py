@@ -435,6 +435,26 @@ class StateBatch:
         return dict(best_action=best, child_visits=visits, child_reward=reward, child_outcome=outcome,
                     root_stats=stats)
 
+    def alpha_beta_search(self, depth_limit=-1, maximizing_player=None, leaf_value=None, max_nodes=1 << 22,
+                          on_host=False):
+        """algorithms.minimax.alpha_beta_search for every root, node for node (tic_tac_toe, connect_four, hex up to
+        128 cells).  depth_limit < 0: unlimited; maximizing_player None: the player to move at each root;
+        leaf_value: the constant a `value_function=lambda s: c` would return at the depth limit (None: no value
+        function); max_nodes: node budget per root.  Returns (value f64, best_action i32, nodes i64, status u8), on the
+        device unless on_host.  status 0 done, 1 depth limit reached with no leaf value (the reference's
+        NotImplementedError), 2 budget exhausted — reported per root, never raised; value is NaN there."""
+        cfg = _abi.AbCfg(int(depth_limit), -1 if maximizing_player is None else int(maximizing_player),
+                         0 if leaf_value is None else 1, 0.0 if leaf_value is None else float(leaf_value), int(max_nodes))
+        if on_host:
+            value, best = torch.empty(self.n, dtype=torch.float64), torch.empty(self.n, dtype=torch.int32)
+            nodes, status = torch.empty(self.n, dtype=torch.int64), torch.empty(self.n, dtype=torch.uint8)
+        else:
+            value, best = self._dev((self.n,), torch.float64), self._dev((self.n,), torch.int32)
+            nodes, status = self._dev((self.n,), torch.int64), self._dev((self.n,), torch.uint8)
+        check(lib().osg_alpha_beta_search(self._h, C.byref(cfg), _ptr(value), _ptr(best), _ptr(nodes), _ptr(status),
+                                          1 if on_host else 0))
+        return value, best, nodes, status
+
 
 class TabularSolver:
     """CFRSolver / CFRPlusSolver / external-sampling MCCFR on the device.

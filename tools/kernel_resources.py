@@ -41,6 +41,8 @@ HOT = [
     "k_cfr_sub<8, false, false>", "k_cfr_sub<8, true, false>", "k_mccfr_resident_flat<3>", "k_mcts_advance<osg::Ttt, true, true>", "k_mcts_wave<osg::HexT<3>, true, true, false>",
     "k_rollout<osg::HexT<3> >", "k_eval_jobs", "k_geval_", "k_policy_eval", "k_oneshot_allreduce<double>",
     "k_observation_rows<osg::C4T<6, 7, 4, unsigned long>", "k_fold_deltas",
+    # the alpha-beta search of the probe's three workloads (tools/probe_minimax.py)
+    "k_alpha_beta<osg::Ttt>", "k_alpha_beta<osg::C4T<6, 7, 4, unsigned long> >", "k_alpha_beta<osg::HexT<3> >",
 ]
 # Hot kernels whose parked registers / scratch are known, measured and kept (the note says where the decision is recorded).
 KNOWN = {
@@ -70,6 +72,9 @@ KNOWN = {
         "the one-root search: ONE searching wavefront per launch by construction (1 wave per SIMD is its occupancy whatever "
         "the register count), 72 scalar registers parked in vector lanes; round 6 took its node accesses off volatile "
         "(12.39 -> 11.68 ms per 1000-simulation search, profiles/r06d_one_root_noderef_ab.txt)",
+    "k_alpha_beta<osg::HexT<3> >":
+        "36 scalar registers parked in vector lanes (v_readlane, no memory), no scratch, no LDS, 5 waves per SIMD: the hex(9) "
+        "parameter block (five 3-word bit sets) beside a frame of 12 eight-byte words in registers — no form without them has been measured",
     "k_rollout<osg::HexT<3> >":
         "41 scalar registers parked in vector lanes (v_readlane, no memory), no scratch, 6 waves per SIMD; RandomRolloutEvaluator "
         "of hex(9) outside the search kernel (config 4's playouts run inside k_mcts_wave) — no form without them has been measured",
