@@ -495,6 +495,37 @@ int osg_mccfr_sample_uniforms(osg_cfr* s, int player, const double* h_uniforms, 
  * the other players following their best responses, ApplyRegretMatching. */
 int osg_cfr_br_iterate(osg_cfr* s, int iters);
 
+/* Extensive-form fictitious play: XFPSolver.iteration() (open_spiel/python/algorithms/fictitious_play.py:165-240; Heinrich,
+ * Lanctot and Silver 2015, Algorithm 1) x iters on a CFRSolverBase object (solver 0, one replica, no discounting).  The
+ * AVERAGE policy lives in the current-policy table, uniform after osg_cfr_create / osg_cfr_reset; the regret and
+ * cumulative-policy tables are not touched, and a later osg_cfr_iterate overwrites the current-policy table.  One
+ * iteration: every player's best response to the average policy (TabularBestResponse, best_response.cc:194-227: the first
+ * legal action with the maximal counterfactual-weighted value; the first legal action where there is no counterfactual
+ * reach), then at every infostate of player p, with alpha = 1 / (iterations + 1) formed on the host in double precision
+ * after the counter was raised (fictitious_play.py:166,228), avg_reach / br_reach the products of p's own action
+ * probabilities on the way there under the average policy / the best response (1.0 at the root, multiplied root to leaf,
+ * all taken from the table as it was before the iteration),
+ *   new[a] = avg[a] + (alpha * br_reach * (br[a] - avg[a])) / ((1.0 - alpha) * avg_reach + alpha * br_reach)
+ * in exactly that order (fictitious_play.py:232-236), not contracted.  osg_cfr_iteration counts the iterations.  A
+ * checkpoint is restored with osg_cfr_upload_tables(cur_policy) and osg_cfr_set_iteration; an uploaded policy with zero
+ * probabilities gives the reference's IEEE result where both reaches vanish (0 / 0 = NaN), not an error.
+ * OSG_ERR_INVALID for an MCCFR solver and for a discounting solver, OSG_ERR_UNSUPPORTED for replicas > 1 and for a tree
+ * with an information state that spans several levels; the message names the reason.
+ * osg_cfr_last_kernel afterwards: "k_xfp_small" — ONE launch of one workgroup for all iterations, the policy and the best
+ * response's scratch in LDS (trees one workgroup evaluates: the kuhn_poker family) —, or the general form, a best-response
+ * evaluation and two launches (reach, update) per iteration, named after the evaluation it used: "k_xfp<k_policy_eval>",
+ * "k_xfp<k_eval_jobs>" (leduc_poker), "k_xfp<k_geval>" (3-player leduc_poker; osg_cfr_cfg.kernel = 2 forces it).
+ * osg_cfr_cfg.kernel = 1 forces the general form with the one-workgroup evaluation.  Both forms give the same bits. */
+int osg_xfp_iterate(osg_cfr* s, int iters);
+/* The averaging half of one iteration (fictitious_play.py:184-240) with the CALLER's best responses: h_best_index [I], an
+ * index among each row's legal actions as osg_cfr_best_response returns it.  Raises the iteration counter.  This is where
+ * approximate or learned best responses enter (fictitious self-play).  OSG_ERR_INVALID for an index out of range: the
+ * table and the counter are left as they were.  osg_cfr_last_kernel: "k_xfp_update". */
+int osg_xfp_update(osg_cfr* s, const int32_t* h_best_index);
+/* Diagnostic: the two [I] vectors avg_reach and br_reach the next update would use, for h_best_index as above or, where it
+ * is NULL, for the device's own best responses to the current-policy table.  Changes neither table nor counter. */
+int osg_xfp_reaches(osg_cfr* s, const int32_t* h_best_index, double* h_avg_reach, double* h_br_reach);
+
 /* ExternalSamplingMCCFRSolver::RunIteration (external_sampling_mccfr.cc:71-186,
  * AverageType::kSimple) for `trajectories` traverser passes (player = global
  * trajectory index mod P), mini-batched: every trajectory of one call reads the

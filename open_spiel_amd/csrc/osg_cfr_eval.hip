@@ -55,62 +55,7 @@ k_policy_eval(Tree t, EvalArrays ea, const double* pol, int from_cum = 0, double
     __syncthreads();
   }
   if (tid < P) ea.out[tid] = ea.value[tid];
-  // ---- best response of every player ----
-  for (int r = 0; r < P; ++r) {
-    for (int m = tid; m < ea.M; m += nt) {
-      const int h = t.mem[m];
-      if (t.actor[h] != r) continue;
-      double cf = 1.0;
-      for (int e = ea.path_off[m]; e < ea.path_off[m + 1]; ++e) {
-        const int code = ea.path[e];
-        const int slot = (code >> 24) & 0xF, idx = code & 0x7FFFFF;
-        const double pr = ((code >> 23) & 1) ? t.edge_prob[idx] : (slot == r ? 1.0 : pol[idx]);
-        cf = cf * pr;
-      }
-      ea.cf[m] = cf;
-    }
-    __syncthreads();
-    for (int l = t.D - 1; l >= 0; --l) {
-      for (int i = tid; i < t.I; i += nt) {
-        if (t.info_player[i] != r || ea.info_level[i] != l) continue;
-        const int n = t.nact[i];
-        int best = -1;
-        double best_v = -1.7976931348623157e308;  // numeric_limits<double>::lowest()
-        for (int a = 0; a < n; ++a) {
-          double v = 0.0;
-          for (int m = t.mem_off[i]; m < t.mem_off[i + 1]; ++m)
-            v += ea.cf[m] * ea.brv[t.first_child[t.mem[m]] + a];
-          if (v > best_v) { best_v = v; best = a; }
-        }
-        ea.best[i] = best < 0 ? 0 : best;
-      }
-      __syncthreads();
-      for (int h = t.level_off[l] + tid; h < t.level_off[l + 1]; h += nt) {
-        const int k = t.kind[h];
-        double v = 0.0;
-        if (k == kTerminalNode) {
-          v = t.term_ret[h * P + r];
-        } else {
-          const int fc = t.first_child[h], nc = t.nchild[h];
-          if (k == kDecisionNode && t.actor[h] == r) {
-            v += 1.0 * ea.brv[fc + ea.best[t.info[h]]];
-          } else {
-            const int row = k == kDecisionNode ? t.info[h] * A : 0;
-            for (int a = 0; a < nc; ++a) {
-              const double pr = k == kChanceNode ? t.edge_prob[fc + a] : pol[row + a];
-              v += pr * ea.brv[fc + a];
-            }
-          }
-        }
-        ea.brv[h] = v;
-      }
-      __syncthreads();
-    }
-    if (tid == 0) ea.out[P + r] = ea.brv[0];
-    if (ea.keep && r == ea.keep_r)
-      for (int h = tid; h < t.H; h += nt) ea.keep[h] = ea.brv[h];
-    __syncthreads();
-  }
+  policy_eval_best_responses(t, ea, pol);
 }
 
 // ---------------------------------------------------------------------------

@@ -671,3 +671,85 @@ class LCFRSolver(DCFRSolver):
 
     def __init__(self, ctx, game_string, **kw):
         super().__init__(ctx, game_string, alpha=1, beta=1, gamma=1, **kw)
+
+
+class XFPSolver(TabularSolver):
+    """fictitious_play.XFPSolver(game) on the device: extensive-form fictitious play (Heinrich, Lanctot and Silver 2015,
+    Algorithm 1).  XFP has no parameters.  The average policy lives in the solver's current-policy table (uniform at the
+    start); every iteration mixes every player's best response to it into it (osg_xfp_iterate in include/osg_abi.h has
+    the arithmetic).  The trajectory depends on argmax decisions: where the reference's best response sits on an exact
+    or rounding-level tie, feed that iteration's best response through update().
+    general_kernel: as for TabularSolver (True: the general per-iteration form where the fused kernel applies; "grid":
+    the best response by a launch per level).  The reference's save_oracles and get_empirical_metagame are out of
+    scope: no best response is kept beyond its iteration."""
+
+    def __init__(self, ctx, game_string, general_kernel=False):
+        super().__init__(ctx, game_string, alternating_updates=True, linear_averaging=False, regret_matching_plus=False,
+                         general_kernel=general_kernel)
+
+    def iteration(self):
+        """XFPSolver.iteration() (fictitious_play.py:165-168).  The reference's method takes the name of TabularSolver's
+        counter property; the counter is `iterations` here, as the reference calls its own."""
+        self.iterate(1)
+
+    @property
+    def iterations(self):
+        """Fictitious-play iterations done so far (osg_cfr_iteration)."""
+        return lib().osg_cfr_iteration(self._h)
+
+    def iterate(self, iters=1):
+        check(lib().osg_xfp_iterate(self._h, int(iters)))
+
+    def best_responses(self):
+        """Every player's best response to the average policy: ([I] int32 indices among each row's legal actions, [P]
+        best-response values)."""
+        best = np.zeros(self.num_infostates, np.int32)
+        values = np.zeros(_abi.describe(self.game_string).num_players)
+        check(lib().osg_cfr_best_response(self._h, 1, None, best.ctypes.data, values.ctypes.data))
+        return best, values
+
+    def _best_index(self, best_index):
+        best = np.ascontiguousarray(best_index, np.int32)
+        if best.shape != (self.num_infostates,):
+            raise OsgError(f"best_index: expected {self.num_infostates} indices, one per information state")
+        return best
+
+    def update(self, best_index):
+        """The averaging half of one iteration with the caller's best responses (osg_xfp_update)."""
+        best = self._best_index(best_index)
+        check(lib().osg_xfp_update(self._h, best.ctypes.data))
+
+    def reaches(self, best_index=None):
+        """(avg_reach [I], br_reach [I]) the next update would use; best_index None: the device's own best responses."""
+        best = None if best_index is None else self._best_index(best_index)
+        avg, br = np.zeros(self.num_infostates), np.zeros(self.num_infostates)
+        check(lib().osg_xfp_reaches(self._h, None if best is None else best.ctypes.data, avg.ctypes.data, br.ctypes.data))
+        return avg, br
+
+    def evaluate_and_update_policy(self, iters=1):
+        raise OsgError("XFPSolver: iterate() / iteration() advance fictitious play; a CFR iteration would overwrite the average policy")
+
+    evaluate_and_update_policy_cfr_br = evaluate_and_update_policy
+
+    def evaluate_policy(self, which="current", table=None):
+        return super().evaluate_policy(which, table)
+
+    def nash_conv(self):
+        return self.evaluate_policy("current")["nash_conv"]
+
+    def exploitability(self):
+        return self.evaluate_policy("current")["exploitability"]
+
+    def average_policy_tables(self):
+        """XFPSolver.average_policy_tables(): per player, {infostate string: {action: probability}}."""
+        t = self.tables()
+        out = [{} for _ in range(_abi.describe(self.game_string).num_players)]
+        for i, k in enumerate(t["keys"]):
+            player = lib().osg_cfr_infostate_player(self._h, i)
+            out[player][k] = {int(t["legal"][i, a]): float(t["cur_policy"][i, a]) for a in range(t["nact"][i])}
+        return out
+
+    def average_policy(self):
+        t = self.tables()
+        return {k: [(int(t["legal"][i, a]), float(t["cur_policy"][i, a])) for a in range(t["nact"][i])]
+                for i, k in enumerate(t["keys"])}
