@@ -286,7 +286,9 @@ struct C4T {
   // placement — a line it has not got then, it had not got before either (a subset) — and only where that test fires
   // (a winning move, or an uploaded position that was over already) the plane as it was is tested too.  Returns the
   // successor's open columns (0 when the game is over); same results as the generic sequence, case by case
-  // (tests/test_gpu_parity.py steps these boards against the oracle at every ply).
+  // (tests/test_z15_gpu_win_geometry.py steps these boards through a history for every line placement of every
+  // direction and colour, draws, wins on the last cell and column-wrap near misses, against the oracle at every ply;
+  // tests/test_gpu_parity.py does the same on random playouts).
   OSG_D static uint32_t fused_step(const Params& p, State& s, int a, bool& illegal, bool& term, int& outcome) {
     const int H = R(p) + 1;
     const BB all = s.x | s.o, tp = top(p);
@@ -648,12 +650,16 @@ struct HexT {
     if (a && b) {
       res = player == 0 ? 1u : 2u;  // Win label; no flood fill (hex.cc:248-252)
     } else if (a || b) {
-      // flood the plain same-colour group reachable from the new stone
+      // flood the plain same-colour group reachable from the new stone.  The reference floods without a bound
+      // (hex.cc:262-276); here every step that goes on adds at least one cell, so the number of cells the planes hold
+      // (32 * NW, as in fill_playout_winner) bounds the steps on every board.  (A fixed 128 was exact only up to 128
+      // cells: a chain winding through a 19 x 19 board is over 150 steps deep, and the cells beyond the cap kept
+      // their plain label — tests/test_z15_gpu_win_geometry.py.)
       const Bits own = sel(player == 0, s.black, s.white);
       Bits plain = bandn(bandn(own, s.ea), s.eb);
       Bits region = zero();
       Bits frontier = single(move);
-      for (int it = 0; it < 128; ++it) {
+      for (int it = 0; it < 32 * NW; ++it) {
         Bits grow = bandn(band(neighbours(p, frontier), plain), region);
         if (!any(grow)) break;
         region = bor(region, grow);
