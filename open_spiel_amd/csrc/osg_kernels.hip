@@ -1967,7 +1967,8 @@ int osg_step(const osg_batch* src, osg_batch* dst, const uint8_t* d_actions, voi
   const int W = src->spec.desc.mask_words;
   const int64_t n = src->n;
   // d_mask == NULL ("do not write the successor's mask"): hex only, where the mask is ~occupied of the successor record
-  if (!d_mask && !(src->spec.desc.game_kind == kHex && cmb == 4 * W && W == src->spec.hex_nw && W <= 4))
+  // (a board of up to 16 cells has a 1- or 2-byte compact mask; with no mask to write its format does not matter)
+  if (!d_mask && !(src->spec.desc.game_kind == kHex && W == src->spec.hex_nw && W <= 4))
     return set_error(OSG_ERR_UNSUPPORTED, "osg_step: d_mask may be NULL only for hex boards of up to 128 cells (there the successor's "
                                           "mask is ~occupied of the record written); every other game's mask comes from the step itself");
   // the kernels that move several states per lane use 16-byte plane accesses: planes start 16-byte aligned when the
@@ -2027,7 +2028,7 @@ int osg_step(const osg_batch* src, osg_batch* dst, const uint8_t* d_actions, voi
     return OSG_OK;
   }
   // hex: V states per thread (16-byte plane accesses with V = 4); the mask rows are the [n, NW] u32 output
-  if (kind == kHex && cmb == 4 * W && W == src->spec.hex_nw && W <= 4) {   // (the big boards: one state per thread, below)
+  if (kind == kHex && (cmb == 4 * W || !d_mask) && W == src->spec.hex_nw && W <= 4) {   // (the big boards: one state per thread, below)
     // OSG_HEX_STEP="<states per thread>:<non-temporal 0|1>" overrides the choice (a tuning knob; results do not depend on it)
     int v = 2, nt = n >= (int64_t{1} << 22) ? 1 : 0;
     if (const char* e = std::getenv("OSG_HEX_STEP")) {
