@@ -526,6 +526,42 @@ int osg_xfp_update(osg_cfr* s, const int32_t* h_best_index);
  * is NULL, for the device's own best responses to the current-policy table.  Changes neither table nor counter. */
 int osg_xfp_reaches(osg_cfr* s, const int32_t* h_best_index, double* h_avg_reach, double* h_br_reach);
 
+/* Magnetic mirror descent over the sequence form with dilated entropy: MMDDilatedEnt
+ * (open_spiel/python/algorithms/mmd_dilated.py:132-366 with sequence_form_utils.py:120-228,325-389; Sokota et al. 2023,
+ * arXiv 2206.05825) on a CFRSolverBase object (solver 0, no discounting) of a two-player zero-sum game.  The behavioural
+ * policy pi lives in the current-policy table and the average sequences avg_x in the cumulative-policy table, so
+ * osg_cfr_tables(avg_policy) and osg_cfr_evaluate_policy(which = 0) give the average policy (sequence_to_policy,
+ * sequence_form_utils.py:284-322) and which = 1 the last iterate; the regret table is not touched.  With alpha > 0 the last
+ * iterate converges linearly to the alpha-reduced normal-form QRE, with alpha = 0 the average converges to a Nash
+ * equilibrium.  csrc/osg_mmd.h has the arithmetic of one update_sequences() (mmd_dilated.py:261-323) and its fixed
+ * orders of summation; no floating-point atomics, two runs and both kernel forms give the same bits.
+ *
+ * osg_mmd_default_stepsize: alpha / max|payoff_mat|^2 (mmd_dilated.py:169), the matrix formed on the host once per solver
+ * (sequence_form_utils.py:148-153,207-228). */
+int osg_mmd_default_stepsize(osg_cfr* s, double alpha, double* out);
+/* alpha[n], stepsize[n]: one pair per replica (n = osg_cfr_replicas).  The first accepted call puts the solver into
+ * mirror-descent mode (mmd_dilated.py:174-176): avg_x = x of the current-policy table (uniform on a fresh solver), counter 0.
+ * Later calls change the parameters only, so an annealing schedule keeps the state (the reference's `alpha` and `stepsize`
+ * attributes).  OSG_ERR_INVALID for an MCCFR or a discounting solver, n != replicas, and a negative or non-finite alpha or
+ * stepsize (mmd_dilated.py:149); OSG_ERR_UNSUPPORTED for a game with other than two players (mmd_dilated.py:142), an
+ * information state that spans several tree levels, and replicas > 1 where only the general form serves the solver.  A
+ * refused call changes nothing.  In mirror-descent mode osg_cfr_iterate, osg_cfr_br_iterate and osg_xfp_iterate answer
+ * OSG_ERR_INVALID; osg_cfr_reset returns to the uniform start (avg_x = x, counter 0) and keeps the parameters. */
+int osg_mmd_set_params(osg_cfr* s, int n, const double* alpha, const double* stepsize);
+/* update_sequences() x iters (mmd_dilated.py:261-281) for every replica, each with its own pair.  osg_cfr_iteration counts
+ * the calls (the reference's iteration_count - 1).  A checkpoint is osg_cfr_upload_tables(cum_policy = avg_x, cur_policy =
+ * pi) and osg_cfr_set_iteration.  OSG_ERR_INVALID before osg_mmd_set_params.  osg_cfr_last_kernel afterwards:
+ * "k_mmd_small" — ONE launch for all iterations, a workgroup per replica with pi, x, avg_x in LDS (tables up to 128 KiB:
+ * the kuhn_poker family, leduc_poker) —, or "k_mmd", a launch per infostate level and one for the average per iteration
+ * (osg_cfr_cfg.kernel = 1 forces it; one replica). */
+int osg_mmd_iterate(osg_cfr* s, int iters);
+/* get_gap() (mmd_dilated.py:325-359) of the selected replica's policy at its alpha: the saddle-point gap of the
+ * regularised game.  OSG_ERR_INVALID where that alpha is 0 (mmd_dilated.py:333).  Changes neither table nor counter. */
+int osg_mmd_gap(osg_cfr* s, double* out);
+/* current_sequences() (which = 0, mmd_dilated.py:368-374: x of the current-policy table) or get_avg_sequences() (which = 1,
+ * :376-382) of the selected replica as an [I, Amax] host array, cell (I, a) the sequence value, padding 0. */
+int osg_mmd_sequences(osg_cfr* s, int which, double* h_x);
+
 /* ExternalSamplingMCCFRSolver::RunIteration (external_sampling_mccfr.cc:71-186,
  * AverageType::kSimple) for `trajectories` traverser passes (player = global
  * trajectory index mod P), mini-batched: every trajectory of one call reads the

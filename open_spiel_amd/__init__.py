@@ -4,7 +4,8 @@ A from-scratch HIP (gfx950) implementation of OpenSpiel's data-parallel hot
 path: batched LegalActions / ApplyAction / IsTerminal / Returns /
 ObservationTensor for tic_tac_toe, connect_four, hex, kuhn_poker and
 leduc_poker, random-rollout evaluation, MCTS and alpha-beta search over batches of roots, and
-tabular CFR / Discounted CFR / external-sampling MCCFR / extensive-form fictitious play.  The C-ABI is include/osg_abi.h.
+tabular CFR / Discounted CFR / external-sampling MCCFR / extensive-form fictitious play /
+magnetic mirror descent.  The C-ABI is include/osg_abi.h.
 """
 from ._abi import OsgError, describe, lib  # noqa: F401
 
@@ -27,7 +28,7 @@ def __getattr__(name):
         return importlib.import_module(".pyspiel_hip", __name__)
     # torch-backed classes are imported lazily so that `import open_spiel_amd`
     # (and the ABI symbol check) works without touching torch.
-    if name in ("Context", "Game", "StateBatch", "TabularSolver", "DCFRSolver", "LCFRSolver", "XFPSolver"):
+    if name in ("Context", "Game", "StateBatch", "TabularSolver", "DCFRSolver", "LCFRSolver", "XFPSolver", "MMDSolver"):
         from . import engine
         return getattr(engine, name)
     if name in ("BatchedEnvironment", "TimeStep", "StepType", "ObservationType"):

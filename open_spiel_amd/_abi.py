@@ -154,6 +154,11 @@ SIGNATURES = {
     "osg_xfp_iterate": (INT, [VP, INT]),
     "osg_xfp_update": (INT, [VP, VP]),
     "osg_xfp_reaches": (INT, [VP, VP, VP, VP]),
+    "osg_mmd_default_stepsize": (INT, [VP, C.c_double, VP]),
+    "osg_mmd_set_params": (INT, [VP, INT, VP, VP]),
+    "osg_mmd_iterate": (INT, [VP, INT]),
+    "osg_mmd_gap": (INT, [VP, VP]),
+    "osg_mmd_sequences": (INT, [VP, INT, VP]),
     "osg_mccfr_iterate": (INT, [VP, U64, I64, I64]),
     "osg_cfr_table_ptrs": (INT, [VP, C.POINTER(VP), C.POINTER(VP), C.POINTER(VP)]),
     "osg_mccfr_delta_ptrs": (INT, [VP, C.POINTER(VP), C.POINTER(VP)]),

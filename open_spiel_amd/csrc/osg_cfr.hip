@@ -488,6 +488,7 @@ int osg_cfr_destroy(osg_cfr* s) {
                   s->d_jobs_mem, s->d_jobs_deal, s->d_jobs_ticket, s->d_disc};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  mmd_destroy(s);
   if (s->h_sub_err) (void)hipHostFree(s->h_sub_err);
   if (s->h_eval_out) (void)hipHostFree(s->h_eval_out);
   osg::ctx_release(s->ctx);
@@ -501,10 +502,14 @@ int osg_cfr_sizes(const osg_cfr* s, int64_t* out) {
   return OSG_OK;
 }
 
-int osg_cfr_reset(osg_cfr* s) { return init_tables(s); }
+int osg_cfr_reset(osg_cfr* s) {
+  if (int rc = init_tables(s)) return rc;
+  return mmd_mode(s) ? mmd_after_reset(s) : OSG_OK;   // (mirror descent keeps its parameters and starts from avg_x = x again)
+}
 
 int osg_cfr_iterate(osg_cfr* s, int iters) {
   if (!s || iters < 0) return set_error(OSG_ERR_INVALID, "osg_cfr_iterate: bad argument");
+  if (mmd_mode(s)) return set_error(OSG_ERR_INVALID, "osg_cfr_iterate: the solver is in mirror-descent mode (osg_mmd_set_params); a CFR iteration would overwrite its tables");
   if (iters == 0) return OSG_OK;
   if (int rc = cfr_sub_error(s)) return rc;
   int threads = ((s->max_level_width + 63) / 64) * 64;
@@ -550,6 +555,7 @@ int osg_cfr_iterate(osg_cfr* s, int iters) {
 
 int osg_cfr_br_iterate(osg_cfr* s, int iters) {
   if (!s || iters < 0) return set_error(OSG_ERR_INVALID, "osg_cfr_br_iterate: bad argument");
+  if (mmd_mode(s)) return set_error(OSG_ERR_INVALID, "osg_cfr_br_iterate: the solver is in mirror-descent mode (osg_mmd_set_params); a CFR-BR iteration would overwrite its tables");
   if (s->cfg.solver != 0) return set_error(OSG_ERR_INVALID, "osg_cfr_br_iterate: needs a CFRSolverBase table (solver 0)");
   if (s->dcfr) return set_error(OSG_ERR_INVALID, "osg_cfr_br_iterate: CFRBRSolver is plain CFR, this solver discounts (osg_cfr_set_discounting)");
   if (s->cfg.linear_averaging || s->cfg.regret_matching_plus)

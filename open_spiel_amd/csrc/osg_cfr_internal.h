@@ -362,6 +362,8 @@ struct ResidentTree {
 
 constexpr int kMaxOsDepth = 32;
 
+struct MmdState;   // magnetic mirror descent's host-built arrays and parameters (osg_cfr_mmd.hip)
+
 template <class T>
 int upload(const std::vector<T>& v, T** d, hipStream_t stream) {
   const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
@@ -484,6 +486,8 @@ struct osg_cfr {
   int n_uret = 0, n_uprob = 0, num_cus = 0;
   uint64_t* d_rec = nullptr;
   double *d_uret = nullptr, *d_uprob = nullptr;
+  // magnetic mirror descent (osg_cfr_mmd.hip): built at the first osg_mmd_* call
+  MmdState* mmd = nullptr;
 
   Tree tree() const {
     Tree t;
@@ -534,4 +538,8 @@ int launch_grid_eval(const osg_cfr* s, const EvalArrays& ea, const double* src, 
 int cfr_best_responses_to_current(osg_cfr* s, const EvalArrays& ea, int threads, bool jobs);   // every player's best response (CFR-BR)
 // ---- osg_cfr_mccfr.hip ----
 int build_resident_tree(osg_cfr* s);
+// ---- osg_cfr_mmd.hip ----
+bool mmd_mode(const osg_cfr* s);       // osg_mmd_set_params was accepted: pi and avg_x live in the cur and cum tables
+int mmd_after_reset(osg_cfr* s);       // avg_x = x of the fresh uniform policy
+void mmd_destroy(osg_cfr* s);
 }  // namespace osg_cfr_impl

@@ -222,6 +222,7 @@ extern "C" {
 
 int osg_xfp_iterate(osg_cfr* s, int iters) {
   if (!s || iters < 0) return set_error(OSG_ERR_INVALID, "osg_xfp_iterate: bad argument");
+  if (mmd_mode(s)) return set_error(OSG_ERR_INVALID, "osg_xfp_iterate: the solver is in mirror-descent mode (osg_mmd_set_params); fictitious play would overwrite its policy table");
   if (int rc = xfp_refusal(s, "osg_xfp_iterate")) return rc;
   if (iters == 0) return OSG_OK;
   hipStream_t st = s->ctx->stream;

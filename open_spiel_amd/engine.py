@@ -753,3 +753,95 @@ class XFPSolver(TabularSolver):
         t = self.tables()
         return {k: [(int(t["legal"][i, a]), float(t["cur_policy"][i, a])) for a in range(t["nact"][i])]
                 for i, k in enumerate(t["keys"])}
+
+
+class MMDSolver(TabularSolver):
+    """mmd_dilated.MMDDilatedEnt(game, alpha, stepsize) on the device: magnetic mirror descent over the sequence form with
+    dilated entropy (Sokota et al. 2023).  With alpha > 0 the LAST iterate converges linearly to the alpha-reduced
+    normal-form QRE; with alpha = 0 it is mirror descent-ascent and the average converges to a Nash equilibrium.  The
+    policy lives in the current-policy table, the average sequences in the cumulative-policy table (osg_mmd_set_params in
+    include/osg_abi.h; csrc/osg_mmd.h has the arithmetic).
+    alpha, stepsize: scalars or one value per replica (a sweep: replica r runs with its own pair); stepsize None is the
+    reference's default alpha / max|payoff|**2.  general_kernel=True forces the launch-per-level form (one replica)."""
+
+    def __init__(self, ctx, game_string, alpha, stepsize=None, replicas=1, general_kernel=False):
+        super().__init__(ctx, game_string, alternating_updates=True, linear_averaging=False, regret_matching_plus=False,
+                         general_kernel=general_kernel, replicas=replicas)
+        self.set_params(alpha, stepsize)
+
+    def _per_replica(self, value, what):
+        v = np.atleast_1d(np.asarray(value, np.float64))
+        if v.shape == (1,):
+            v = np.repeat(v, self.replicas)
+        if v.ndim != 1:
+            raise OsgError(f"MMDSolver: {what} must be a scalar or a sequence")
+        return np.ascontiguousarray(v)
+
+    def default_stepsize(self, alpha):
+        out = C.c_double(0)
+        check(lib().osg_mmd_default_stepsize(self._h, C.c_double(float(alpha)), C.byref(out)))
+        return out.value
+
+    def set_params(self, alpha, stepsize=None):
+        """The parameters of the update_sequences() calls that follow; the state is kept (annealing)."""
+        a = self._per_replica(alpha, "alpha")
+        if stepsize is None:
+            e = np.array([self.default_stepsize(v) for v in a], np.float64)
+        else:
+            e = self._per_replica(stepsize, "stepsize")
+        if e.size != a.size:
+            raise OsgError("MMDSolver: alpha and stepsize differ in length")
+        check(lib().osg_mmd_set_params(self._h, int(a.size), a.ctypes.data, e.ctypes.data))
+        self.alpha, self.stepsize = a.copy(), e.copy()
+
+    def iterate(self, iters=1):
+        check(lib().osg_mmd_iterate(self._h, int(iters)))
+
+    def update_sequences(self):
+        """MMDDilatedEnt.update_sequences() (mmd_dilated.py:261-281)."""
+        self.iterate(1)
+
+    def get_gap(self):
+        """MMDDilatedEnt.get_gap() of the selected replica: the saddle-point gap of the regularised game (alpha > 0)."""
+        out = C.c_double(0)
+        check(lib().osg_mmd_gap(self._h, C.byref(out)))
+        return out.value
+
+    def _sequences(self, which):
+        x = np.zeros((self.num_infostates, self.amax), np.float64)
+        check(lib().osg_mmd_sequences(self._h, which, x.ctypes.data))
+        return x
+
+    def current_sequences(self):
+        """[I, Amax]: the sequence value of every (infostate, action) under the current policy."""
+        return self._sequences(0)
+
+    def get_avg_sequences(self):
+        return self._sequences(1)
+
+    def _policy_dict(self, name):
+        t = self.tables()
+        return {k: [(int(t["legal"][i, a]), float(t[name][i, a])) for a in range(t["nact"][i])]
+                for i, k in enumerate(t["keys"])}
+
+    def get_policies(self):
+        """get_policies(): the current behavioural policy, {infostate string: [(action, probability)]}."""
+        return self._policy_dict("cur_policy")
+
+    def get_avg_policies(self):
+        """get_avg_policies(): the average sequences row-normalised (sequence_form_utils.py:284-322)."""
+        return self._policy_dict("avg_policy")
+
+    def evaluate_and_update_policy(self, iters=1):
+        raise OsgError("MMDSolver: iterate() / update_sequences() advance mirror descent; a CFR iteration would overwrite its tables")
+
+    evaluate_and_update_policy_cfr_br = evaluate_and_update_policy
+
+    def evaluate_policy(self, which="current", table=None):
+        return super().evaluate_policy(which, table)
+
+    def nash_conv(self):
+        return self.evaluate_policy("current")["nash_conv"]
+
+    def exploitability(self):
+        return self.evaluate_policy("current")["exploitability"]
