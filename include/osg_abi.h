@@ -629,6 +629,41 @@ int osg_cfr_best_response(osg_cfr* s, int which_policy, const double* h_policy, 
  * when it best-responds from there on and the others follow the policy (choices as for osg_cfr_evaluate_policy). */
 int osg_cfr_best_response_history_values(osg_cfr* s, int which_policy, const double* h_policy, int responder,
                                          double* h_history_values);
+/* Per-infostate action values and reaches of a policy profile: TreeWalkCalculator (open_spiel/python/algorithms/
+ * action_value.py:87-216) and, with a best responder, Calculator (action_value_vs_best_response.py:63-156).  Every
+ * player plays the policy which_policy selects (as for osg_cfr_evaluate_policy; 2: the [I, Amax] table `policy`), except
+ * `responder` (-1: nobody; two-player games only, action_value_vs_best_response.py:67), who plays the deterministic
+ * TabularBestResponse to it exactly as osg_cfr_best_response picks it.  For a member history h of infostate i (player
+ * p): r_q(h) the product of player q's probabilities on the root path, c(h) chance's, reach(h) = r_0 * ... * c,
+ * opp(h) = prod_{q != p} r_q, v(h) the profile's expected returns below h.  Summed over an infostate's member histories
+ * in the reference's visiting order:
+ *   reach = sum reach(h) (info_state_prob), cf_reach = sum c(h) * opp(h) (counterfactual_reach_probs), chance_reach =
+ *   sum c(h) (info_state_chance_prob), player_reach = r_p(h) of a member (player_reach_probs),
+ *   weighted_values[i, a, q] = sum v_q(child(h, a)) * reach(h) (weighted_action_values, :148),
+ *   action_values[i, a] = weighted_values[i, a, p] / reach[i] where reach[i] > 0, else 0 (:202-204),
+ *   cf_reach_by_value[i, a] = sum (v_p(child(h, a)) * opp(h)) * c(h) (sum_cfr_reach_by_action_value, :149-151),
+ *   root_values = v(root) (root_node_values); best_response_value = the responder's best-response value (Calculator's
+ *   `exploitability`), best_index its choice at its rows (an index among the row's legal actions), -1 elsewhere.
+ * Rows in the solver's infostate order, columns the row's legal actions ascending, padding cells 0.  on_host = 1:
+ * `policy` and the outputs are host memory and the call returns when they have arrived; on_host = 0: they are device
+ * memory and everything is enqueued on the context's stream (but for the best-response evaluation of a responder, which
+ * waits as osg_cfr_best_response does).  A refused call writes nothing.  The sums have one fixed order (no atomics):
+ * two calls give the same bits, in either kernel form (osg_cfr_cfg.kernel = 2 forces the launch-per-level form;
+ * osg_cfr_last_eval_kernel names the one taken). */
+typedef struct {
+  double* root_values;         /* [P] */
+  double* action_values;       /* [I, Amax] */
+  double* cf_reach;            /* [I] */
+  double* player_reach;        /* [I] */
+  double* reach;               /* [I] */
+  double* chance_reach;        /* [I] */
+  double* cf_reach_by_value;   /* [I, Amax] */
+  double* weighted_values;     /* [I, Amax, P] */
+  double* best_response_value; /* [1], responder >= 0 only */
+  int32_t* best_index;         /* [I], responder >= 0 only */
+} osg_action_values_out;       /* any member may be NULL */
+int osg_cfr_action_values(osg_cfr* s, int which_policy, const double* policy, int responder, int on_host,
+                          const osg_action_values_out* out);
 /* The flattened tree's edges: parent [H] (-1 at the root) and the action / chance outcome on the edge from the
  * parent [H] (-1 at the root); histories are numbered level by level.  Either may be NULL. */
 int osg_cfr_tree_edges(const osg_cfr* s, int32_t* parent, int32_t* action);

@@ -79,6 +79,12 @@ class CfrCfg(C.Structure):
     ]
 
 
+class ActionValuesOut(C.Structure):   # osg_action_values_out: host or device addresses, any may be None
+    _fields_ = [(name, C.c_void_p) for name in (
+        "root_values", "action_values", "cf_reach", "player_reach", "reach", "chance_reach", "cf_reach_by_value",
+        "weighted_values", "best_response_value", "best_index")]
+
+
 VP = C.c_void_p
 I64 = C.c_int64
 U64 = C.c_uint64
@@ -170,6 +176,7 @@ SIGNATURES = {
     "osg_cfr_evaluate_policy": (INT, [VP, INT, VP, VP, VP, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "osg_cfr_infostate_player": (INT, [VP, I64]),
     "osg_cfr_best_response": (INT, [VP, INT, VP, VP, VP]),
+    "osg_cfr_action_values": (INT, [VP, INT, VP, INT, INT, C.POINTER(ActionValuesOut)]),
     "osg_cfr_infostate_key": (INT, [VP, I64, C.c_char_p, INT]),
     "osg_cfr_best_response_history_values": (INT, [VP, INT, VP, INT, VP]),
     "osg_cfr_tree_edges": (INT, [VP, VP, VP]),

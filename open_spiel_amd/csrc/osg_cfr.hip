@@ -485,7 +485,7 @@ int osg_cfr_destroy(osg_cfr* s) {
                   s->d_sub_info_off, s->d_sub_info_list, s->d_sub_bar, s->d_sub_ndec, s->d_sub_dec_row, s->d_sub_rec,
                   s->d_sub_stamps, s->d_mccfr_stamps, s->d_sub_recbuf, s->d_sub_chance_prob, s->d_sub_term_val, s->d_sub_dec_off, s->d_sub_fold_info, s->d_sub_fold_off, s->d_sub_nroot, s->d_sub_root_loc, s->d_sub_root_idx, s->d_sub_upper_rec, s->d_sub_root_value,
                   s->d_jobs_job, s->d_jobs_level, s->d_jobs_desc, s->d_jobs_fc, s->d_jobs_row, s->d_jobs_glob, s->d_jobs_info,
-                  s->d_jobs_mem, s->d_jobs_deal, s->d_jobs_ticket, s->d_disc};
+                  s->d_jobs_mem, s->d_jobs_deal, s->d_jobs_ticket, s->d_disc, s->d_qv_out, s->d_qv_best};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   mmd_destroy(s);

@@ -5,6 +5,7 @@
 //   osg_cfr_split.hip   k_cfr_split                   one workgroup per deal subtree (leduc_poker)
 //   osg_cfr_sub.hip     k_cfr_sub, k_gcfr_*           one persistent cooperative launch / a launch per phase (3-player leduc)
 //   osg_cfr_eval.hip    k_policy_eval, k_geval_*, k_eval_jobs     ExpectedReturns / TabularBestResponse / NashConv
+//   osg_cfr_qvalues.hip k_qvalues_small, k_qv_*       per-infostate action values and reaches of a policy
 //   osg_cfr_mccfr.hip   k_mccfr*, k_os_mccfr*, ...    external / outcome sampling MCCFR and their entry points
 //
 // Every kernel is launched from the translation unit that defines it; what crosses the units are the device-side
@@ -486,6 +487,9 @@ struct osg_cfr {
   int n_uret = 0, n_uprob = 0, num_cus = 0;
   uint64_t* d_rec = nullptr;
   double *d_uret = nullptr, *d_uprob = nullptr;
+  // per-infostate action values (osg_cfr_qvalues.hip): the results of a call, allocated at the first one
+  double* d_qv_out = nullptr;
+  int32_t* d_qv_best = nullptr;
   // magnetic mirror descent (osg_cfr_mmd.hip): built at the first osg_mmd_* call
   MmdState* mmd = nullptr;
 

@@ -651,6 +651,82 @@ class TabularSolver:
     def exploitability(self):
         return self.evaluate_policy()["exploitability"]
 
+    def action_values(self, which="average", table=None, responder=None, device=False, layout="legal"):
+        """Per-infostate action values and reaches of a policy on the device (action_value.TreeWalkCalculator; with
+        `responder`, the profile of action_value_vs_best_response.Calculator: that player best-responds, two-player
+        games only).  which / table as for evaluate_policy.  Returns a dict: root_values [P], action_values and
+        cf_reach_by_value [I, Amax], weighted_values [I, Amax, P], reach, cf_reach, chance_reach, player_reach [I], and
+        with a responder best_response_value and best_index [I] (-1 at the other players' rows): osg_cfr_action_values
+        in include/osg_abi.h has the definitions.  device=False: numpy arrays.  device=True: torch fp64 tensors on
+        the context's device, enqueued on its stream with no host round trip, and `table` may be a device tensor.
+        layout "legal": columns are the row's legal actions ascending; "action_id": action_values and
+        cf_reach_by_value are [I, num_distinct_actions] indexed by action id, zeros at illegal ids (the reference's
+        shape)."""
+        code = {"average": 0, "current": 1, "table": 2}[which]
+        if layout not in ("legal", "action_id"):
+            raise OsgError(f"action_values: layout must be 'legal' or 'action_id', not {layout!r}")
+        I, A = self.num_infostates, self.amax
+        P = _abi.describe(self.game_string).num_players
+        b = -1 if responder is None else int(responder)
+        shapes = dict(root_values=(P,), action_values=(I, A), cf_reach=(I,), player_reach=(I,), reach=(I,),
+                      chance_reach=(I,), cf_reach_by_value=(I, A), weighted_values=(I, A, P))
+        if b >= 0:
+            shapes.update(best_response_value=(1,), best_index=(I,))
+        tab = None
+        if code == 2:
+            if device:
+                tab = torch.as_tensor(table, dtype=torch.float64, device=self.ctx.device).contiguous()
+            else:
+                tab = np.ascontiguousarray(table, np.float64)
+            if tuple(tab.shape) != (I, A):
+                raise OsgError(f"action_values: expected a table of shape {(I, A)}")
+        if device:
+            res = {k: torch.zeros(shape, dtype=torch.int32 if k == "best_index" else torch.float64, device=self.ctx.device)
+                   for k, shape in shapes.items()}
+            addr = lambda t: t.data_ptr()
+        else:
+            res = {k: np.zeros(shape, np.int32 if k == "best_index" else np.float64) for k, shape in shapes.items()}
+            addr = lambda a: a.ctypes.data
+        out = _abi.ActionValuesOut(**{k: addr(v) for k, v in res.items()})
+        check(lib().osg_cfr_action_values(self._h, code, None if tab is None else addr(tab), b, 0 if device else 1,
+                                          C.byref(out)))
+        if b >= 0:
+            res["best_response_value"] = res["best_response_value"][0] if device else float(res["best_response_value"][0])
+        if layout == "action_id":
+            n_ids = _abi.describe(self.game_string).num_distinct_actions
+            nact, legal = np.zeros(I, np.int32), np.zeros((I, A), np.int32)
+            check(lib().osg_cfr_tables(self._h, nact.ctypes.data, legal.ctypes.data, None, None, None, None))
+            rows, cols = np.nonzero(np.arange(A)[None, :] < nact[:, None])
+            ids = legal[rows, cols]
+            for k in ("action_values", "cf_reach_by_value"):
+                if device:
+                    wide = torch.zeros((I, n_ids), dtype=torch.float64, device=self.ctx.device)
+                    r, c, d = (torch.as_tensor(x, device=self.ctx.device, dtype=torch.int64) for x in (rows, cols, ids))
+                    wide[r, d] = res[k][r, c]
+                else:
+                    wide = np.zeros((I, n_ids))
+                    wide[rows, ids] = res[k][rows, cols]
+                res[k] = wide
+        return res
+
+    def action_values_vs_best_response(self, player, which="average", table=None):
+        """action_value_vs_best_response.Calculator(game)(player, policy, info_states) for `player`'s information
+        states in this solver's order: `player` plays the policy, the opponent best-responds.  Returns a dict:
+        exploitability (the best responder's value), values_vs_br [n, num_distinct_actions] (indexed by action id,
+        zeros at illegal ids), counterfactual_reach_probs_vs_br [n], player_reach_probs_vs_br [n], and rows [n], the
+        solver's infostate indices of `player`'s rows."""
+        player = int(player)
+        P = _abi.describe(self.game_string).num_players
+        if P != 2:   # action_value_vs_best_response.py:67
+            raise OsgError(f"action_values_vs_best_response: only supports 2-player games ({P} players)")
+        if player not in (0, 1):
+            raise OsgError(f"action_values_vs_best_response: no player {player}")
+        res = self.action_values(which, table, responder=1 - player, layout="action_id")
+        rows = np.nonzero(res["best_index"] < 0)[0]
+        return dict(exploitability=res["best_response_value"], values_vs_br=res["action_values"][rows],
+                    counterfactual_reach_probs_vs_br=res["cf_reach"][rows], player_reach_probs_vs_br=res["player_reach"][rows],
+                    rows=rows)
+
     def average_policy(self):
         t = self.tables()
         return {k: [(int(t["legal"][i, a]), float(t["avg_policy"][i, a])) for a in range(t["nact"][i])]

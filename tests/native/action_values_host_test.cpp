@@ -1,0 +1,185 @@
+// The per-infostate action values and reaches as the kernels compute them (open_spiel_amd/csrc/osg_action_values.h,
+// host + device) driven on the CPU over every case of tests/golden/action_value_vectors.npz: what the reference's own
+// action_value.py and action_value_vs_best_response.py computed.  Built by tests/test_action_values_native.py with
+// hipcc --cuda-host-only -ffp-contract=off, like the library.
+//
+//   action_values_host_test <cases.bin> <tolerance> [<tables.bin>]
+//
+// cases.bin is written by tests/action_value_cases.py write_cases().  Per case the program forms sigma, every member's
+// reach products, the values bottom-up and every infostate's sums twice: by qv_infostate (one thread per infostate, the
+// resident kernel's order) and 64 members at a time with the terms added in member order (the wavefront kernel's order);
+// the two must agree bit for bit, and both with the recorded outputs within the tolerance.  It prints the largest
+// deviation per array and, with a third argument, leaves its tables there.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "osg_action_values.h"
+
+using namespace osg;
+
+namespace {
+
+struct Reader {
+  FILE* f;
+  template <class T>
+  std::vector<T> take(size_t n) {
+    std::vector<T> v(n);
+    if (n && fread(v.data(), sizeof(T), n, f) != n) { fprintf(stderr, "short read\n"); exit(2); }
+    return v;
+  }
+};
+
+struct Tables {
+  std::vector<double> reach, cf_reach, chance_reach, player_reach, q, cf_q, weighted;
+  Tables(int I, int A, int P)
+      : reach(I), cf_reach(I), chance_reach(I), player_reach(I), q(static_cast<size_t>(I) * A), cf_q(static_cast<size_t>(I) * A),
+        weighted(static_cast<size_t>(I) * A * P) {}
+  QvTables view() { return QvTables{reach.data(), cf_reach.data(), chance_reach.data(), player_reach.data(), q.data(), cf_q.data(), weighted.data()}; }
+  std::vector<const std::vector<double>*> all() const { return {&reach, &cf_reach, &chance_reach, &player_reach, &q, &cf_q, &weighted}; }
+};
+
+// The wavefront kernel's order: 64 members at a time, every lane its member's term, the terms added in member order.
+void infostate_by_chunks(int i, int p, int n, int A, int P, int m0, int m1, const int32_t* mem, const int32_t* first_child,
+                         const double* rm, const double* value, const QvTables& o) {
+  const int cnt = m1 - m0;
+  double reach = 0.0, cf = 0.0, chance = 0.0;
+  std::vector<double> w(static_cast<size_t>(A) * P, 0.0), cfq(A, 0.0);
+  for (int c0 = 0; c0 < cnt; c0 += 64) {
+    const int here = cnt - c0 < 64 ? cnt - c0 : 64;
+    QvMember lane[64];
+    for (int j = 0; j < here; ++j) lane[j] = qv_member(rm + static_cast<size_t>(m0 + c0 + j) * (P + 1), P, p);
+    for (int j = 0; j < here; ++j) cf += qv_cf_reach_term(lane[j]);
+    for (int j = 0; j < here; ++j) reach += lane[j].reach;
+    for (int j = 0; j < here; ++j) chance += lane[j].chance;
+    for (int a = 0; a < n; ++a)
+      for (int q = 0; q < P; ++q) {
+        double term[64], cterm[64];
+        for (int j = 0; j < here; ++j) {
+          const double v = value[static_cast<size_t>(first_child[mem[m0 + c0 + j]] + a) * P + q];
+          term[j] = qv_weighted_term(v, lane[j]);
+          cterm[j] = qv_cf_value_term(v, lane[j]);
+        }
+        for (int j = 0; j < here; ++j) w[static_cast<size_t>(a) * P + q] += term[j];
+        if (q == p)
+          for (int j = 0; j < here; ++j) cfq[a] += cterm[j];
+      }
+  }
+  o.reach[i] = reach; o.cf_reach[i] = cf; o.chance_reach[i] = chance;
+  o.player_reach[i] = cnt > 0 ? rm[static_cast<size_t>(m0) * (P + 1) + p] : 0.0;
+  for (int a = 0; a < A; ++a) {
+    for (int q = 0; q < P; ++q) o.weighted[(static_cast<size_t>(i) * A + a) * P + q] = w[static_cast<size_t>(a) * P + q];
+    o.q[static_cast<size_t>(i) * A + a] = a < n ? qv_action_value(w[static_cast<size_t>(a) * P + p], reach) : 0.0;
+    o.cf_q[static_cast<size_t>(i) * A + a] = cfq[a];
+  }
+}
+
+double deviation(const std::vector<double>& got, const std::vector<double>& want) {
+  double d = 0.0;
+  for (size_t k = 0; k < got.size(); ++k) {
+    const double e = std::fabs(got[k] - want[k]);
+    if (!(e <= d)) d = e;   // (a NaN sticks)
+  }
+  return d;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc < 3) { fprintf(stderr, "usage: %s cases.bin tolerance [tables.bin]\n", argv[0]); return 2; }
+  Reader in{fopen(argv[1], "rb")};
+  if (!in.f) { perror(argv[1]); return 2; }
+  const double tol = atof(argv[2]);
+  FILE* dump = argc > 3 ? fopen(argv[3], "wb") : nullptr;
+  const std::vector<int32_t> hdr = in.take<int32_t>(6);
+  const int H = hdr[0], I = hdr[1], A = hdr[2], P = hdr[3], M = hdr[4], C = hdr[5];
+  const std::vector<int32_t> parent = in.take<int32_t>(H), kind = in.take<int32_t>(H), actor = in.take<int32_t>(H),
+                             info = in.take<int32_t>(H), nact = in.take<int32_t>(I), player = in.take<int32_t>(I),
+                             mem_off = in.take<int32_t>(I + 1), mem = in.take<int32_t>(M);
+  const std::vector<double> edge_prob = in.take<double>(H), term_ret = in.take<double>(static_cast<size_t>(H) * P);
+  // the links and root paths the solver keeps (osg_cfr.hip build_tree)
+  std::vector<int32_t> first_child(H, 0), nchild(H, 0);
+  for (int h = H - 1; h > 0; --h) { first_child[parent[h]] = h; ++nchild[parent[h]]; }
+  std::vector<int32_t> path_off{0}, path;
+  for (int m = 0; m < M; ++m) {
+    std::vector<int32_t> rev;
+    for (int32_t v = mem[m]; parent[v] >= 0; v = parent[v]) {
+      const int32_t par = parent[v];
+      const bool chance = kind[par] == 0;
+      const int slot = chance ? P : actor[par];
+      const int32_t idx = chance ? v : info[par] * A + (v - first_child[par]);
+      rev.push_back((slot << 24) | ((chance ? 1 : 0) << 23) | idx);
+    }
+    path.insert(path.end(), rev.rbegin(), rev.rend());
+    path_off.push_back(static_cast<int32_t>(path.size()));
+  }
+  const char* names[] = {"reach", "cf_reach", "chance_reach", "player_reach", "action_values", "cf_reach_by_value", "weighted_values"};
+  bool failed = false;
+  for (int c = 0; c < C; ++c) {
+    const std::vector<int32_t> head = in.take<int32_t>(2);
+    const int responder = head[0];
+    const double want_brv = in.take<double>(1)[0];
+    const std::vector<double> policy = in.take<double>(static_cast<size_t>(I) * A);
+    const std::vector<int32_t> best = in.take<int32_t>(I);
+    const std::vector<double> want_root = in.take<double>(P);
+    Tables want(I, A, P);
+    want.reach = in.take<double>(I); want.cf_reach = in.take<double>(I); want.chance_reach = in.take<double>(I);
+    want.player_reach = in.take<double>(I); want.q = in.take<double>(static_cast<size_t>(I) * A);
+    want.cf_q = in.take<double>(static_cast<size_t>(I) * A); want.weighted = in.take<double>(static_cast<size_t>(I) * A * P);
+    // sigma
+    std::vector<double> sigma(static_cast<size_t>(I) * A);
+    for (int i = 0; i < I; ++i)
+      qv_sigma_row(&policy[static_cast<size_t>(i) * A], &sigma[static_cast<size_t>(i) * A], nact[i], A, 1,
+                   responder >= 0 && player[i] == responder ? best[i] : -1);
+    // reach products of every member
+    std::vector<double> rm(static_cast<size_t>(M) * (P + 1));
+    for (int m = 0; m < M; ++m)
+      qv_member_reach(path.data(), path_off[m], path_off[m + 1], P, sigma.data(), edge_prob.data(), &rm[static_cast<size_t>(m) * (P + 1)]);
+    // values, deepest first (a child's index is above its parent's)
+    std::vector<double> value(static_cast<size_t>(H) * P);
+    for (int h = H - 1; h >= 0; --h)
+      for (int q = 0; q < P; ++q) {
+        if (kind[h] == 2) { value[static_cast<size_t>(h) * P + q] = term_ret[static_cast<size_t>(h) * P + q]; continue; }
+        const double* prob = kind[h] == 0 ? &edge_prob[first_child[h]] : &sigma[static_cast<size_t>(info[h]) * A];
+        value[static_cast<size_t>(h) * P + q] = qv_node_value(prob, value.data(), first_child[h], nchild[h], P, q);
+      }
+    Tables got(I, A, P), chunked(I, A, P);
+    for (int i = 0; i < I; ++i) {
+      qv_infostate(i, player[i], nact[i], A, P, mem_off[i], mem_off[i + 1], mem.data(), first_child.data(), rm.data(), value.data(), got.view());
+      infostate_by_chunks(i, player[i], nact[i], A, P, mem_off[i], mem_off[i + 1], mem.data(), first_child.data(), rm.data(), value.data(), chunked.view());
+    }
+    bool same = true;
+    for (size_t k = 0; k < got.all().size(); ++k)
+      same = same && std::memcmp(got.all()[k]->data(), chunked.all()[k]->data(), sizeof(double) * got.all()[k]->size()) == 0;
+    double worst = 0.0;
+    const std::vector<double> root(value.begin(), value.begin() + P);
+    double d = deviation(root, want_root);
+    printf("case %d responder %d largest deviation: root_values %.3g", c, responder, d);
+    worst = d;
+    for (size_t k = 0; k < got.all().size(); ++k) {
+      d = deviation(*got.all()[k], *want.all()[k]);
+      printf(" %s %.3g", names[k], d);
+      if (!(d <= worst)) worst = d;
+    }
+    if (responder >= 0) {
+      d = std::fabs(root[responder] - want_brv);
+      printf(" best_response_value %.3g", d);
+      if (!(d <= worst)) worst = d;
+    }
+    printf("; the two orders %s\n", same ? "agree bit for bit" : "DIFFER");
+    if (!(worst <= tol) || !same) { printf("case %d FAILED\n", c); failed = true; }
+    if (dump) {
+      fwrite(root.data(), sizeof(double), root.size(), dump);
+      for (const std::vector<double>* t : got.all()) fwrite(t->data(), sizeof(double), t->size(), dump);
+    }
+  }
+  if (dump) fclose(dump);
+  fclose(in.f);
+  if (failed) return 1;
+  printf("ok: %d cases\n", C);
+  return 0;
+}
