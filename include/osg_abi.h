@@ -347,6 +347,43 @@ typedef struct {
 int osg_alpha_beta_search(const osg_batch* roots, const osg_ab_cfg* cfg, double* value, int32_t* best_action,
                           int64_t* nodes, uint8_t* status, int on_host);
 
+/* ---- every reachable position and its game-theoretic value ------------------------------------------------
+ * algorithms::GetAllStates (open_spiel/algorithms/get_all_states.h:38-43, get_all_states.cc:28-91;
+ * python/algorithms/get_all_states.py:88-142) and algorithms::ValueIteration (open_spiel/algorithms/
+ * value_iteration.h:41-42, value_iteration.cc:84-138; python/algorithms/value_iteration.py:73-159) for tic_tac_toe,
+ * connect_four (every geometry) and hex without the swap move on boards of up to 64 cells, enumerated level by level
+ * (a level = the positions after that many plies) and solved by one backward sweep.  Other games, hex(swap=true),
+ * hex(string_rep=explicit) and larger hex boards: OSG_ERR_UNSUPPORTED with a message.
+ * Result order: by level, within a level ascending by the canonical key of the position (csrc/osg_solve.h), so the
+ * output is unique; position 0 is the initial state.  Arrays over the n positions:
+ *   value [n] f64           Returns()[0] at a terminal position, else the max (player 0 to move) / min (player 1) over
+ *                           the children; a child that the limits leave out counts 0 (value_iteration.cc:118)
+ *   mask [n * mask_words]   the legal actions whose child has the position's value (the layout of osg_legal_mask); zero
+ *                           at a terminal position
+ *   distance [n] i32        plies to the end under optimal play: 0 at a terminal position, else 1 + that of the child
+ *                           chosen among the optimal ones — the nearest end for a win of the mover, the farthest for a
+ *                           loss or a draw
+ *   edge_off [n + 1] i64, action [edges] i32, child [edges] i64
+ *                           the legal actions of position i, ascending, at edge_off[i] .. edge_off[i + 1], and the index
+ *                           of each child (-1 where the limits leave it out)
+ * osg_solve_create: depth_limit < 0 = none; depth_limit and include_terminals as in get_all_states.cc:36-48 (a terminal
+ * position is listed whatever its depth).  max_states <= 0 = 2^26; a game with more positions fails with
+ * OSG_ERR_UNSUPPORTED as soon as that is known, and the context stays usable.
+ * osg_solve_level_offsets writes levels + 1 host values.  osg_solve_states fills a batch of the same game and of n
+ * states with the positions in result order.  osg_solve_lookup: index [query n] i64, the position of each query state
+ * in the result or -1, by key and binary search in one launch. */
+typedef struct osg_solve osg_solve;
+int osg_solve_create(osg_ctx* ctx, const char* game_string, int32_t depth_limit, int32_t include_terminals,
+                     int64_t max_states, osg_solve** out);
+int osg_solve_destroy(osg_solve* s);
+int osg_solve_sizes(const osg_solve* s, int64_t* states, int32_t* levels, int64_t* edges, int64_t* terminals);
+int osg_solve_level_offsets(const osg_solve* s, int64_t* h_offsets);
+int osg_solve_states(const osg_solve* s, osg_batch* dst);
+int osg_solve_values(const osg_solve* s, double* value, int on_host);
+int osg_solve_optimal(const osg_solve* s, uint32_t* mask, int32_t* distance, int on_host);
+int osg_solve_edges(const osg_solve* s, int64_t* edge_off, int32_t* action, int64_t* child, int on_host);
+int osg_solve_lookup(const osg_solve* s, const osg_batch* query, int64_t* index, int on_host);
+
 /* ---- MCTS with the Evaluator outside the kernel (Evaluator interface mcts.h:83-92; the batched shape of
  * alpha_zero_torch/vpevaluator.{h,cc}) ------------------------------------------------------------------
  * Search trees for every root of a batch that persist between calls.  osg_mcts_tree_advance runs every

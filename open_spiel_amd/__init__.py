@@ -28,7 +28,7 @@ def __getattr__(name):
         return importlib.import_module(".pyspiel_hip", __name__)
     # torch-backed classes are imported lazily so that `import open_spiel_amd`
     # (and the ABI symbol check) works without touching torch.
-    if name in ("Context", "Game", "StateBatch", "TabularSolver", "DCFRSolver", "LCFRSolver", "XFPSolver", "MMDSolver"):
+    if name in ("Context", "Game", "StateBatch", "SolvedGame", "TabularSolver", "DCFRSolver", "LCFRSolver", "XFPSolver", "MMDSolver"):
         from . import engine
         return getattr(engine, name)
     if name in ("BatchedEnvironment", "TimeStep", "StepType", "ObservationType"):

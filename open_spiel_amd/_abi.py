@@ -129,6 +129,15 @@ SIGNATURES = {
     "osg_rollout": (INT, [VP, U64, I64, INT, VP, VP, INT]),
     "osg_mcts_search": (INT, [VP, C.POINTER(MctsCfg), VP, VP, VP, VP, VP, INT]),
     "osg_alpha_beta_search": (INT, [VP, C.POINTER(AbCfg), VP, VP, VP, VP, INT]),
+    "osg_solve_create": (INT, [VP, C.c_char_p, C.c_int32, C.c_int32, I64, C.POINTER(VP)]),
+    "osg_solve_destroy": (INT, [VP]),
+    "osg_solve_sizes": (INT, [VP, C.POINTER(I64), C.POINTER(C.c_int32), C.POINTER(I64), C.POINTER(I64)]),
+    "osg_solve_level_offsets": (INT, [VP, VP]),
+    "osg_solve_states": (INT, [VP, VP]),
+    "osg_solve_values": (INT, [VP, VP, INT]),
+    "osg_solve_optimal": (INT, [VP, VP, VP, INT]),
+    "osg_solve_edges": (INT, [VP, VP, VP, VP, INT]),
+    "osg_solve_lookup": (INT, [VP, VP, VP, INT]),
     "osg_mcts_tree_create": (INT, [VP, C.POINTER(MctsCfg), INT, C.POINTER(VP)]),
     "osg_mcts_tree_destroy": (INT, [VP]),
     "osg_mcts_tree_advance": (INT, [VP, VP, VP, VP, VP, INT, C.POINTER(I64)]),

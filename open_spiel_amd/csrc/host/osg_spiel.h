@@ -2990,6 +2990,41 @@ inline std::pair<double, Action> AlphaBetaSearch(const Game& game, const State* 
   return {value, best_action < 0 ? kInvalidAction : static_cast<Action>(best_action)};
 }
 
+// algorithms/value_iteration.h:41-42, value_iteration.cc:84-138: the value of every state reachable within depth_limit
+// (negative: no limit), keyed by ToString(), with the reference's game-type checks (value_iteration.cc:88-98).  ONE
+// device enumeration and backward sweep (osg_solve_create: tic_tac_toe, connect_four, hex without the swap move; other
+// games are a fatal error with the library's message) instead of sweeps until the change falls below `threshold`: the
+// games' values are exactly -1 / 0 / +1 and the positions form levels, so the sweep's result IS the fixed point and
+// `threshold` has nothing left to bound.  The extra trailing parameter caps the number of states (0: 2^26).
+inline std::map<std::string, double> ValueIteration(const Game& game, int depth_limit, double threshold, int64_t max_states = 0) {
+  (void)threshold;
+  if (game.NumPlayers() != 1 && game.NumPlayers() != 2) SpielFatalError("ValueIteration: game.NumPlayers() == 1 || game.NumPlayers() == 2");
+  const GameType game_info = game.GetType();
+  if (game.NumPlayers() == 2 && game_info.utility != GameType::Utility::kZeroSum) SpielFatalError("ValueIteration: the game must be zero-sum");
+  if (game_info.dynamics != GameType::Dynamics::kSequential) SpielFatalError("ValueIteration: the game must be sequential");
+  if (game_info.information != GameType::Information::kPerfectInformation)
+    SpielFatalError("ValueIteration: the game must have perfect information");
+  osg_solve* solved = nullptr;
+  Check(osg_solve_create(game.Ctx(), game.GameString().c_str(), depth_limit, /*include_terminals=*/1, max_states, &solved));
+  int64_t n = 0;
+  osg_batch* states = nullptr;
+  std::vector<double> value;
+  int rc = osg_solve_sizes(solved, &n, nullptr, nullptr, nullptr);
+  if (!rc) rc = osg_batch_create(game.Ctx(), game.GameString().c_str(), n, &states);
+  if (!rc) rc = osg_solve_states(solved, states);
+  if (!rc) { value.resize(n); rc = osg_solve_values(solved, value.data(), 1); }
+  std::map<std::string, double> values;
+  char text[1024];
+  for (int64_t i = 0; !rc && i < n; ++i) {
+    const int len = osg_state_string(states, i, text, sizeof text);
+    if (len < 0) rc = len; else values[text] = value[i];
+  }
+  osg_batch_destroy(states);
+  osg_solve_destroy(solved);
+  Check(rc);
+  return values;
+}
+
 enum class AverageType { kSimple, kFull };
 
 // The MCCFR solvers' text checkpoints (external_sampling_mccfr.cc:82-120,233-288;

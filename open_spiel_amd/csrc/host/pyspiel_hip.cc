@@ -774,6 +774,20 @@ PYBIND11_MODULE(pyspiel_hip, m) {
   m.def("expected_returns", [](std::shared_ptr<Game> g, const Policy& p) { return ExpectedReturns(*g, p); },
         py::arg("game"), py::arg("policy"));
 
+  // algorithms.value_iteration.value_iteration / algorithms.get_all_states.get_all_states under the reference's names
+  // (python/algorithms/value_iteration.py:73, get_all_states.py:88; value_iteration.h:41, get_all_states.h:38)
+  m.def("value_iteration", [](std::shared_ptr<Game> g, int depth_limit, double threshold) { return ValueIteration(*g, depth_limit, threshold); },
+        py::arg("game"), py::arg("depth_limit") = -1, py::arg("threshold") = 0.01);
+  m.def("get_all_states",
+        [](std::shared_ptr<Game> g, int depth_limit, bool include_terminals, bool include_chance_states, bool stop_if_encountered) {
+          py::dict out;
+          for (auto& kv : GetAllStates(*g, depth_limit, include_terminals, include_chance_states, stop_if_encountered))
+            out[py::str(kv.first)] = py::cast(std::move(kv.second));
+          return out;
+        },
+        py::arg("game"), py::arg("depth_limit") = -1, py::arg("include_terminals") = true, py::arg("include_chance_states") = false,
+        py::arg("stop_if_encountered") = true);
+
   // pyspiel.kuhn_poker.get_optimal_policy (python/pybind11/games_kuhn_poker.cc:23-24)
   py::module_ kuhn = m.def_submodule("kuhn_poker");
   kuhn.def("get_optimal_policy", [](double alpha) { return std::make_shared<TabularPolicy>(kuhn_poker::GetOptimalPolicy(alpha)); },

@@ -143,6 +143,12 @@ class Game:
     def new_initial_states(self, ctx, n):
         return StateBatch(ctx, self.game_string, n)
 
+    def solve(self, ctx, depth_limit=-1, include_terminals=True, max_states=1 << 26):
+        """Every reachable position and its game-theoretic value (algorithms.get_all_states + value_iteration) for
+        tic_tac_toe, connect_four and hex without the swap move: a SolvedGame.  depth_limit / include_terminals as
+        get_all_states; a game with more than max_states positions raises OsgError."""
+        return SolvedGame(ctx, self.game_string, depth_limit, include_terminals, max_states)
+
 
 class StateBatch:
     """N states of one game in HBM (all start at Game::NewInitialState())."""
@@ -454,6 +460,76 @@ class StateBatch:
         check(lib().osg_alpha_beta_search(self._h, C.byref(cfg), _ptr(value), _ptr(best), _ptr(nodes), _ptr(status),
                                           1 if on_host else 0))
         return value, best, nodes, status
+
+
+class SolvedGame:
+    """The positions of a game level by level (a level = the positions after that many plies), within a level
+    ascending by the canonical key, and what the backward pass found at each (osg_solve_* of include/osg_abi.h).
+
+    states         StateBatch of the n positions in result order (position 0 is the initial state)
+    values         [n] f64: the value for player 0 (value_iteration's dict, by position)
+    optimal_mask   [n, mask_words] i32 bit-packed: the legal actions whose child has the position's value
+    distance       [n] i32: plies to the end under optimal play (a win as fast, a loss or draw as slow as possible)
+    level_offsets  [levels + 1] i64;  num_terminals
+    edge_off [n + 1] i64, edge_action [edges] i32, edge_child [edges] i64 (-1: a child the limits left out)
+    All tensors live on the context's device."""
+
+    def __init__(self, ctx, game_string, depth_limit=-1, include_terminals=True, max_states=1 << 26):
+        self.ctx = ctx
+        self.game_string = game_string
+        self._h = None
+        h = C.c_void_p()
+        check(lib().osg_solve_create(ctx._h, game_string.encode(), int(depth_limit), 1 if include_terminals else 0,
+                                     int(max_states), C.byref(h)))
+        self._h = h
+        n, levels, edges, terminals = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int64()
+        check(lib().osg_solve_sizes(h, C.byref(n), C.byref(levels), C.byref(edges), C.byref(terminals)))
+        self.n, self.num_levels, self.num_edges, self.num_terminals = n.value, levels.value, edges.value, terminals.value
+        dev = ctx.device
+        offs = np.empty(self.num_levels + 1, np.int64)
+        check(lib().osg_solve_level_offsets(h, offs.ctypes.data))
+        self.level_offsets = torch.from_numpy(offs).to(dev)
+        self.states = StateBatch(ctx, game_string, self.n)
+        check(lib().osg_solve_states(h, self.states._h))
+        words = self.states.desc.mask_words
+        self.values = torch.empty(self.n, dtype=torch.float64, device=dev)
+        self.optimal_mask = torch.empty((self.n, words), dtype=torch.int32, device=dev)
+        self.distance = torch.empty(self.n, dtype=torch.int32, device=dev)
+        self.edge_off = torch.empty(self.n + 1, dtype=torch.int64, device=dev)
+        self.edge_action = torch.empty(self.num_edges, dtype=torch.int32, device=dev)
+        self.edge_child = torch.empty(self.num_edges, dtype=torch.int64, device=dev)
+        check(lib().osg_solve_values(h, _ptr(self.values), 0))
+        check(lib().osg_solve_optimal(h, _ptr(self.optimal_mask), _ptr(self.distance), 0))
+        check(lib().osg_solve_edges(h, _ptr(self.edge_off), _ptr(self.edge_action), _ptr(self.edge_child), 0))
+        ctx.synchronize()
+
+    def __len__(self):
+        return self.n
+
+    def close(self):
+        if self._h:
+            lib().osg_solve_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def lookup(self, batch):
+        """[len(batch)] i64 on the device: the index of each state of `batch` in the result, -1 if it is not there."""
+        out = torch.empty(batch.n, dtype=torch.int64, device=self.ctx.device)
+        check(lib().osg_solve_lookup(self._h, batch._h, _ptr(out), 0))
+        return out
+
+    def state_strings(self):
+        """State::ToString() of every position, in result order (host; small games)."""
+        return [self.states.state_string(i) for i in range(self.n)]
+
+    def value_dict(self):
+        """value_iteration's {str(state): value} (host; small games)."""
+        return dict(zip(self.state_strings(), self.values.cpu().tolist()))
 
 
 class TabularSolver:
