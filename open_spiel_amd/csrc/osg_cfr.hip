@@ -326,7 +326,7 @@ namespace osg_cfr_impl {
 // tables mixed: the solver refuses further work.  The kernels raise a pinned host word, read here without a copy or a
 // wait — by every entry point that advances, reads or hands out the tables.
 int cfr_sub_error(const osg_cfr* s) {
-  if (s->h_sub_err && __atomic_load_n(s->h_sub_err, __ATOMIC_RELAXED) != 0)
+  if (s->h_sub_err && __atomic_load_n(s->h_sub_err.get(), __ATOMIC_RELAXED) != 0)
     return set_error(OSG_ERR_HIP, "a grid barrier of the subtree CFR kernel timed out in an earlier launch (the launch is "
                                   "cooperative: a hung device, not contention); the tables are not usable — "
                                   "osg_cfr_cfg.kernel = 3 runs one workgroup");
@@ -348,20 +348,15 @@ int cfr_discount_table(osg_cfr* s, int iteration0, int iters, const double** d_t
   if (!s->dcfr) return OSG_OK;
   const size_t n = 3 * static_cast<size_t>(iters);
   hipStream_t st = s->ctx->stream;
-  // (the stream may still be copying from h_disc or reading d_disc for the previous call)
-  if (n > s->disc_cap || n * sizeof(double) > (64u << 10)) OSG_HIP(hipStreamSynchronize(st));
-  if (n > s->disc_cap) {
-    if (s->d_disc) OSG_HIP(hipFree(s->d_disc));
-    s->d_disc = nullptr; s->disc_cap = 0;
-    OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_disc), sizeof(double) * n));
-    s->disc_cap = n;
-  }
-  s->h_disc.resize(n);
+  // (the stream may still be copying from h_iter_table or reading d_iter_table for the previous call)
+  if (n > s->d_iter_table.size() || n * sizeof(double) > (64u << 10)) OSG_HIP(hipStreamSynchronize(st));
+  OSG_HIP(s->d_iter_table.ensure(n));
+  s->h_iter_table.resize(n);
   for (int it = 0; it < iters; ++it)
-    discount_factors(s->dcfr_alpha, s->dcfr_beta, s->dcfr_gamma, iteration0 + it + 1, &s->h_disc[3 * static_cast<size_t>(it)]);
-  OSG_HIP(hipMemcpyAsync(s->d_disc, s->h_disc.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+    discount_factors(s->dcfr_alpha, s->dcfr_beta, s->dcfr_gamma, iteration0 + it + 1, &s->h_iter_table[3 * static_cast<size_t>(it)]);
+  OSG_HIP(hipMemcpyAsync(s->d_iter_table, s->h_iter_table.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
   if (n * sizeof(double) > (64u << 10)) OSG_HIP(hipStreamSynchronize(st));   // (as upload(): a large pageable copy may outlive the call)
-  *d_table = s->d_disc;
+  *d_table = s->d_iter_table;
   return OSG_OK;
 }
 
@@ -401,20 +396,20 @@ int osg_cfr_create(osg_ctx* ctx, const char* game_string, const osg_cfr_cfg* cfg
   }
   osg::ctx_retain(ctx);  // from here on the object dies through osg_cfr_destroy, which releases
   hipStream_t st = ctx->stream;
-  if ((rc = upload(s->level_off, &s->d_level_off, st)) || (rc = upload(s->parent, &s->d_parent, st)) ||
-      (rc = upload(s->first_child, &s->d_first_child, st)) || (rc = upload(s->info, &s->d_info, st)) ||
-      (rc = upload(s->mem_off, &s->d_mem_off, st)) || (rc = upload(s->mem, &s->d_mem, st)) ||
-      (rc = upload(s->nact, &s->d_nact, st)) || (rc = upload(s->kind, &s->d_kind, st)) ||
-      (rc = upload(s->nchild, &s->d_nchild, st)) || (rc = upload(s->aidx, &s->d_aidx, st)) ||
-      (rc = upload(s->actor, &s->d_actor, st)) || (rc = upload(s->info_player, &s->d_info_player, st)) ||
-      (rc = upload(s->edge_prob, &s->d_edge_prob, st)) || (rc = upload(s->term_ret, &s->d_term_ret, st))) {
+  if ((rc = upload(s->level_off, s->d_level_off, st)) || (rc = upload(s->parent, s->d_parent, st)) ||
+      (rc = upload(s->first_child, s->d_first_child, st)) || (rc = upload(s->info, s->d_info, st)) ||
+      (rc = upload(s->mem_off, s->d_mem_off, st)) || (rc = upload(s->mem, s->d_mem, st)) ||
+      (rc = upload(s->nact, s->d_nact, st)) || (rc = upload(s->kind, s->d_kind, st)) ||
+      (rc = upload(s->nchild, s->d_nchild, st)) || (rc = upload(s->aidx, s->d_aidx, st)) ||
+      (rc = upload(s->actor, s->d_actor, st)) || (rc = upload(s->info_player, s->d_info_player, st)) ||
+      (rc = upload(s->edge_prob, s->d_edge_prob, st)) || (rc = upload(s->term_ret, s->d_term_ret, st))) {
     osg_cfr_destroy(s);
     return rc;
   }
   const size_t IA = static_cast<size_t>(s->I) * s->A;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_tables), sizeof(double) * s->B * 5 * std::max<size_t>(IA, 1));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_reach), sizeof(double) * s->H * (s->P + 1));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_value), sizeof(double) * s->H * s->P);
+  hipError_t e = s->d_tables.alloc(s->B * 5 * std::max<size_t>(IA, 1));
+  if (e == hipSuccess) e = s->d_reach.alloc(static_cast<size_t>(s->H) * (s->P + 1));
+  if (e == hipSuccess) e = s->d_value.alloc(static_cast<size_t>(s->H) * s->P);
   if (e != hipSuccess) { osg_cfr_destroy(s); return set_error(OSG_ERR_NOMEM, hipGetErrorString(e)); }
   // Whole solver state in LDS when it fits (gfx950: 160 KiB per workgroup; leave headroom).
   s->lds_bytes = sizeof(double) * (static_cast<size_t>(s->H) * (2 * s->P + 1) + 3 * IA);
@@ -430,18 +425,16 @@ int osg_cfr_create(osg_ctx* ctx, const char* game_string, const osg_cfr_cfg* cfg
     s->meta32.resize(s->H);
     for (int h = 0; h < s->H; ++h) s->meta32[h] = s->kind[h] | (s->nchild[h] << 2) | ((s->actor[h] + 1) << 10);
     s->info_player32.assign(s->info_player.begin(), s->info_player.end());
-    if ((rc = upload(s->path_off, &s->d_path_off, st)) || (rc = upload(s->path, &s->d_path, st)) ||
-        (rc = upload(s->info_level, &s->d_info_level, st)) || (rc = upload(s->mem_index, &s->d_mem_index, st)) ||
-        (rc = upload(s->meta32, &s->d_meta32, st)) || (rc = upload(s->info_player32, &s->d_info_player32, st))) {
+    if ((rc = upload(s->path_off, s->d_path_off, st)) || (rc = upload(s->path, s->d_path, st)) ||
+        (rc = upload(s->info_level, s->eval.info_level, st)) || (rc = upload(s->mem_index, s->eval.mem_index, st)) ||
+        (rc = upload(s->meta32, s->d_meta32, st)) || (rc = upload(s->info_player32, s->d_info_player32, st))) {
       osg_cfr_destroy(s);
       return rc;
     }
-    const size_t eval_doubles = static_cast<size_t>(s->H) * (s->P + 1) + M + 2 * s->P + IA;
-    e = hipMalloc(reinterpret_cast<void**>(&s->d_eval), sizeof(double) * eval_doubles);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_best), sizeof(int32_t) * std::max(s->I, 1));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_skip), sizeof(int32_t) * std::max<size_t>(M, 1));
-    if (e == hipSuccess)
-      e = hipMalloc(reinterpret_cast<void**>(&s->d_node_delta), sizeof(double) * 2 * std::max<size_t>(M * s->A, 1));
+    e = s->eval.scratch.alloc(eval_scratch_doubles(s));
+    if (e == hipSuccess) e = s->eval.best.alloc(s->I);
+    if (e == hipSuccess) e = s->d_skip.alloc(M);
+    if (e == hipSuccess) e = s->d_node_delta.alloc(2 * std::max<size_t>(M * s->A, 1));
     if (e != hipSuccess) { osg_cfr_destroy(s); return set_error(OSG_ERR_NOMEM, hipGetErrorString(e)); }
     if (!index_fits) s->eval_ok = false;
   }
@@ -452,7 +445,7 @@ int osg_cfr_create(osg_ctx* ctx, const char* game_string, const osg_cfr_cfg* cfg
   }
   rc = build_resident_tree(s);
   if (rc) { osg_cfr_destroy(s); return rc; }
-  if (hipHostMalloc(reinterpret_cast<void**>(&s->h_sub_err), sizeof(unsigned int), hipHostMallocMapped) != hipSuccess) {
+  if (s->h_sub_err.alloc(1) != hipSuccess) {
     (void)hipGetLastError();
     osg_cfr_destroy(s);
     return set_error(OSG_ERR_NOMEM, "osg_cfr_create: pinned error word");
@@ -461,7 +454,7 @@ int osg_cfr_create(osg_ctx* ctx, const char* game_string, const osg_cfr_cfg* cfg
   rc = build_split(s);
   if (rc == OSG_OK) rc = build_sub(s);
   if (rc == OSG_OK) rc = build_eval_jobs(s);
-  if (rc == OSG_OK && hipHostMalloc(reinterpret_cast<void**>(&s->h_eval_out), sizeof(double) * (2 * s->P + 1), hipHostMallocMapped) != hipSuccess) {
+  if (rc == OSG_OK && s->eval.h_out.alloc(2 * s->P + 1) != hipSuccess) {
     (void)hipGetLastError();
     rc = set_error(OSG_ERR_NOMEM, "osg_cfr_create: pinned result buffer");
   }
@@ -475,24 +468,9 @@ int osg_cfr_create(osg_ctx* ctx, const char* game_string, const osg_cfr_cfg* cfg
 int osg_cfr_destroy(osg_cfr* s) {
   if (!s) return OSG_OK;
   (void)hipStreamSynchronize(s->ctx->stream);
-  void* ptrs[] = {s->d_level_off, s->d_parent, s->d_first_child, s->d_info, s->d_mem_off, s->d_mem, s->d_nact,
-                  s->d_kind, s->d_nchild, s->d_aidx, s->d_actor, s->d_info_player, s->d_edge_prob, s->d_term_ret,
-                  s->d_tables, s->d_reach, s->d_value, s->d_path_off, s->d_path, s->d_info_level, s->d_mem_index,
-                  s->d_best, s->d_eval, s->d_eval_ev, s->d_eval_level_info, s->d_eval_level_off, s->d_geval_bar, s->d_meta32, s->d_info_player32, s->d_skip, s->d_node_delta, s->d_rec,
-                  s->d_uret, s->d_uprob, s->d_spare_delta[0], s->d_spare_delta[1], s->d_split_nloc, s->d_split_desc,
-                  s->d_split_fc, s->d_split_row, s->d_split_glob, s->d_split_mem_m, s->d_split_mem_hloc, s->d_split_info,
-                  s->d_split_terms, s->d_split_bar, s->d_sub_nloc, s->d_sub_desc, s->d_sub_fc, s->d_sub_aux, s->d_sub_mem_off,
-                  s->d_sub_info_off, s->d_sub_info_list, s->d_sub_bar, s->d_sub_ndec, s->d_sub_dec_row, s->d_sub_rec,
-                  s->d_sub_stamps, s->d_mccfr_stamps, s->d_sub_recbuf, s->d_sub_chance_prob, s->d_sub_term_val, s->d_sub_dec_off, s->d_sub_fold_info, s->d_sub_fold_off, s->d_sub_nroot, s->d_sub_root_loc, s->d_sub_root_idx, s->d_sub_upper_rec, s->d_sub_root_value,
-                  s->d_jobs_job, s->d_jobs_level, s->d_jobs_desc, s->d_jobs_fc, s->d_jobs_row, s->d_jobs_glob, s->d_jobs_info,
-                  s->d_jobs_mem, s->d_jobs_deal, s->d_jobs_ticket, s->d_disc, s->d_qv_out, s->d_qv_best};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  mmd_destroy(s);
-  if (s->h_sub_err) (void)hipHostFree(s->h_sub_err);
-  if (s->h_eval_out) (void)hipHostFree(s->h_eval_out);
-  osg::ctx_release(s->ctx);
-  delete s;
+  osg_ctx* ctx = s->ctx;
+  delete s;                // the solver's buffers go first:
+  osg::ctx_release(ctx);   // the context's device resources may go with its last reference
   return OSG_OK;
 }
 
@@ -512,8 +490,6 @@ int osg_cfr_iterate(osg_cfr* s, int iters) {
   if (mmd_mode(s)) return set_error(OSG_ERR_INVALID, "osg_cfr_iterate: the solver is in mirror-descent mode (osg_mmd_set_params); a CFR iteration would overwrite its tables");
   if (iters == 0) return OSG_OK;
   if (int rc = cfr_sub_error(s)) return rc;
-  int threads = ((s->max_level_width + 63) / 64) * 64;
-  threads = std::max(64, std::min(threads, 1024));
   Tables tb{s->regrets(), s->cum(), s->cur()};
   if (s->B > 1) {  // all replicas advance together: workgroup b works on replica b's tables
     double* base0 = s->replica_base(0);
@@ -524,18 +500,15 @@ int osg_cfr_iterate(osg_cfr* s, int iters) {
   const bool grid_path = s->path_kernel && s->B == 1 && (s->cfg.kernel == 2 || (s->cfg.kernel == 0 && s->H > 65536));
   // Trees too big for one workgroup: the persistent cooperative launch with a workgroup per deal subtree where the
   // tree has that shape (kernel == 5 forces it, 2 forces the per-phase launches), else a launch per phase.
-  const bool sub_path = s->sub_ok && (!s->dcfr || s->sub_dcfr_ok) && s->B == 1 && (s->cfg.kernel == 5 || (s->cfg.kernel == 0 && grid_path));
+  const bool sub_path = s->sub.ok && (!s->dcfr || s->sub.dcfr_ok) && s->B == 1 && (s->cfg.kernel == 5 || (s->cfg.kernel == 0 && grid_path));
   if (sub_path) return cfr_sub_iterate(s, tb, iters);     // osg_cfr_sub.hip
   if (grid_path) return cfr_grid_iterate(s, tb, iters);   // osg_cfr_sub.hip
-  if (s->split_ok && (s->cfg.kernel == 0 || s->cfg.kernel == 4)) {
+  if (s->split.ok && (s->cfg.kernel == 0 || s->cfg.kernel == 4)) {
     // one workgroup per deal subtree, one grid barrier per player pass (k_cfr_split)
-    const int M = static_cast<int>(s->mem.size());
-    SmallTree stree{s->d_path_off, s->d_path, M, static_cast<int>(s->path.size())};
-    SplitTree sp{s->split_G, s->split_L, s->split_NL, s->split_NM, s->split_NI, s->d_split_nloc, s->d_split_desc,
-                 s->d_split_fc, s->d_split_row, s->d_split_glob, s->d_split_mem_m, s->d_split_mem_hloc, s->d_split_info,
-                 s->d_split_terms, s->d_split_bar, s->h_sub_err};
+    const SmallTree stree = small_tree_of(s);
+    const SplitTree sp = split_tree_of(s);
     const int passes = s->cfg.alternating_updates ? s->P : 1;
-    const int per_launch = std::max(1, (1 << 30) / std::max(1, passes * s->split_G));  // the arrival counter is 32 bits
+    const int per_launch = std::max(1, (1 << 30) / std::max(1, passes * s->split.G));  // the arrival counter is 32 bits
     const double* disc = nullptr;
     if (int rc = cfr_discount_table(s, s->iteration, iters, &disc)) return rc;
     for (int done = 0; done < iters; done += per_launch) {
@@ -548,7 +521,7 @@ int osg_cfr_iterate(osg_cfr* s, int iters) {
     s->last_kernel = s->dcfr ? "k_cfr_split<dcfr>" : "k_cfr_split";
     return OSG_OK;
   }
-  if (int rc = cfr_small_iterate(s, tb, iters, threads, grid_b)) return rc;   // osg_cfr_small.hip
+  if (int rc = cfr_small_iterate(s, tb, iters, grid_b)) return rc;   // osg_cfr_small.hip
   s->iteration += iters;
   return OSG_OK;
 }
@@ -563,40 +536,28 @@ int osg_cfr_br_iterate(osg_cfr* s, int iters) {
   if (s->B != 1) return set_error(OSG_ERR_UNSUPPORTED, "osg_cfr_br_iterate: one solver per object");
   if (!s->eval_ok) return set_error(OSG_ERR_UNSUPPORTED, "an information state spans several tree levels");
   if (int rc = cfr_sub_error(s)) return rc;
-  const size_t M = s->mem.size();
-  EvalArrays ea;
-  ea.path_off = s->d_path_off; ea.path = s->d_path; ea.info_level = s->d_info_level; ea.mem_index = s->d_mem_index;
-  ea.M = static_cast<int>(M);
-  ea.value = s->d_eval;
-  ea.brv = ea.value + static_cast<size_t>(s->H) * s->P;
-  ea.cf = ea.brv + s->H;
-  ea.out = ea.cf + M;
-  ea.best = s->d_best;
-  int threads = ((s->max_level_width + 63) / 64) * 64;
-  threads = std::max(64, std::min(threads, 1024));
+  const EvalArrays ea = eval_arrays_of(s);
   osg_cfr_cfg cfg = s->cfg;
   cfg.alternating_updates = 0;
   Tables tb{s->regrets(), s->cum(), s->cur()};
   // every player's best response to the current policy (cfr_br.cc:55-68), then one regret / average-policy
   // pass per player against the others' best responses (cfr_br.cc:70-81) and ApplyRegretMatching
-  const bool jobs = s->jobs_ok && OSG_EVAL_JOBS_ENABLED();
-  const bool split = s->split_ok && s->split_br_ok && (s->cfg.kernel == 0 || s->cfg.kernel == 4);
-  SmallTree stree{s->d_path_off, s->d_path, static_cast<int>(M), static_cast<int>(s->path.size())};
-  SplitTree sp{s->split_G, s->split_L, s->split_NL, s->split_NM, s->split_NI, s->d_split_nloc, s->d_split_desc,
-               s->d_split_fc, s->d_split_row, s->d_split_glob, s->d_split_mem_m, s->d_split_mem_hloc, s->d_split_info,
-               s->d_split_terms, s->d_split_bar, s->h_sub_err};
+  const bool jobs = s->jobs.ok && OSG_EVAL_JOBS_ENABLED();
+  const bool split = s->split.ok && s->split.br_ok && (s->cfg.kernel == 0 || s->cfg.kernel == 4);
   if (!split && !jobs && eval_takes_the_grid(s) && s->path_kernel) {   // large trees (osg_cfr_sub.hip)
     // the P passes in ONE persistent launch per iteration (kernel == 2 keeps a launch per phase: the cross-check)
-    if (s->sub_ok && s->sub_br_ok && s->cfg.kernel != 2) return cfr_sub_br_iterate(s, tb, ea, cfg, iters);
+    if (s->sub.ok && s->sub.br_ok && s->cfg.kernel != 2) return cfr_sub_br_iterate(s, tb, ea, cfg, iters);
     return cfr_grid_br_iterate(s, tb, ea, cfg, iters);
   }
+  const SmallTree stree = small_tree_of(s);
+  const SplitTree sp = split_tree_of(s);
   for (int it = 0; it < iters; ++it) {
-    if (int rc = cfr_best_responses_to_current(s, ea, threads, jobs)) return rc;   // osg_cfr_eval.hip
+    if (int rc = cfr_best_responses_to_current(s, ea, jobs)) return rc;   // osg_cfr_eval.hip
     if (split) {
       const int rc = launch_split(s, stree, sp, tb, 1, s->iteration, cfg, true);
       if (rc) return rc;
     } else {
-      cfr_general_br_pass(s, tb, threads, cfg);   // osg_cfr_small.hip
+      cfr_general_br_pass(s, tb, cfg);   // osg_cfr_small.hip
     }
     ++s->iteration;
   }
@@ -636,7 +597,7 @@ int osg_cfr_tables(const osg_cfr* s, int32_t* nact, int32_t* legal, double* regr
   if (cur_policy) OSG_HIP(hipMemcpyAsync(cur_policy, s->cur(), bytes, hipMemcpyDeviceToHost, st));
   OSG_HIP(hipMemcpyAsync(cum.data(), s->cum(), bytes, hipMemcpyDeviceToHost, st));
   unsigned int split_error = 0;
-  if (s->split_ok) OSG_HIP(hipMemcpyAsync(&split_error, s->d_split_bar + 2, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+  if (s->split.ok) OSG_HIP(hipMemcpyAsync(&split_error, s->split.bar + 2, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
   OSG_HIP(hipStreamSynchronize(st));
   if (split_error)
     return set_error(OSG_ERR_HIP, "k_cfr_split: a grid barrier timed out after seconds (the launch is cooperative: this is a hung "

@@ -511,10 +511,10 @@ namespace osg_cfr_impl {
 
 EvalJobs eval_jobs_of(const osg_cfr* s) {
   EvalJobs ej;
-  ej.J = s->jobs_J; ej.L = s->jobs_L; ej.G = s->jobs_G; ej.NT = s->jobs_NT;
-  ej.job = s->d_jobs_job; ej.level_off = s->d_jobs_level; ej.node_desc = s->d_jobs_desc; ej.node_fc = s->d_jobs_fc;
-  ej.node_row = s->d_jobs_row; ej.node_glob = s->d_jobs_glob; ej.info_ent = s->d_jobs_info; ej.mem_ent = s->d_jobs_mem;
-  ej.deal = s->d_jobs_deal; ej.ticket = s->d_jobs_ticket;
+  ej.J = s->jobs.J; ej.L = s->jobs.L; ej.G = s->jobs.G; ej.NT = s->jobs.NT;
+  ej.job = s->jobs.job; ej.level_off = s->jobs.level; ej.node_desc = s->jobs.desc; ej.node_fc = s->jobs.fc;
+  ej.node_row = s->jobs.row; ej.node_glob = s->jobs.glob; ej.info_ent = s->jobs.info; ej.mem_ent = s->jobs.mem;
+  ej.deal = s->jobs.deal; ej.ticket = s->jobs.ticket;
   return ej;
 }
 
@@ -526,7 +526,42 @@ bool eval_takes_the_grid(const osg_cfr* s) {
   if (e && e[0] == '1') return true;
   return s->H > 65536;
 }
-int launch_grid_eval(const osg_cfr* s, const EvalArrays& ea, const double* src, bool from_cum, double* d_pol, bool only_br) {
+// The plan of the large-tree evaluation, made at its first use: the infostates of every level, and — only where
+// OSG_EVAL_PERSIST=1 asks for the one persistent launch — the offsets on the device, the grid barrier and the grid.
+static int build_grid_eval_plan(osg_cfr* s, bool persist) {
+  EvalPlan& p = s->eval;
+  hipStream_t st = s->ctx->stream;
+  if (p.level_off.empty()) {
+    std::vector<int32_t> off(static_cast<size_t>(s->D) + 1, 0);
+    for (int i = 0; i < s->I; ++i)
+      if (s->info_level[i] >= 0 && s->info_level[i] < s->D) ++off[s->info_level[i] + 1];
+    for (int l = 0; l < s->D; ++l) off[l + 1] += off[l];
+    std::vector<int32_t> list(static_cast<size_t>(std::max(off[s->D], 1)), 0), at(off.begin(), off.end() - 1);
+    for (int i = 0; i < s->I; ++i)
+      if (s->info_level[i] >= 0 && s->info_level[i] < s->D) list[at[s->info_level[i]]++] = i;
+    if (int rc = upload(list, p.level_info, st)) return rc;
+    p.level_off = std::move(off);   // (last: "built" is said only of a plan that is whole)
+  }
+  if (persist && p.grid == 0) {
+    if (int rc = upload(p.level_off, p.d_level_off, st)) return rc;
+    OSG_HIP(p.bar.alloc(kSubBarWords));
+    int per_cu = 0;
+    hipDeviceProp_t prop;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_geval_persist, kGEvalThreads, 0) != hipSuccess || per_cu < 1 ||
+        hipGetDeviceProperties(&prop, s->ctx->device) != hipSuccess || !prop.cooperativeLaunch) {
+      (void)hipGetLastError();
+      p.grid = -1;   // (no resident grid: a launch per level and phase)
+    } else {
+      const char* w = getenv("OSG_EVAL_PERSIST_PER_CU");
+      const int want = w ? std::max(1, atoi(w)) : 1;
+      p.grid = std::min(std::min(per_cu, want) * prop.multiProcessorCount, 1024);
+      if (static_cast<unsigned long long>(s->H) * s->P * sizeof(double) >= (1ull << 31)) p.grid = -1;   // (32-bit buffer offsets)
+    }
+  }
+  return OSG_OK;
+}
+
+int launch_grid_eval(osg_cfr* s, const EvalArrays& ea, const double* src, bool from_cum, double* d_pol, bool only_br) {
   hipStream_t st = s->ctx->stream;
   const Tree t = s->tree();
   const double* pol = src;
@@ -538,69 +573,38 @@ int launch_grid_eval(const osg_cfr* s, const EvalArrays& ea, const double* src, 
   // (the expected returns ride in the best responses' sweep, in an [H, P] array of their own: allocated on first use)
   double* d_ev = nullptr;
   if (!only_br) {
-    osg_cfr* mut = const_cast<osg_cfr*>(s);
-    if (!mut->d_eval_ev)
-      OSG_HIP(hipMalloc(reinterpret_cast<void**>(&mut->d_eval_ev), sizeof(double) * static_cast<size_t>(s->H) * s->P));
-    d_ev = mut->d_eval_ev;
+    if (!s->eval.ev) OSG_HIP(s->eval.ev.alloc(static_cast<size_t>(s->H) * s->P));
+    d_ev = s->eval.ev;
   }
-  const unsigned mblocks = static_cast<unsigned>((s->mem.size() + 255) / 256), iblocks = static_cast<unsigned>((s->I + 255) / 256);
+  const unsigned mblocks = static_cast<unsigned>((s->mem.size() + 255) / 256);
   // every player's best response in one bottom-up sweep: the responder values take the expected-value array over (its
   // sweep is done: the root's values are in out); the argmax launch only where the level holds infostates
-  osg_cfr* ms = const_cast<osg_cfr*>(s);
-  if (ms->eval_level_off.empty()) {   // the infostates of every level, once per solver
-    ms->eval_level_off.assign(static_cast<size_t>(s->D) + 1, 0);
-    for (int i = 0; i < s->I; ++i)
-      if (s->info_level[i] >= 0 && s->info_level[i] < s->D) ++ms->eval_level_off[s->info_level[i] + 1];
-    for (int l = 0; l < s->D; ++l) ms->eval_level_off[l + 1] += ms->eval_level_off[l];
-    std::vector<int32_t> list(static_cast<size_t>(std::max(ms->eval_level_off[s->D], 1)), 0), at(ms->eval_level_off.begin(), ms->eval_level_off.end() - 1);
-    for (int i = 0; i < s->I; ++i)
-      if (s->info_level[i] >= 0 && s->info_level[i] < s->D) list[at[s->info_level[i]]++] = i;
-    if (int rc = upload(list, &ms->d_eval_level_info, st)) return rc;
-  }
-  (void)iblocks;
   // OSG_EVAL_PERSIST=1: ONE persistent cooperative launch for the whole sweep (round 6).  Measured SLOWER than the launches
   // below on 3-player leduc (0.61 against 0.40 ms per NashConv, profiles/r06t_*): not the default; kept as the cross-check
-  {
-    const char* pe = getenv("OSG_EVAL_PERSIST");
-    if (pe && pe[0] == '1') {
-      if (!ms->d_eval_level_off) {
-        if (int rc = upload(ms->eval_level_off, &ms->d_eval_level_off, st)) return rc;
-        OSG_HIP(hipMalloc(reinterpret_cast<void**>(&ms->d_geval_bar), sizeof(unsigned int) * kSubBarWords));
-        int per_cu = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_geval_persist, kGEvalThreads, 0) != hipSuccess || per_cu < 1 ||
-            hipGetDeviceProperties(&prop, s->ctx->device) != hipSuccess || !prop.cooperativeLaunch) {
-          (void)hipGetLastError();
-          ms->geval_grid = -1;   // (no resident grid: the launches below)
-        } else {
-          const char* w = getenv("OSG_EVAL_PERSIST_PER_CU");
-          const int want = w ? std::max(1, atoi(w)) : 1;
-          ms->geval_grid = std::min(std::min(per_cu, want) * prop.multiProcessorCount, 1024);
-          if (static_cast<unsigned long long>(s->H) * s->P * sizeof(double) >= (1ull << 31)) ms->geval_grid = -1;   // (32-bit buffer offsets)
-        }
-      }
-      if (ms->geval_grid > 0) {
-        GEvalPlan gp{ms->d_eval_level_info, ms->d_eval_level_off, ms->d_geval_bar, s->h_sub_err, 400000000ull /* 4 s at 100 MHz */};
-        OSG_HIP(hipMemsetAsync(ms->d_geval_bar, 0, sizeof(unsigned int) * kSubBarWords, st));
-        Tree tt = t;
-        EvalArrays eaa = ea;
-        const double* pp = pol;
-        void* args[] = {&tt, &eaa, &pp, &d_ev, &gp};
-        static const bool plain = std::getenv("OSG_CFR_PLAIN_LAUNCH") && std::getenv("OSG_CFR_PLAIN_LAUNCH")[0] == '1';
-        const void* kern = reinterpret_cast<const void*>(&k_geval_persist);
-        if (plain) OSG_HIP(hipLaunchKernel(kern, dim3(static_cast<unsigned>(ms->geval_grid)), dim3(kGEvalThreads), args, 0, st));
-        else OSG_HIP(hipLaunchCooperativeKernel(kern, dim3(static_cast<unsigned>(ms->geval_grid)), dim3(kGEvalThreads), args, 0, st));
-        ms->last_eval_kernel = "k_geval_persist";
-        return OSG_OK;
-      }
-    }
+  const char* pe = getenv("OSG_EVAL_PERSIST");
+  const bool persist = pe && pe[0] == '1';
+  if (s->eval.level_off.empty() || (persist && s->eval.grid == 0))
+    if (int rc = build_grid_eval_plan(s, persist)) return rc;
+  if (persist && s->eval.grid > 0) {
+    GEvalPlan gp{s->eval.level_info, s->eval.d_level_off, s->eval.bar, s->h_sub_err, 400000000ull /* 4 s at 100 MHz */};
+    OSG_HIP(hipMemsetAsync(s->eval.bar, 0, sizeof(unsigned int) * kSubBarWords, st));
+    Tree tt = t;
+    EvalArrays eaa = ea;
+    const double* pp = pol;
+    void* args[] = {&tt, &eaa, &pp, &d_ev, &gp};
+    static const bool plain = std::getenv("OSG_CFR_PLAIN_LAUNCH") && std::getenv("OSG_CFR_PLAIN_LAUNCH")[0] == '1';
+    const void* kern = reinterpret_cast<const void*>(&k_geval_persist);
+    if (plain) OSG_HIP(hipLaunchKernel(kern, dim3(static_cast<unsigned>(s->eval.grid)), dim3(kGEvalThreads), args, 0, st));
+    else OSG_HIP(hipLaunchCooperativeKernel(kern, dim3(static_cast<unsigned>(s->eval.grid)), dim3(kGEvalThreads), args, 0, st));
+    s->last_eval_kernel = "k_geval_persist";
+    return OSG_OK;
   }
-  ms->last_eval_kernel = "k_geval";
+  s->last_eval_kernel = "k_geval";
   k_geval_cf<<<dim3(std::max(1u, mblocks)), dim3(256), 0, st>>>(t, ea, pol);
   for (int l = s->D - 1; l >= 0; --l) {
-    const int n_infos = ms->eval_level_off[l + 1] - ms->eval_level_off[l];
+    const int n_infos = s->eval.level_off[l + 1] - s->eval.level_off[l];
     if (n_infos > 0)
-      k_geval_best<<<dim3(static_cast<unsigned>((n_infos + 3) / 4)), dim3(256), 0, st>>>(t, ea, ms->d_eval_level_info + ms->eval_level_off[l], n_infos);
+      k_geval_best<<<dim3(static_cast<unsigned>((n_infos + 3) / 4)), dim3(256), 0, st>>>(t, ea, s->eval.level_info + s->eval.level_off[l], n_infos);
     k_geval_brv<<<dim3(width(l)), dim3(256), 0, st>>>(t, ea, pol, l, d_ev);
   }
   OSG_HIP(hipGetLastError());
@@ -618,7 +622,7 @@ bool OSG_EVAL_JOBS_ENABLED() {
 // member history of the same infostate of r", one best-response job per component.  Trees of another shape, or with a
 // component that does not fit a workgroup's LDS, keep the one-workgroup kernel.
 int build_eval_jobs(osg_cfr* s) {
-  s->jobs_ok = false;
+  s->jobs.ok = false;
   if (!s->eval_ok || s->H < 2000 || s->D >= 64 || s->P > 15) return OSG_OK;
   const int P = s->P, A = s->A, D = s->D;
   int L = 0;
@@ -714,30 +718,30 @@ int build_eval_jobs(osg_cfr* s) {
   if (lds > 150 * 1024) return OSG_OK;
   hipStream_t st = s->ctx->stream;
   int rc;
-  if ((rc = upload(job, &s->d_jobs_job, st)) || (rc = upload(jlevel, &s->d_jobs_level, st)) ||
-      (rc = upload(desc, &s->d_jobs_desc, st)) || (rc = upload(fc, &s->d_jobs_fc, st)) || (rc = upload(row, &s->d_jobs_row, st)) ||
-      (rc = upload(glob, &s->d_jobs_glob, st)) || (rc = upload(ient, &s->d_jobs_info, st)) || (rc = upload(ment, &s->d_jobs_mem, st)))
+  if ((rc = upload(job, s->jobs.job, st)) || (rc = upload(jlevel, s->jobs.level, st)) ||
+      (rc = upload(desc, s->jobs.desc, st)) || (rc = upload(fc, s->jobs.fc, st)) || (rc = upload(row, s->jobs.row, st)) ||
+      (rc = upload(glob, s->jobs.glob, st)) || (rc = upload(ient, s->jobs.info, st)) || (rc = upload(ment, s->jobs.mem, st)))
     return rc;
-  OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_jobs_deal), sizeof(double) * 2 * P * G));
-  OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_jobs_ticket), sizeof(unsigned int) * 4));
-  OSG_HIP(hipMemsetAsync(s->d_jobs_deal, 0, sizeof(double) * 2 * P * G, st));
-  OSG_HIP(hipMemsetAsync(s->d_jobs_ticket, 0, sizeof(unsigned int) * 4, st));
+  OSG_HIP(s->jobs.deal.alloc(static_cast<size_t>(2) * P * G));
+  OSG_HIP(s->jobs.ticket.alloc(4));
+  OSG_HIP(hipMemsetAsync(s->jobs.deal, 0, sizeof(double) * 2 * P * G, st));
+  OSG_HIP(hipMemsetAsync(s->jobs.ticket, 0, sizeof(unsigned int) * 4, st));
   if (raise_lds_cap(reinterpret_cast<const void*>(&k_eval_jobs), static_cast<int>(lds)) != hipSuccess) {
     (void)hipGetLastError();
     return OSG_OK;
   }
-  s->jobs_J = J; s->jobs_L = L; s->jobs_G = G; s->jobs_NT = NT; s->jobs_lds_bytes = lds;
-  s->jobs_threads = std::max(64, std::min(1024, (max_nodes + 63) / 64 * 64));
-  s->jobs_ok = true;
+  s->jobs.J = J; s->jobs.L = L; s->jobs.G = G; s->jobs.NT = NT; s->jobs.lds_bytes = lds;
+  s->jobs.threads = std::max(64, std::min(1024, (max_nodes + 63) / 64 * 64));
+  s->jobs.ok = true;
   return OSG_OK;
 }
 
 // Every player's best response to the current policy (cfr_br.cc:55-68): the first half of a CFR-BR iteration.
-int cfr_best_responses_to_current(osg_cfr* s, const EvalArrays& ea, int threads, bool jobs) {
+int cfr_best_responses_to_current(osg_cfr* s, const EvalArrays& ea, bool jobs) {
   hipStream_t st = s->ctx->stream;
-  if (jobs) { k_eval_jobs<<<dim3(s->jobs_J), dim3(s->jobs_threads), s->jobs_lds_bytes, st>>>(s->tree(), ea, eval_jobs_of(s), s->cur(), 1, 1); s->last_eval_kernel = "k_eval_jobs"; }
+  if (jobs) { k_eval_jobs<<<dim3(s->jobs.J), dim3(s->jobs.threads), s->jobs.lds_bytes, st>>>(s->tree(), ea, eval_jobs_of(s), s->cur(), 1, 1); s->last_eval_kernel = "k_eval_jobs"; }
   else if (eval_takes_the_grid(s)) { if (int rc = launch_grid_eval(s, ea, s->cur(), false, nullptr, true)) return rc; }
-  else { k_policy_eval<<<dim3(1), dim3(threads), 0, st>>>(s->tree(), ea, s->cur()); s->last_eval_kernel = "k_policy_eval"; }
+  else { k_policy_eval<<<dim3(1), dim3(level_threads(s)), 0, st>>>(s->tree(), ea, s->cur()); s->last_eval_kernel = "k_policy_eval"; }
   return OSG_OK;
 }
 
@@ -767,33 +771,27 @@ static int evaluate_policy_impl(osg_cfr* s, int which_policy, const double* h_po
                                 int keep_responder, double* h_history_values) {
   if (!s) return set_error(OSG_ERR_INVALID, "osg_cfr_evaluate_policy: null solver");
   if (!s->eval_ok) return set_error(OSG_ERR_UNSUPPORTED, "an information state spans several tree levels");
-  const size_t IA = static_cast<size_t>(s->I) * s->A, M = s->mem.size();
+  const size_t IA = static_cast<size_t>(s->I) * s->A;
   const int P = s->P;
   hipStream_t st = s->ctx->stream;
   if (which_policy < 0 || which_policy > 2) return set_error(OSG_ERR_INVALID, "osg_cfr_evaluate_policy: which_policy must be 0, 1 or 2");
   if (which_policy != 2)
     if (int rc = cfr_sub_error(s)) return rc;
   if (which_policy == 2 && !h_policy) return set_error(OSG_ERR_INVALID, "osg_cfr_evaluate_policy: which_policy == 2 needs h_policy");
-  EvalArrays ea;
-  ea.path_off = s->d_path_off; ea.path = s->d_path; ea.info_level = s->d_info_level; ea.mem_index = s->d_mem_index;
-  ea.M = static_cast<int>(M);
-  ea.value = s->d_eval;
-  ea.brv = ea.value + static_cast<size_t>(s->H) * P;
-  ea.cf = ea.brv + s->H;
-  double* d_pol = ea.cf + M + 2 * P;
+  EvalArrays ea = eval_arrays_of(s);
+  double* d_pol = eval_policy_slot(s);
   // the 2 P results land in pinned host memory straight from the kernel (the device address of h_eval_out): the call is a
   // launch and a wait — no copy-back launches (two of them were ~10 us of a 45 us call)
-  OSG_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&ea.out), s->h_eval_out, 0));
-  ea.best = s->d_best;
-  if (h_history_values) {  // the responder's value of every history: kept in d_reach ([H, P + 1] doubles, free here)
-    ea.keep = s->d_reach;
+  OSG_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&ea.out), s->eval.h_out, 0));
+  if (h_history_values) {  // the responder's value of every history
+    ea.keep = history_values_in_reach(s);
     ea.keep_r = keep_responder;
   }
-  if (s->jobs_ok && OSG_EVAL_JOBS_ENABLED()) {
+  if (s->jobs.ok && OSG_EVAL_JOBS_ENABLED()) {
     // the tables never leave the device: the average policy is formed from the cumulative table inside the jobs
     const double* src = which_policy == 0 ? s->cum() : which_policy == 1 ? s->cur() : d_pol;
     if (which_policy == 2) OSG_HIP(hipMemcpyAsync(d_pol, h_policy, sizeof(double) * IA, hipMemcpyHostToDevice, st));
-    k_eval_jobs<<<dim3(s->jobs_J), dim3(s->jobs_threads), s->jobs_lds_bytes, st>>>(s->tree(), ea, eval_jobs_of(s), src,
+    k_eval_jobs<<<dim3(s->jobs.J), dim3(s->jobs.threads), s->jobs.lds_bytes, st>>>(s->tree(), ea, eval_jobs_of(s), src,
                                                                                    which_policy == 0 ? 0 : 1, 0);
     s->last_eval_kernel = "k_eval_jobs";
     OSG_HIP(hipGetLastError());
@@ -804,18 +802,16 @@ static int evaluate_policy_impl(osg_cfr* s, int which_policy, const double* h_po
   } else {
     const double* src = which_policy == 0 ? s->cum() : which_policy == 1 ? s->cur() : d_pol;
     if (which_policy == 2) OSG_HIP(hipMemcpyAsync(d_pol, h_policy, sizeof(double) * IA, hipMemcpyHostToDevice, st));
-    int threads = ((s->max_level_width + 63) / 64) * 64;
-    threads = std::max(64, std::min(threads, 1024));
-    k_policy_eval<<<dim3(1), dim3(threads), 0, st>>>(s->tree(), ea, src, which_policy == 0 ? 1 : 0, d_pol);
+    k_policy_eval<<<dim3(1), dim3(level_threads(s)), 0, st>>>(s->tree(), ea, src, which_policy == 0 ? 1 : 0, d_pol);
     s->last_eval_kernel = "k_policy_eval";
     OSG_HIP(hipGetLastError());
   }
   if (h_history_values)
-    OSG_HIP(hipMemcpyAsync(h_history_values, s->d_reach, sizeof(double) * s->H, hipMemcpyDeviceToHost, st));
+    OSG_HIP(hipMemcpyAsync(h_history_values, ea.keep, sizeof(double) * s->H, hipMemcpyDeviceToHost, st));
   OSG_HIP(hipStreamSynchronize(st));
   if (which_policy != 2)   // the tables are only as good as the launches that wrote them (the kernels raise the pinned word)
     if (int rc = cfr_sub_error(s)) return rc;
-  const double* out = s->h_eval_out;
+  const double* out = s->eval.h_out;
   double nc = 0.0, total_br = 0.0;
   for (int p = 0; p < P; ++p) {
     if (expected_returns) expected_returns[p] = out[p];
@@ -835,7 +831,7 @@ int osg_cfr_best_response(osg_cfr* s, int which_policy, const double* h_policy, 
   if (!s || !h_best_index) return set_error(OSG_ERR_INVALID, "osg_cfr_best_response: null argument");
   int rc = osg_cfr_evaluate_policy(s, which_policy, h_policy, nullptr, best_response_values, nullptr, nullptr);
   if (rc) return rc;
-  OSG_HIP(hipMemcpyAsync(h_best_index, s->d_best, sizeof(int32_t) * s->I, hipMemcpyDeviceToHost, s->ctx->stream));
+  OSG_HIP(hipMemcpyAsync(h_best_index, s->eval.best, sizeof(int32_t) * s->I, hipMemcpyDeviceToHost, s->ctx->stream));
   OSG_HIP(hipStreamSynchronize(s->ctx->stream));
   return OSG_OK;
 }

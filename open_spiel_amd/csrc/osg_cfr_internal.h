@@ -8,8 +8,13 @@
 //   osg_cfr_qvalues.hip k_qvalues_small, k_qv_*       per-infostate action values and reaches of a policy
 //   osg_cfr_mccfr.hip   k_mccfr*, k_os_mccfr*, ...    external / outcome sampling MCCFR and their entry points
 //
+//   osg_cfr_xfp.hip     k_xfp_small, k_xfp_*          extensive-form fictitious play
+//   osg_cfr_mmd.hip     k_mmd_small, k_mmd_*          magnetic mirror descent (MmdState lives there)
+//
 // Every kernel is launched from the translation unit that defines it; what crosses the units are the device-side
-// argument structs below, struct osg_cfr, and the host functions declared at the end.  Reference files: cfr.{h,cc},
+// argument structs below (views: raw pointers), the per-family plans that own the memory behind them (SplitPlan,
+// SubPlan, EvalPlan, JobsPlan, ResidentPlan: DeviceArray / PinnedArray of osg_device_buffer.h), struct osg_cfr, the one
+// function per family that forms a view from its plan, and the host functions declared at the end.  Reference files: cfr.{h,cc},
 // external_sampling_mccfr.{h,cc}, outcome_sampling_mccfr.cc, cfr_br.cc, expected_returns.cc, best_response.cc.
 #pragma once
 #include <algorithm>
@@ -18,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -365,24 +371,80 @@ constexpr int kMaxOsDepth = 32;
 
 struct MmdState;   // magnetic mirror descent's host-built arrays and parameters (osg_cfr_mmd.hip)
 
-template <class T>
-int upload(const std::vector<T>& v, T** d, hipStream_t stream) {
-  const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  OSG_HIP(hipMalloc(reinterpret_cast<void**>(d), bytes));
-  if (!v.empty()) {
-    OSG_HIP(hipMemcpyAsync(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-    // The callers pass vectors that die when they return, and a large copy from pageable memory may still be reading
-    // the host buffer after the call (seen once as a GPU fault at a host address with an 87 MB vector): wait.
-    if (v.size() * sizeof(T) > (64u << 10)) OSG_HIP(hipStreamSynchronize(stream));
-  }
-  return OSG_OK;
-}
+// ---------------------------------------------------------------------------
+// What the solver holds per kernel family: the plan's sizes and the device arrays a build_* function uploaded.  Each
+// owns its memory (osg_device_buffer.h); the matching view struct above is formed from it by ONE function, declared
+// at the end of this header (split_tree_of, sub_tree_of, eval_jobs_of, eval_arrays_of).
+// ---------------------------------------------------------------------------
+struct SplitPlan {   // one workgroup per deal subtree (k_cfr_split): build_split -> split_tree_of
+  bool ok = false, br_ok = false;
+  int G = 0, L = 0, NL = 0, NM = 0, NI = 0, threads = 0;
+  size_t lds_bytes = 0;
+  DeviceArray<int32_t> nloc, desc, fc, row, glob, mem_m, mem_hloc, info;
+  DeviceArray<double> terms;
+  DeviceArray<unsigned int> bar;
+};
+
+struct SubPlan {   // one cooperative launch, a workgroup per deal subtree of any size (k_cfr_sub): build_sub -> sub_tree_of
+  bool ok = false;
+  bool br_ok = false;           // k_cfr_sub<., kBr> (the CFR-BR pass set) fits the same grid
+  bool dcfr_ok = false;         // k_cfr_sub<., false, kDcfr> (Discounted CFR) fits the same grid
+  int G = 0, L = 0, NL = 0, K = 0, grid = 0;
+  size_t lds_bytes = 0;
+  int ND = 0, PL = 0;
+  DeviceArray<int32_t> ndec, dec_row, rec, nloc, desc, fc, aux, mem_off, info_off, info_list;
+  DeviceArray<unsigned int> bar;
+  // forest form (SubTree's comment): the kernel's own skip words, piece roots, upper members
+  bool forest = false;
+  int NR = 0, G0 = 0;   // G0: the deal subtrees; G: the bins they (or their pieces) were packed into
+  DeviceArray<unsigned long long> stamps;   // profiling stamps, made at the first call that asks for them (per solver: never shared across contexts / devices)
+  DeviceArray<double> recbuf, chance_prob, term_val;
+  DeviceArray<int32_t> dec_off, fold_info, fold_off;
+  int NCP = 0;
+  bool keep_rows = false;
+  DeviceArray<int32_t> nroot, root_loc, root_idx, upper_rec;
+  DeviceArray<double> root_value;
+};
+
+struct EvalPlan {   // policy evaluation (k_policy_eval, k_geval_*): eval_arrays_of, eval_policy_slot
+  DeviceArray<int32_t> info_level, mem_index, best;
+  DeviceArray<double> scratch;   // value [H,P] | brv [H] | cf [M] | out [2P] | policy [I,A]: laid out by eval_arrays_of alone
+  PinnedArray<double> h_out;     // mapped: the evaluation kernels write their [2 P] results here
+  // the large-tree evaluation's plan (launch_grid_eval), built at its first use
+  DeviceArray<double> ev;             // [H, P]: the expected returns, made at the first evaluation that wants them
+  std::vector<int32_t> level_off;     // [D + 1] the infostates of level l: level_info[level_off[l] ...); empty: not built
+  DeviceArray<int32_t> level_info;
+  DeviceArray<int32_t> d_level_off;   // the same offsets on the device (k_geval_persist)
+  DeviceArray<unsigned int> bar;      // its grid barrier's counters
+  int grid = 0;                       // its resident grid (0: not asked for yet, -1: none, a launch per level and phase instead)
+};
+
+struct JobsPlan {   // the evaluation as independent jobs over the device (k_eval_jobs): build_eval_jobs -> eval_jobs_of
+  bool ok = false;
+  int J = 0, L = 0, G = 0, NT = 0, threads = 0;
+  size_t lds_bytes = 0;
+  DeviceArray<int32_t> job, level, desc, fc, row, glob, info, mem;
+  DeviceArray<double> deal;
+  DeviceArray<unsigned int> ticket;
+};
+
+struct ResidentPlan {   // LDS-resident MCCFR traversal (k_mccfr_resident): build_resident_tree
+  bool ok = false;
+  size_t lds_bytes = 0;
+  int n_uret = 0, n_uprob = 0;
+  DeviceArray<uint64_t> rec;
+  DeviceArray<double> uret, uprob;
+};
 
 }  // namespace osg_cfr_impl
 
 using namespace osg_cfr_impl;
 
+// The solver object.  It owns every device and pinned allocation it uses, through the members below: osg_cfr_destroy
+// deletes it and nothing else frees solver memory.
 struct osg_cfr {
+  osg_cfr();
+  ~osg_cfr();   // (out of line: MmdState is complete in osg_cfr_mmd.hip only)
   osg_ctx* ctx = nullptr;
   GameSpec spec;
   osg_cfr_cfg cfg{};
@@ -391,12 +453,13 @@ struct osg_cfr {
   int max_level_width = 0;
   int average_type = 0;  // ES-MCCFR AverageType: 0 kSimple, 1 kFull (external_sampling_mccfr.h:48)
   int iteration = 0;
-  // Discounted CFR (osg_cfr_set_discounting): the exponents, and the factor table of the latest launch
+  // Discounted CFR (osg_cfr_set_discounting): the exponents
   bool dcfr = false;
   double dcfr_alpha = 0.0, dcfr_beta = 0.0, dcfr_gamma = 0.0;
-  std::vector<double> h_disc;
-  double* d_disc = nullptr;
-  size_t disc_cap = 0;   // doubles
+  // One value set per iteration of the latest launch, grow-only: Discounted CFR's three factors, or
+  // fictitious play's averaging weight — a solver runs one of the two, never both
+  std::vector<double> h_iter_table;
+  DeviceArray<double> d_iter_table;
   const char* last_kernel = "";  // the kernel family the last iterate / sample call launched (osg_cfr_last_kernel)
   // host tree
   std::vector<int32_t> level_off, parent, first_child, info, mem_off, mem, nact, legal;
@@ -406,92 +469,45 @@ struct osg_cfr {
   std::vector<double> edge_prob, term_ret;
   std::vector<std::string> keys;
   // device tree
-  int32_t *d_level_off = nullptr, *d_parent = nullptr, *d_first_child = nullptr, *d_info = nullptr,
-          *d_mem_off = nullptr, *d_mem = nullptr, *d_nact = nullptr;
-  uint8_t *d_kind = nullptr, *d_nchild = nullptr, *d_aidx = nullptr;
-  int8_t *d_actor = nullptr, *d_info_player = nullptr;
-  double *d_edge_prob = nullptr, *d_term_ret = nullptr;
+  DeviceArray<int32_t> d_level_off, d_parent, d_first_child, d_info, d_mem_off, d_mem, d_nact;
+  DeviceArray<uint8_t> d_kind, d_nchild, d_aidx;
+  DeviceArray<int8_t> d_actor, d_info_player;
+  DeviceArray<double> d_edge_prob, d_term_ret;
   // device tables and work arrays
-  double* d_tables = nullptr;  // regrets | cum | cur | dreg | dpol, each [I, A]
-  double* d_reach = nullptr;   // [H, P+1]
-  double* d_value = nullptr;   // [H, P]
+  DeviceArray<double> d_tables;  // regrets | cum | cur | dreg | dpol, each [I, A]
+  DeviceArray<double> d_reach;   // [H, P+1]; between CFR launches its borrowers take it through the *_in_reach accessors below
+  DeviceArray<double> d_value;   // [H, P]
   bool lds_resident = false;
   size_t lds_bytes = 0;
   // small-tree kernel: root paths of the decision histories (member order)
   std::vector<int32_t> path_off, path;
-  int32_t *d_path_off = nullptr, *d_path = nullptr;
+  DeviceArray<int32_t> d_path_off, d_path;
   bool small_tree = false;   // the all-in-LDS variant fits
   bool path_kernel = false;  // the path-based kernel (k_cfr_small) is usable at all
   int max_path_decisions = 0;  // the most decision entries any member's root path holds
   int first_decision_level = 0;  // the first level with a decision history (SmallTree::L0)
   size_t small_lds_bytes = 0;
   std::vector<int32_t> meta32, info_player32;
-  int32_t *d_meta32 = nullptr, *d_info_player32 = nullptr, *d_skip = nullptr;
-  double* d_node_delta = nullptr;  // dreg [M, A] | dpol [M, A]
-  double* d_spare_delta[2] = {nullptr, nullptr};  // osg_mccfr_spare_delta_buffer: [2, I, A] each, allocated on request
+  DeviceArray<int32_t> d_meta32, d_info_player32, d_skip;
+  DeviceArray<double> d_node_delta;  // dreg [M, A] | dpol [M, A]
+  DeviceArray<double> d_spare_delta[2];  // osg_mccfr_spare_delta_buffer: [2, I, A] each, allocated on request
   bool delta_clean[3] = {false, false, false};    // the internal / spare delta buffers are all zero (the last fold left them so)
-  // one workgroup per deal subtree (k_cfr_split)
-  bool split_ok = false, split_br_ok = false;
-  int split_G = 0, split_L = 0, split_NL = 0, split_NM = 0, split_NI = 0, split_threads = 0;
-  size_t split_lds_bytes = 0;
-  int32_t *d_split_nloc = nullptr, *d_split_desc = nullptr, *d_split_fc = nullptr, *d_split_row = nullptr,
-          *d_split_glob = nullptr, *d_split_mem_m = nullptr, *d_split_mem_hloc = nullptr, *d_split_info = nullptr;
-  double* d_split_terms = nullptr;
-  unsigned int* d_split_bar = nullptr;
-  // one cooperative launch, a workgroup per deal subtree of any size (k_cfr_sub)
-  bool sub_ok = false;
-  bool sub_br_ok = false;           // k_cfr_sub<., kBr> (the CFR-BR pass set) fits the same grid
-  bool sub_dcfr_ok = false;         // k_cfr_sub<., false, kDcfr> (Discounted CFR) fits the same grid
-  int sub_G = 0, sub_L = 0, sub_NL = 0, sub_K = 0, sub_grid = 0;
-  size_t sub_lds_bytes = 0;
-  int sub_ND = 0, sub_PL = 0;
-  int32_t *d_sub_ndec = nullptr, *d_sub_dec_row = nullptr, *d_sub_rec = nullptr;
-  int32_t *d_sub_nloc = nullptr, *d_sub_desc = nullptr, *d_sub_fc = nullptr, *d_sub_aux = nullptr, *d_sub_mem_off = nullptr,
-          *d_sub_info_off = nullptr, *d_sub_info_list = nullptr;
-  unsigned int* d_sub_bar = nullptr;
-  // forest form of k_cfr_sub (SubTree's comment): the kernel's own skip words, piece roots, upper members
-  bool sub_forest = false;
-  int sub_NR = 0, sub_G0 = 0;   // G0: the deal subtrees; sub_G: the bins they (or their pieces) were packed into
-  unsigned long long *d_sub_stamps = nullptr, *d_mccfr_stamps = nullptr;   // profiling stamps (per solver: never shared across contexts / devices)
-  double *d_sub_recbuf = nullptr, *d_sub_chance_prob = nullptr, *d_sub_term_val = nullptr;
-  int32_t *d_sub_dec_off = nullptr, *d_sub_fold_info = nullptr, *d_sub_fold_off = nullptr;
-  int sub_NCP = 0;
-  bool sub_keep_rows = false;
-  int32_t *d_sub_nroot = nullptr, *d_sub_root_loc = nullptr, *d_sub_root_idx = nullptr, *d_sub_upper_rec = nullptr;
-  double* d_sub_root_value = nullptr;
-  unsigned int* h_sub_err = nullptr;   // pinned: raised by the kernel when a grid barrier times out
-  // policy evaluation (k_policy_eval)
+  DeviceArray<unsigned long long> d_mccfr_stamps;   // profiling stamps of the MCCFR kernels, made at the first call that asks for them
+  PinnedArray<unsigned int> h_sub_err;   // mapped: raised by a kernel when a grid barrier times out
+  SplitPlan split;
+  SubPlan sub;
   std::vector<int32_t> info_level, mem_index;
   bool eval_ok = true;  // every infostate's members sit on one tree level
-  int32_t *d_info_level = nullptr, *d_mem_index = nullptr, *d_best = nullptr;
-  double *d_eval = nullptr;  // value [H,P] | brv [H] | cf [M] | out [2P] | policy [I,A]
-  double* d_eval_ev = nullptr;   // [H, P]: the expected returns of the large-tree evaluation (allocated on first use)
-  std::vector<int32_t> eval_level_off;   // [D + 1] the infostates of level l: d_eval_level_info[eval_level_off[l] ...)
-  int32_t* d_eval_level_info = nullptr;
-  int32_t* d_eval_level_off = nullptr;   // the same offsets on the device (k_geval_persist)
-  unsigned int* d_geval_bar = nullptr;   // its grid barrier's counters
-  int geval_grid = 0;                    // its resident grid (-1: none, a launch per level and phase instead)
+  EvalPlan eval;
   const char* last_eval_kernel = "";
-  // the evaluation as independent jobs over the device (k_eval_jobs)
-  bool jobs_ok = false;
-  int jobs_J = 0, jobs_L = 0, jobs_G = 0, jobs_NT = 0, jobs_threads = 0;
-  size_t jobs_lds_bytes = 0;
-  int32_t *d_jobs_job = nullptr, *d_jobs_level = nullptr, *d_jobs_desc = nullptr, *d_jobs_fc = nullptr, *d_jobs_row = nullptr,
-          *d_jobs_glob = nullptr, *d_jobs_info = nullptr, *d_jobs_mem = nullptr;
-  double* d_jobs_deal = nullptr;
-  unsigned int* d_jobs_ticket = nullptr;
-  double* h_eval_out = nullptr;  // pinned, mapped: the evaluation kernels write their [2 P] results here
-  // LDS-resident MCCFR traversal (k_mccfr_resident)
-  bool resident_ok = false;
-  size_t resident_lds_bytes = 0;
-  int n_uret = 0, n_uprob = 0, num_cus = 0;
-  uint64_t* d_rec = nullptr;
-  double *d_uret = nullptr, *d_uprob = nullptr;
+  JobsPlan jobs;
+  ResidentPlan resident;
+  int num_cus = 0;
   // per-infostate action values (osg_cfr_qvalues.hip): the results of a call, allocated at the first one
-  double* d_qv_out = nullptr;
-  int32_t* d_qv_best = nullptr;
+  DeviceArray<double> d_qv_out;
+  DeviceArray<int32_t> d_qv_best;
   // magnetic mirror descent (osg_cfr_mmd.hip): built at the first osg_mmd_* call
-  MmdState* mmd = nullptr;
+  std::unique_ptr<MmdState> mmd;
 
   Tree tree() const {
     Tree t;
@@ -514,6 +530,55 @@ struct osg_cfr {
 };
 
 namespace osg_cfr_impl {
+// ---------------------------------------------------------------------------
+// The kernels' views of the solver, each formed in one place.
+// ---------------------------------------------------------------------------
+// The block size of the one-workgroup kernels that sweep the tree level by level: the widest level, in whole waves.
+inline int level_threads(const osg_cfr* s) { return std::max(64, std::min(((s->max_level_width + 63) / 64) * 64, 1024)); }
+
+inline SmallTree small_tree_of(const osg_cfr* s) {   // (L0 is set by the one kernel that reads it: cfr_small_iterate)
+  return SmallTree{s->d_path_off, s->d_path, static_cast<int>(s->mem.size()), static_cast<int>(s->path.size())};
+}
+
+inline SplitTree split_tree_of(const osg_cfr* s) {
+  const SplitPlan& p = s->split;
+  return SplitTree{p.G, p.L, p.NL, p.NM, p.NI, p.nloc, p.desc, p.fc, p.row, p.glob, p.mem_m, p.mem_hloc, p.info,
+                   p.terms, p.bar, s->h_sub_err};
+}
+
+// The evaluation's scratch, EvalPlan::scratch: value [H, P] | brv [H] | cf [M] | out [2 P] | policy [I, A].  `out` is the
+// device slot (CFR-BR, XFP); the evaluation proper points it at the pinned result words instead.
+inline EvalArrays eval_arrays_of(const osg_cfr* s) {
+  const size_t M = s->mem.size();
+  EvalArrays ea;
+  ea.path_off = s->d_path_off; ea.path = s->d_path; ea.info_level = s->eval.info_level; ea.mem_index = s->eval.mem_index;
+  ea.M = static_cast<int>(M);
+  ea.value = s->eval.scratch;
+  ea.brv = ea.value + static_cast<size_t>(s->H) * s->P;
+  ea.cf = ea.brv + s->H;
+  ea.out = ea.cf + M;
+  ea.best = s->eval.best;
+  return ea;
+}
+inline double* eval_policy_slot(const osg_cfr* s) { return eval_arrays_of(s).out + 2 * s->P; }
+inline size_t eval_scratch_doubles(const osg_cfr* s) {
+  return static_cast<size_t>(s->H) * (s->P + 1) + s->mem.size() + 2 * s->P + static_cast<size_t>(s->I) * s->A;
+}
+
+// d_reach ([H, P + 1] doubles) is the CFR kernels' own between their launches only; outside them three callers borrow
+// it as scratch.  Each states what it needs of the buffer here, next to the others:
+//   fictitious play: avg reach [I] | best-response reach [I]        2 I <= H (P + 1): checked, the call is refused
+//   action values:   the members' reaches [M, P + 1]                M <= H: holds always (a member is a history)
+//   evaluation:      the responder's value of every history [H]     H <= H (P + 1): holds always
+inline int xfp_reach_in_reach(const osg_cfr* s, const std::string& who, double** out) {
+  if (2 * static_cast<size_t>(s->I) > static_cast<size_t>(s->H) * (s->P + 1))
+    return set_error(OSG_ERR_UNSUPPORTED, who + ": more information states than the reach buffer holds");
+  *out = s->d_reach;
+  return OSG_OK;
+}
+inline double* member_reach_in_reach(const osg_cfr* s) { return s->d_reach; }
+inline double* history_values_in_reach(const osg_cfr* s) { return s->d_reach; }
+
 // ---- osg_cfr.hip ----
 int cfr_sub_error(const osg_cfr* s);   // a grid barrier timed out in an earlier launch: the solver refuses further work
 void discount_factors(double alpha, double beta, double gamma, int iteration, double out[3]);
@@ -521,14 +586,15 @@ void discount_factors(double alpha, double beta, double gamma, int iteration, do
 int cfr_discount_table(osg_cfr* s, int iteration0, int iters, const double** d_table);
 // ---- osg_cfr_small.hip ----
 void cfr_small_prepare(osg_cfr* s);    // LDS caps of k_cfr<true> / k_cfr_small (clears lds_resident / small_tree where refused)
-int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, int threads, unsigned grid_b);   // k_cfr_small / k_cfr
-void cfr_general_br_pass(osg_cfr* s, Tables tb, int threads, osg_cfr_cfg cfg);           // k_cfr<false, kBr> x 1
+int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, unsigned grid_b);   // k_cfr_small / k_cfr
+void cfr_general_br_pass(osg_cfr* s, Tables tb, osg_cfr_cfg cfg);           // k_cfr<false, kBr> x 1
 // ---- osg_cfr_split.hip ----
 int build_split(osg_cfr* s);
 int launch_split(osg_cfr* s, SmallTree stree, SplitTree sp, Tables tb, int iters, int iteration0, osg_cfr_cfg cfg, bool br,
                  const double* disc = nullptr);
 // ---- osg_cfr_sub.hip ----
 int build_sub(osg_cfr* s);
+SubTree sub_tree_of(const osg_cfr* s);   // reads the OSG_CFR_SUB_* switches, at every call
 int cfr_sub_iterate(osg_cfr* s, Tables tb, int iters);      // k_cfr_sub
 int cfr_grid_iterate(osg_cfr* s, Tables tb, int iters);     // k_gcfr_*
 int cfr_grid_br_iterate(osg_cfr* s, Tables tb, const EvalArrays& ea, osg_cfr_cfg cfg, int iters);   // CFR-BR on large trees, a launch per phase
@@ -538,12 +604,11 @@ int build_eval_jobs(osg_cfr* s);
 EvalJobs eval_jobs_of(const osg_cfr* s);
 bool eval_takes_the_grid(const osg_cfr* s);
 bool OSG_EVAL_JOBS_ENABLED();
-int launch_grid_eval(const osg_cfr* s, const EvalArrays& ea, const double* src, bool from_cum, double* d_pol, bool only_br);
-int cfr_best_responses_to_current(osg_cfr* s, const EvalArrays& ea, int threads, bool jobs);   // every player's best response (CFR-BR)
+int launch_grid_eval(osg_cfr* s, const EvalArrays& ea, const double* src, bool from_cum, double* d_pol, bool only_br);
+int cfr_best_responses_to_current(osg_cfr* s, const EvalArrays& ea, bool jobs);   // every player's best response (CFR-BR)
 // ---- osg_cfr_mccfr.hip ----
 int build_resident_tree(osg_cfr* s);
 // ---- osg_cfr_mmd.hip ----
 bool mmd_mode(const osg_cfr* s);       // osg_mmd_set_params was accepted: pi and avg_x live in the cur and cum tables
 int mmd_after_reset(osg_cfr* s);       // avg_x = x of the fresh uniform policy
-void mmd_destroy(osg_cfr* s);
 }  // namespace osg_cfr_impl

@@ -958,7 +958,7 @@ namespace osg_cfr_impl {
 // Packs the tree for k_mccfr_resident (8 bytes per history + the distinct return vectors and chance
 // probabilities) and decides whether it fits one workgroup's LDS next to three [I, A] tables.
 int build_resident_tree(osg_cfr* s) {
-  s->resident_ok = false;
+  s->resident.ok = false;
   if ((s->cfg.solver != 1 && s->cfg.solver != 2) || s->A < 1 || s->A > kMaxA) return OSG_OK;
   if (s->H >= (1 << 24) || s->I >= (1 << 20)) return OSG_OK;
   std::vector<uint64_t> rec(s->H);
@@ -1020,19 +1020,19 @@ int build_resident_tree(osg_cfr* s) {
     if (same) rec[h] |= static_cast<uint64_t>(id0 + 1) << 12;
   }
   if (uprob.empty()) uprob.push_back(1.0);
-  s->n_uret = static_cast<int>(uret.size() / std::max(P, 1));
-  s->n_uprob = static_cast<int>(uprob.size());
+  s->resident.n_uret = static_cast<int>(uret.size() / std::max(P, 1));
+  s->resident.n_uprob = static_cast<int>(uprob.size());
   const size_t IA = static_cast<size_t>(s->I) * s->A;
-  s->resident_lds_bytes = sizeof(double) * (3 * IA + uret.size() + uprob.size()) + sizeof(uint64_t) * s->H;
+  s->resident.lds_bytes = sizeof(double) * (3 * IA + uret.size() + uprob.size()) + sizeof(uint64_t) * s->H;
   hipDeviceProp_t prop;
   OSG_HIP(hipGetDeviceProperties(&prop, s->ctx->device));
   s->num_cus = prop.multiProcessorCount;
-  if (s->resident_lds_bytes > static_cast<size_t>(prop.sharedMemPerBlockOptin ? prop.sharedMemPerBlockOptin
+  if (s->resident.lds_bytes > static_cast<size_t>(prop.sharedMemPerBlockOptin ? prop.sharedMemPerBlockOptin
                                                                               : prop.sharedMemPerBlock))
     return OSG_OK;
   hipStream_t st = s->ctx->stream;
   int rc;
-  if ((rc = upload(rec, &s->d_rec, st)) || (rc = upload(uret, &s->d_uret, st)) || (rc = upload(uprob, &s->d_uprob, st)))
+  if ((rc = upload(rec, s->resident.rec, st)) || (rc = upload(uret, s->resident.uret, st)) || (rc = upload(uprob, s->resident.uprob, st)))
     return rc;
   const void* variants[] = {reinterpret_cast<const void*>(&k_mccfr_resident_flat<1>),
                             reinterpret_cast<const void*>(&k_mccfr_resident_flat<2>),
@@ -1042,7 +1042,7 @@ int build_resident_tree(osg_cfr* s) {
                             reinterpret_cast<const void*>(&k_os_mccfr_resident<2>),
                             reinterpret_cast<const void*>(&k_os_mccfr_resident<3>),
                             reinterpret_cast<const void*>(&k_os_mccfr_resident<4>)};
-  if (raise_lds_cap(variants[(s->cfg.solver == 2 ? 4 : 0) + s->A - 1], static_cast<int>(s->resident_lds_bytes)) != hipSuccess) {
+  if (raise_lds_cap(variants[(s->cfg.solver == 2 ? 4 : 0) + s->A - 1], static_cast<int>(s->resident.lds_bytes)) != hipSuccess) {
     (void)hipGetLastError();
     return OSG_OK;
   }
@@ -1054,11 +1054,11 @@ int build_resident_tree(osg_cfr* s) {
                                   reinterpret_cast<const void*>(&k_mccfr_resident<4, 2>)};
   for (int level = 0; level < 2; ++level)
     if (s->cfg.solver != 2 && s->A >= 2 &&
-        raise_lds_cap(split_variants[2 * (s->A - 1) + level], static_cast<int>(s->resident_lds_bytes)) != hipSuccess) {
+        raise_lds_cap(split_variants[2 * (s->A - 1) + level], static_cast<int>(s->resident.lds_bytes)) != hipSuccess) {
       (void)hipGetLastError();
       return OSG_OK;
     }
-  s->resident_ok = true;
+  s->resident.ok = true;
   return OSG_OK;
 }
 
@@ -1094,11 +1094,11 @@ static int mccfr_sample_impl(osg_cfr* s, uint64_t seed, int64_t first_trajectory
   // Persistent workgroups: each flushes its LDS delta tables once, so fewer, longer-lived
   // groups mean fewer global atomics (256 CUs x 4 groups).
   if (blocks > 1024) blocks = 1024;
-  if (s->resident_ok && s->cfg.kernel != 1) {
+  if (s->resident.ok && s->cfg.kernel != 1) {
     // As many workgroups per CU as the LDS footprint allows.  A footprint that only fits once (leduc:
     // 143 KB) gets one group per CU, sized to the batch — every CU busy, up to 1024 lanes each; small
     // footprints (kuhn) get several 256- or 1024-lane groups per CU.
-    int fit = static_cast<int>((160 * 1024) / std::max<size_t>(s->resident_lds_bytes, 1));
+    int fit = static_cast<int>((160 * 1024) / std::max<size_t>(s->resident.lds_bytes, 1));
     // Mini-batches that leave lanes idle (fewer lanes than one round of the chip even with the split) run the
     // split form of the external-sampling kernel: 2 or 4 lanes per trajectory (OSG_MCCFR_SPLIT=0: never).
     // OSG_MCCFR_SPLIT=0 / 1 / 2: at most that many traverser levels are spread over lanes (default 2)
@@ -1116,11 +1116,11 @@ static int mccfr_sample_impl(osg_cfr* s, uint64_t seed, int64_t first_trajectory
     // Where the flat kernel reads the tree from: when the staged problem allows one workgroup per CU only (leduc: 143 KB,
     // 4 wavefronts per SIMD) but the tables alone would allow two (67 KB), the records can stay in global memory
     // (9 457 x 8 B, read-only: L2-resident) and two 1024-lane workgroups share a CU.  OSG_MCCFR_TREE=global | lds.
-    size_t shmem_bytes = s->resident_lds_bytes;
+    size_t shmem_bytes = s->resident.lds_bytes;
     int tree_global = 0;
     {
       static const char* where = std::getenv("OSG_MCCFR_TREE");
-      const size_t tables_only = s->resident_lds_bytes - sizeof(uint64_t) * s->H;
+      const size_t tables_only = s->resident.lds_bytes - sizeof(uint64_t) * s->H;
       const bool helps = fit <= 1 && (160 * 1024) / std::max<size_t>(tables_only, 1) >= 2 &&
                          trajectories >= static_cast<int64_t>(s->num_cus) * 2048;
       const bool want = where ? std::strcmp(where, "global") == 0 : kMccfrTreeGlobalDefault;
@@ -1140,10 +1140,10 @@ static int mccfr_sample_impl(osg_cfr* s, uint64_t seed, int64_t first_trajectory
       per_cu = std::max(1, std::min(fit, 2048 / threads));
     }
     int64_t groups = std::min<int64_t>((trajectories + threads - 1) / threads, static_cast<int64_t>(s->num_cus) * per_cu);
-    ResidentTree rt{reinterpret_cast<const uint2*>(s->d_rec), s->d_uret, s->d_uprob, s->n_uret, s->n_uprob, tree_global};
-    unsigned long long*& d_stamps = s->d_mccfr_stamps;   // OSG_MCCFR_STAMPS=1: phase stamps of workgroup 0 (tools/probe_mccfr_shard.py); the solver's own buffer
-    if (std::getenv("OSG_MCCFR_STAMPS") && !d_stamps)
-      OSG_HIP(hipMalloc(reinterpret_cast<void**>(&d_stamps), sizeof(unsigned long long) * 4));
+    ResidentTree rt{reinterpret_cast<const uint2*>(s->resident.rec.get()), s->resident.uret, s->resident.uprob, s->resident.n_uret, s->resident.n_uprob, tree_global};
+    // OSG_MCCFR_STAMPS=1: phase stamps of workgroup 0 (tools/probe_mccfr_shard.py); the solver's own buffer
+    if (std::getenv("OSG_MCCFR_STAMPS") && !s->d_mccfr_stamps) OSG_HIP(s->d_mccfr_stamps.alloc(4));
+    unsigned long long* const d_stamps = s->d_mccfr_stamps;
     const dim3 grid(static_cast<unsigned>(groups)), block(threads);
     const size_t shmem = shmem_bytes;
     with_int<1, 2, 3, 4>(s->A, [&](auto ka) {
@@ -1247,9 +1247,9 @@ int osg_mccfr_apply_deltas(osg_cfr* s) {
 int osg_mccfr_spare_delta_buffer(osg_cfr* s, int which, double** d_delta) {
   if (!s || !d_delta || (which != 0 && which != 1)) return set_error(OSG_ERR_INVALID, "osg_mccfr_spare_delta_buffer: bad argument");
   if (!s->d_spare_delta[which]) {
-    const size_t bytes = sizeof(double) * 2 * static_cast<size_t>(s->I) * s->A;
+    const size_t n = 2 * static_cast<size_t>(s->I) * s->A, bytes = sizeof(double) * n;
     OSG_HIP(hipSetDevice(s->ctx->device));
-    OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_spare_delta[which]), bytes));
+    OSG_HIP(s->d_spare_delta[which].alloc(n));
     OSG_HIP(hipMemsetAsync(s->d_spare_delta[which], 0, bytes, s->ctx->stream));
   }
   *d_delta = s->d_spare_delta[which];
@@ -1303,9 +1303,7 @@ int osg_mccfr_full_average(osg_cfr* s, double weight) {
   if (s->B != 1) return set_error(OSG_ERR_UNSUPPORTED, "osg_mccfr_full_average: one solver per object");
   if (s->A > kMaxPolicyRow) return set_error(OSG_ERR_UNSUPPORTED, "osg_mccfr_full_average: policy rows wider than 8 actions");
   if (!(weight > 0.0)) return set_error(OSG_ERR_INVALID, "osg_mccfr_full_average: weight must be positive");
-  int threads = ((s->max_level_width + 63) / 64) * 64;
-  threads = std::max(64, std::min(threads, 1024));
-  k_mccfr_full_average<<<dim3(1), dim3(threads), 0, s->ctx->stream>>>(s->tree(), s->regrets(), s->cum(), s->d_reach, weight);
+  k_mccfr_full_average<<<dim3(1), dim3(level_threads(s)), 0, s->ctx->stream>>>(s->tree(), s->regrets(), s->cum(), s->d_reach, weight);
   OSG_HIP(hipGetLastError());
   return OSG_OK;
 }

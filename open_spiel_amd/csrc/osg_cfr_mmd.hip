@@ -22,16 +22,19 @@ struct MmdState {
   std::vector<double> term_cu;
   int L = 0, max_level = 0;
   double max_abs_payoff = 0.0;
-  int32_t *d_lvl_off = nullptr, *d_lvl_info = nullptr, *d_own_off = nullptr, *d_own = nullptr, *d_child_off = nullptr,
-          *d_child = nullptr, *d_term_off = nullptr, *d_term_opp = nullptr;
-  double* d_term_cu = nullptr;
-  double* d_work = nullptr;   // x [IA] | dot [I] | neg_ent [I] | pi_br [IA] | x_br [IA] | part_a [IA + 1] | part_b [IA + 1] | dgf [I] | dgf_br [I] | gap [1]
-  double* d_par = nullptr;    // [B, 2] alpha, stepsize of every replica
+  DeviceArray<int32_t> d_lvl_off, d_lvl_info, d_own_off, d_own, d_child_off, d_child, d_term_off, d_term_opp;
+  DeviceArray<double> d_term_cu;
+  DeviceArray<double> d_work;   // x [IA] | dot [I] | neg_ent [I] | pi_br [IA] | x_br [IA] | part_a [IA + 1] | part_b [IA + 1] | dgf [I] | dgf_br [I] | gap [1]
+  DeviceArray<double> d_par;    // [B, 2] alpha, stepsize of every replica
   std::vector<double> par;    // the same on the host
   bool active = false;        // osg_mmd_set_params was accepted: the solver is in MMD mode
 };
 
 }  // namespace osg_cfr_impl
+
+// (here, where MmdState is complete, for the unique_ptr that holds it)
+osg_cfr::osg_cfr() = default;
+osg_cfr::~osg_cfr() = default;
 
 namespace {
 
@@ -170,7 +173,8 @@ k_mmd_gap(MmdTree t, const int8_t* __restrict__ player, const double* __restrict
 // build_tree keeps.  Once per solver, at the first MMD call.
 int mmd_build(osg_cfr* s) {
   if (s->mmd) return OSG_OK;
-  MmdState* m = new MmdState;
+  auto built = std::make_unique<MmdState>();
+  MmdState* m = built.get();
   const int I = s->I, A = s->A, IA = I * A;
   std::vector<int32_t> parent_cell(I, -1);
   m->own_off.push_back(0);
@@ -239,24 +243,24 @@ int mmd_build(osg_cfr* s) {
       m->term_opp[at] = t.bucket[1 - p] >= IA ? -1 : t.bucket[1 - p];
       m->term_cu[at] = t.cu[p];
     }
-  s->mmd = m;   // (from here on osg_cfr_destroy frees what was allocated)
   hipStream_t st = s->ctx->stream;
   int rc;
-  if ((rc = upload(m->lvl_off, &m->d_lvl_off, st)) || (rc = upload(m->lvl_info, &m->d_lvl_info, st)) ||
-      (rc = upload(m->own_off, &m->d_own_off, st)) || (rc = upload(m->own, &m->d_own, st)) ||
-      (rc = upload(m->child_off, &m->d_child_off, st)) || (rc = upload(m->child, &m->d_child, st)) ||
-      (rc = upload(m->term_off, &m->d_term_off, st)) || (rc = upload(m->term_opp, &m->d_term_opp, st)) ||
-      (rc = upload(m->term_cu, &m->d_term_cu, st)))
+  if ((rc = upload(m->lvl_off, m->d_lvl_off, st)) || (rc = upload(m->lvl_info, m->d_lvl_info, st)) ||
+      (rc = upload(m->own_off, m->d_own_off, st)) || (rc = upload(m->own, m->d_own, st)) ||
+      (rc = upload(m->child_off, m->d_child_off, st)) || (rc = upload(m->child, m->d_child, st)) ||
+      (rc = upload(m->term_off, m->d_term_off, st)) || (rc = upload(m->term_opp, m->d_term_opp, st)) ||
+      (rc = upload(m->term_cu, m->d_term_cu, st)))
     return rc;
-  OSG_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_work), sizeof(double) * mmd_work_doubles(I, A)));
-  OSG_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_par), sizeof(double) * 2 * s->B));
+  OSG_HIP(m->d_work.alloc(mmd_work_doubles(I, A)));
+  OSG_HIP(m->d_par.alloc(2 * static_cast<size_t>(s->B)));
   OSG_HIP(hipMemsetAsync(m->d_work, 0, sizeof(double) * mmd_work_doubles(I, A), st));   // (the padding cells stay 0)
   OSG_HIP(hipStreamSynchronize(st));
+  s->mmd = std::move(built);   // (whole, or not there: a failed build leaves nothing behind)
   return OSG_OK;
 }
 
 MmdTree mmd_tree(const osg_cfr* s) {
-  const MmdState* m = s->mmd;
+  const MmdState* m = s->mmd.get();
   MmdTree t;
   t.I = s->I; t.A = s->A; t.L = m->L;
   t.nact = s->d_nact; t.lvl_off = m->d_lvl_off; t.lvl_info = m->d_lvl_info; t.own_off = m->d_own_off; t.own = m->d_own;
@@ -294,17 +298,6 @@ int mmd_start_average(osg_cfr* s) {
 
 namespace osg_cfr_impl {
 
-void mmd_destroy(osg_cfr* s) {
-  MmdState* m = s->mmd;
-  if (!m) return;
-  void* ptrs[] = {m->d_lvl_off, m->d_lvl_info, m->d_own_off, m->d_own, m->d_child_off, m->d_child, m->d_term_off, m->d_term_opp,
-                  m->d_term_cu, m->d_work, m->d_par};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  delete m;
-  s->mmd = nullptr;
-}
-
 bool mmd_mode(const osg_cfr* s) { return s->mmd && s->mmd->active; }
 
 int mmd_after_reset(osg_cfr* s) { return mmd_start_average(s); }
@@ -334,7 +327,7 @@ int osg_mmd_set_params(osg_cfr* s, int n, const double* alpha, const double* ste
       return set_error(OSG_ERR_INVALID, "osg_mmd_set_params: the stepsize must be finite and >= 0 (replica " + std::to_string(r) + ")");
   }
   if (int rc = mmd_build(s)) return rc;
-  MmdState* m = s->mmd;
+  MmdState* m = s->mmd.get();
   hipStream_t st = s->ctx->stream;
   OSG_HIP(hipStreamSynchronize(st));   // (an earlier launch may still read d_par)
   m->par.resize(2 * static_cast<size_t>(n));
@@ -357,7 +350,7 @@ int osg_mmd_iterate(osg_cfr* s, int iters) {
   if (int rc = mmd_refusal(s, "osg_mmd_iterate")) return rc;
   if (!mmd_mode(s)) return set_error(OSG_ERR_INVALID, "osg_mmd_iterate: no parameters yet (osg_mmd_set_params comes first)");
   if (iters == 0) return OSG_OK;
-  const MmdState* m = s->mmd;
+  const MmdState* m = s->mmd.get();
   hipStream_t st = s->ctx->stream;
   const MmdTree t = mmd_tree(s);
   if (mmd_takes_the_resident_form(s)) {
@@ -391,7 +384,7 @@ int osg_mmd_gap(osg_cfr* s, double* out) {
   if (!s || !out) return set_error(OSG_ERR_INVALID, "osg_mmd_gap: null argument");
   if (int rc = mmd_refusal(s, "osg_mmd_gap")) return rc;
   if (!mmd_mode(s)) return set_error(OSG_ERR_INVALID, "osg_mmd_gap: no parameters yet (osg_mmd_set_params comes first)");
-  const MmdState* m = s->mmd;
+  const MmdState* m = s->mmd.get();
   const double alpha = m->par[2 * static_cast<size_t>(s->selected)];
   if (!(alpha > 0.0)) return set_error(OSG_ERR_INVALID, "osg_mmd_gap: the gap cannot be computed for alpha = 0 (mmd_dilated.py:333)");
   hipStream_t st = s->ctx->stream;

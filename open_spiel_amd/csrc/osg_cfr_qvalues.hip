@@ -179,12 +179,9 @@ int osg_cfr_action_values(osg_cfr* s, int which_policy, const double* policy, in
   hipStream_t st = s->ctx->stream;
   const int P = s->P;
   const size_t I = s->I, IA = I * s->A, M = s->mem.size();
-  if (!s->d_qv_out) {
-    OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_qv_out), sizeof(double) * qv_out_doubles(s)));
-    OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_qv_best), sizeof(int32_t) * std::max<size_t>(I, 1)));
-  }
-  // the evaluation's scratch: value [H, P] | brv [H] | cf [M] | out [2 P] | policy [I, A] (evaluate_policy_impl's layout)
-  double* d_pol = s->d_eval + static_cast<size_t>(s->H) * (P + 1) + M + 2 * P;
+  if (!s->d_qv_out) OSG_HIP(s->d_qv_out.alloc(qv_out_doubles(s)));
+  if (!s->d_qv_best) OSG_HIP(s->d_qv_best.alloc(I));
+  double* d_pol = eval_policy_slot(s);
   double brv = 0.0;
   if (responder >= 0) {
     // the existing best-response evaluation first: it leaves the argmax of every infostate in d_best
@@ -208,11 +205,11 @@ int osg_cfr_action_values(osg_cfr* s, int which_policy, const double* policy, in
   }
   c.responder = responder;
   c.brv = brv;
-  c.best = s->d_best;
+  c.best = s->eval.best;
   c.path_off = s->d_path_off; c.path = s->d_path; c.M = static_cast<int>(M);
   c.sigma = d_pol;
-  c.rm = s->d_reach;       // [H, P + 1] doubles, free between CFR launches: M <= H
-  c.value = s->d_eval;
+  c.rm = member_reach_in_reach(s);
+  c.value = s->eval.scratch;
   double* o = s->d_qv_out;
   c.root = o;
   c.best_out = s->d_qv_best;
@@ -234,8 +231,7 @@ int osg_cfr_action_values(osg_cfr* s, int which_policy, const double* policy, in
       (void)hipGetLastError();
       lds = 0;
     }
-    const int threads = std::max(64, std::min(((s->max_level_width + 63) / 64) * 64, 1024));
-    k_qvalues_small<<<dim3(1), dim3(threads), lds, st>>>(t, c, lds > 0 ? 1 : 0);
+    k_qvalues_small<<<dim3(1), dim3(level_threads(s)), lds, st>>>(t, c, lds > 0 ? 1 : 0);
     s->last_eval_kernel = "k_qvalues_small";
   }
   OSG_HIP(hipGetLastError());

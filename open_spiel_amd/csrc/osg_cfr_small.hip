@@ -557,15 +557,15 @@ void cfr_small_prepare(osg_cfr* s) {
 
 // The one-workgroup kernels (osg_cfr_iterate's last branch): the path-based kernel, all-in-LDS when the tree is small
 // enough, else the general kernel.
-int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, int threads, unsigned grid_b) {
+int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, unsigned grid_b) {
+  const int threads = level_threads(s);
   const double* disc = nullptr;
   if (int rc = cfr_discount_table(s, s->iteration, iters, &disc)) return rc;
   if (s->path_kernel && s->cfg.kernel != 1) {
     // Path-based kernel: no top-down reach pass; all-in-LDS when the tree is small enough.
-    const int M = static_cast<int>(s->mem.size());
-    SmallTree st{s->d_path_off, s->d_path, M, static_cast<int>(s->path.size())};
+    SmallTree st = small_tree_of(s);
     st.L0 = s->first_decision_level;
-    SmallGlobal sg{s->d_value, s->d_node_delta, s->d_node_delta + static_cast<size_t>(M) * s->A, s->d_skip,
+    SmallGlobal sg{s->d_value, s->d_node_delta, s->d_node_delta + static_cast<size_t>(st.M) * s->A, s->d_skip,
                    s->d_meta32, s->d_info_player32};
     const auto small = [&](auto lds, auto owner, int block, size_t shmem) {   // the reach block: 3, 4 or all players + 1
       with_int<3, 4, kMaxPlayers + 1>(s->P + 1, [&](auto p1) {
@@ -618,9 +618,9 @@ int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, int threads, unsigned gr
   return OSG_OK;
 }
 
-void cfr_general_br_pass(osg_cfr* s, Tables tb, int threads, osg_cfr_cfg cfg) {
-  k_cfr<false, true><<<dim3(1), dim3(threads), 0, s->ctx->stream>>>(s->tree(), tb, s->d_reach, s->d_value, 1, s->iteration, cfg,
-                                                                    s->d_best);
+void cfr_general_br_pass(osg_cfr* s, Tables tb, osg_cfr_cfg cfg) {
+  k_cfr<false, true><<<dim3(1), dim3(level_threads(s)), 0, s->ctx->stream>>>(s->tree(), tb, s->d_reach, s->d_value, 1, s->iteration, cfg,
+                                                                    s->eval.best);
 }
 
 }  // namespace osg_cfr_impl

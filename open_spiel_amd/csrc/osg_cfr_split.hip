@@ -331,7 +331,7 @@ namespace osg_cfr_impl {
 // Cuts the tree below its leading chance levels into subtrees for k_cfr_split: one workgroup each, at most one
 // per CU, every subtree small enough for one thread per history.
 int build_split(osg_cfr* s) {
-  s->split_ok = false;
+  s->split.ok = false;
   if (s->cfg.solver != 0 || s->B != 1 || !s->path_kernel || s->A > kSplitMaxA || s->P + 1 > kMaxPlayers + 1) return OSG_OK;
   if (s->H < 2000 || s->D >= 64) return OSG_OK;
   // the cut: the first level that holds a node which is not a chance node
@@ -409,16 +409,16 @@ int build_split(osg_cfr* s) {
   }
   hipStream_t st = s->ctx->stream;
   int rc;
-  if ((rc = upload(nloc, &s->d_split_nloc, st)) || (rc = upload(desc, &s->d_split_desc, st)) ||
-      (rc = upload(fc, &s->d_split_fc, st)) || (rc = upload(row, &s->d_split_row, st)) ||
-      (rc = upload(glob, &s->d_split_glob, st)) || (rc = upload(mm, &s->d_split_mem_m, st)) ||
-      (rc = upload(mh, &s->d_split_mem_hloc, st)) || (rc = upload(il, &s->d_split_info, st)))
+  if ((rc = upload(nloc, s->split.nloc, st)) || (rc = upload(desc, s->split.desc, st)) ||
+      (rc = upload(fc, s->split.fc, st)) || (rc = upload(row, s->split.row, st)) ||
+      (rc = upload(glob, s->split.glob, st)) || (rc = upload(mm, s->split.mem_m, st)) ||
+      (rc = upload(mh, s->split.mem_hloc, st)) || (rc = upload(il, s->split.info, st)))
     return rc;
   const size_t M = s->mem.size();
-  OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_split_terms), sizeof(double) * 2 * kSplitRec * std::max<size_t>(M, 1)));
-  OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_split_bar), sizeof(unsigned int) * 4));
-  OSG_HIP(hipMemsetAsync(s->d_split_bar, 0, sizeof(unsigned int) * 4, st));
-  OSG_HIP(hipMemsetAsync(s->d_split_terms, 0, sizeof(double) * 2 * kSplitRec * std::max<size_t>(M, 1), st));
+  OSG_HIP(s->split.terms.alloc(2 * kSplitRec * std::max<size_t>(M, 1)));
+  OSG_HIP(s->split.bar.alloc(4));
+  OSG_HIP(hipMemsetAsync(s->split.bar, 0, sizeof(unsigned int) * 4, st));
+  OSG_HIP(hipMemsetAsync(s->split.terms, 0, sizeof(double) * 2 * kSplitRec * std::max<size_t>(M, 1), st));
   if (raise_lds_cap(split_kernel(s->P, false, threads), static_cast<int>(lds)) != hipSuccess ||
       raise_lds_cap(split_kernel(s->P, false, threads, s->A, true), static_cast<int>(lds)) != hipSuccess ||
       raise_lds_cap(split_kernel(s->P, false, threads, 0, false, true), static_cast<int>(lds)) != hipSuccess ||
@@ -427,15 +427,15 @@ int build_split(osg_cfr* s) {
     return OSG_OK;
   }
   // the CFR-BR pass set keeps one more [I, A] array (the effective policy)
-  s->split_br_ok = lds + sizeof(double) * IA <= 158 * 1024;
-  if (s->split_br_ok && (raise_lds_cap(split_kernel(s->P, true, threads), static_cast<int>(lds + sizeof(double) * IA)) != hipSuccess ||
+  s->split.br_ok = lds + sizeof(double) * IA <= 158 * 1024;
+  if (s->split.br_ok && (raise_lds_cap(split_kernel(s->P, true, threads), static_cast<int>(lds + sizeof(double) * IA)) != hipSuccess ||
                          raise_lds_cap(split_kernel(s->P, true, threads, s->A, true), static_cast<int>(lds + sizeof(double) * IA)) != hipSuccess)) {
     (void)hipGetLastError();
-    s->split_br_ok = false;
+    s->split.br_ok = false;
   }
-  s->split_G = G; s->split_L = L; s->split_NL = NL; s->split_NM = NM; s->split_NI = NI; s->split_threads = threads;
-  s->split_lds_bytes = lds;
-  s->split_ok = true;
+  s->split.G = G; s->split.L = L; s->split.NL = NL; s->split.NM = NM; s->split.NI = NI; s->split.threads = threads;
+  s->split.lds_bytes = lds;
+  s->split.ok = true;
   return OSG_OK;
 }
 
@@ -448,12 +448,12 @@ int launch_split(osg_cfr* s, SmallTree stree, SplitTree sp, Tables tb, int iters
   hipStream_t st = s->ctx->stream;
   // (the barrier's counters are zero: build_split zeroed them and every launch leaves them so; a launch that timed out
   // does not — and makes the solver unusable, cfr_sub_error)
-  const dim3 grid(static_cast<unsigned>(s->split_G)), block(static_cast<unsigned>(s->split_threads));
+  const dim3 grid(static_cast<unsigned>(s->split.G)), block(static_cast<unsigned>(s->split.threads));
   Tree tr = s->tree();
-  const int32_t* best = br ? s->d_best : nullptr;
+  const int32_t* best = br ? s->eval.best : nullptr;
   void* args[] = {&tr, &stree, &sp, &tb, &iters, &iteration0, &cfg, &best, &disc};
-  const void* kern = split_kernel(s->P, br, s->split_threads, s->A, br || cfg.alternating_updates, disc != nullptr);
-  const size_t lds = s->split_lds_bytes + (br ? sizeof(double) * static_cast<size_t>(s->I) * s->A : 0);
+  const void* kern = split_kernel(s->P, br, s->split.threads, s->A, br || cfg.alternating_updates, disc != nullptr);
+  const size_t lds = s->split.lds_bytes + (br ? sizeof(double) * static_cast<size_t>(s->I) * s->A : 0);
   // OSG_CFR_PLAIN_LAUNCH=1: an ordinary launch, for hosts that run the solver alone on the device — the cooperative
   // launch costs 20 us per call (47.6 vs 27.6 us per one-iteration launch, CFR-BR 1.30e4 vs 1.82e4 it/s), which only the
   // calling pattern "one iteration per call" notices; without it the grid is resident together only as long as nothing

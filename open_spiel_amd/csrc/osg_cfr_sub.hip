@@ -737,7 +737,7 @@ const void* cfr_sub_kernel_of(int K, bool br, bool dcfr = false) {
   return K == 2 ? cfr_sub_kernel<2>() : (K == 4 ? cfr_sub_kernel<4>() : cfr_sub_kernel<8>());
 }
 int build_sub(osg_cfr* s) {
-  s->sub_ok = false;
+  s->sub.ok = false;
   if (s->cfg.solver != 0 || s->B != 1 || !s->path_kernel || s->A > kSplitMaxA || !s->cfg.alternating_updates) return OSG_OK;
   if (s->H < 4096 || s->D >= 63 || s->H >= (1 << 23)) return OSG_OK;
   int L = 0;
@@ -1025,20 +1025,20 @@ int build_sub(osg_cfr* s) {
     return OSG_OK;
   }
   // the CFR-BR form of the same kernel: taken when it can be resident on the same grid (else CFR-BR keeps the launches per phase)
-  s->sub_br_ok = false;
+  s->sub.br_ok = false;
   if (raise_lds_cap(cfr_sub_kernel_of(K, true), static_cast<int>(lds)) == hipSuccess) {
     int per_cu_br = 0;
     hipError_t eb;
     if (K == 2) eb = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_br, k_cfr_sub<2, true>, kSubThreads, lds);
     else if (K == 4) eb = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_br, k_cfr_sub<4, true>, kSubThreads, lds);
     else eb = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_br, k_cfr_sub<8, true>, kSubThreads, lds);
-    if (eb == hipSuccess) s->sub_br_ok = per_cu_br >= 1;
+    if (eb == hipSuccess) s->sub.br_ok = per_cu_br >= 1;
     else (void)hipGetLastError();
   } else {
     (void)hipGetLastError();
   }
   // the discounting form likewise (else a discounting solver keeps the launches per phase)
-  s->sub_dcfr_ok = false;
+  s->sub.dcfr_ok = false;
   int per_cu_d = 0;
   if (raise_lds_cap(cfr_sub_kernel_of(K, false, true), static_cast<int>(lds)) == hipSuccess) {
     hipError_t ed;
@@ -1060,7 +1060,7 @@ int build_sub(osg_cfr* s) {
     return OSG_OK;
   }
   const int grid = std::min(G, per_cu * prop.multiProcessorCount);
-  s->sub_dcfr_ok = per_cu_d >= 1 && std::min(G, per_cu_d * prop.multiProcessorCount) >= grid;   // resident on the same grid
+  s->sub.dcfr_ok = per_cu_d >= 1 && std::min(G, per_cu_d * prop.multiProcessorCount) >= grid;   // resident on the same grid
   // the fold's shares: a workgroup's run of the updating player's infostates (info_list order), balanced by members
   std::vector<int32_t> fold_info(info_list.size() * 4), fold_off(static_cast<size_t>(s->P) * (grid + 1), 0);
   for (size_t e = 0; e < info_list.size(); ++e) {
@@ -1088,13 +1088,13 @@ int build_sub(osg_cfr* s) {
   }
   hipStream_t st = s->ctx->stream;
   int rc;
-  if ((rc = upload(nloc, &s->d_sub_nloc, st)) || (rc = upload(desc, &s->d_sub_desc, st)) || (rc = upload(fc, &s->d_sub_fc, st)) ||
-      (rc = upload(aux, &s->d_sub_aux, st)) || (rc = upload(mem_off, &s->d_sub_mem_off, st)) ||
-      (rc = upload(sub_rec, &s->d_sub_rec, st)) ||
-      (rc = upload(info_off, &s->d_sub_info_off, st)) || (rc = upload(info_list, &s->d_sub_info_list, st)) ||
-      (rc = upload(ndec, &s->d_sub_ndec, st)) || (rc = upload(dec_row, &s->d_sub_dec_row, st)) ||
-      (rc = upload(dec_off, &s->d_sub_dec_off, st)) || (rc = upload(chance_prob, &s->d_sub_chance_prob, st)) ||
-      (rc = upload(fold_info, &s->d_sub_fold_info, st)) || (rc = upload(fold_off, &s->d_sub_fold_off, st)))
+  if ((rc = upload(nloc, s->sub.nloc, st)) || (rc = upload(desc, s->sub.desc, st)) || (rc = upload(fc, s->sub.fc, st)) ||
+      (rc = upload(aux, s->sub.aux, st)) || (rc = upload(mem_off, s->sub.mem_off, st)) ||
+      (rc = upload(sub_rec, s->sub.rec, st)) ||
+      (rc = upload(info_off, s->sub.info_off, st)) || (rc = upload(info_list, s->sub.info_list, st)) ||
+      (rc = upload(ndec, s->sub.ndec, st)) || (rc = upload(dec_row, s->sub.dec_row, st)) ||
+      (rc = upload(dec_off, s->sub.dec_off, st)) || (rc = upload(chance_prob, s->sub.chance_prob, st)) ||
+      (rc = upload(fold_info, s->sub.fold_info, st)) || (rc = upload(fold_off, s->sub.fold_off, st)))
     return rc;
   {
     // the terminal returns of every bin by player, in the bin's local order: a pass starts with one coalesced copy into LDS
@@ -1108,10 +1108,10 @@ int build_sub(osg_cfr* s) {
         for (int q = 0; q < s->P; ++q)
           term_val[(static_cast<size_t>(g) * s->P + q) * NL + j] = s->term_ret[static_cast<size_t>(h) * s->P + q];
       }
-    if ((rc = upload(term_val, &s->d_sub_term_val, st))) return rc;
+    if ((rc = upload(term_val, s->sub.term_val, st))) return rc;
   }
-  s->sub_NCP = NCP;
-  s->sub_keep_rows = grid >= G;
+  s->sub.NCP = NCP;
+  s->sub.keep_rows = grid >= G;
   {
     // the members' 64-byte records: zero, but an upper member's says which one it is (kSubFlagHi | 2 + u)
     std::vector<double> recbuf(std::max<size_t>(M, 1) * kSubRecDoubles, 0.0);
@@ -1120,78 +1120,84 @@ int build_sub(osg_cfr* s) {
         const int64_t bits = (static_cast<int64_t>(kSubFlagHi) << 32) | static_cast<int64_t>(2 + upper_of[m]);
         memcpy(&recbuf[m * kSubRecDoubles], &bits, sizeof bits);
       }
-    if ((rc = upload(recbuf, &s->d_sub_recbuf, st))) return rc;
+    if ((rc = upload(recbuf, s->sub.recbuf, st))) return rc;
   }
-  s->sub_forest = upper;
+  s->sub.forest = upper;
   if (upper) {
-    if ((rc = upload(nroot, &s->d_sub_nroot, st)) || (rc = upload(root_loc, &s->d_sub_root_loc, st)) ||
-        (rc = upload(root_idx, &s->d_sub_root_idx, st)) || (rc = upload(upper_rec, &s->d_sub_upper_rec, st)))
+    if ((rc = upload(nroot, s->sub.nroot, st)) || (rc = upload(root_loc, s->sub.root_loc, st)) ||
+        (rc = upload(root_idx, s->sub.root_idx, st)) || (rc = upload(upper_rec, s->sub.upper_rec, st)))
       return rc;
     const size_t n_roots = static_cast<size_t>(s->level_off[piece_level + 1] - root_base);
-    OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_sub_root_value), sizeof(double) * std::max<size_t>(n_roots, 1)));
-    OSG_HIP(hipMemsetAsync(s->d_sub_root_value, 0, sizeof(double) * std::max<size_t>(n_roots, 1), st));
-    s->sub_NR = NR;
+    OSG_HIP(s->sub.root_value.alloc(n_roots));
+    OSG_HIP(hipMemsetAsync(s->sub.root_value, 0, sizeof(double) * std::max<size_t>(n_roots, 1), st));
+    s->sub.NR = NR;
   }
-  s->sub_ND = ND;
-  s->sub_PL = PL;
-  OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_sub_bar), sizeof(unsigned int) * kSubBarWords));
-  OSG_HIP(hipMemsetAsync(s->d_sub_bar, 0, sizeof(unsigned int) * kSubBarWords, st));
-  s->sub_G0 = G0;
-  s->sub_G = G; s->sub_L = L; s->sub_NL = NL; s->sub_K = K; s->sub_grid = grid; s->sub_lds_bytes = lds;
-  s->sub_ok = true;
+  s->sub.ND = ND;
+  s->sub.PL = PL;
+  OSG_HIP(s->sub.bar.alloc(kSubBarWords));
+  OSG_HIP(hipMemsetAsync(s->sub.bar, 0, sizeof(unsigned int) * kSubBarWords, st));
+  s->sub.G0 = G0;
+  s->sub.G = G; s->sub.L = L; s->sub.NL = NL; s->sub.K = K; s->sub.grid = grid; s->sub.lds_bytes = lds;
+  s->sub.ok = true;
   return OSG_OK;
+}
+
+// k_cfr_sub's view of the plan.  The OSG_CFR_SUB_* switches are read here, at every call.
+SubTree sub_tree_of(const osg_cfr* s) {
+  const SubPlan& p = s->sub;
+  const auto env_is = [](const char* name, const char* value) { const char* e = std::getenv(name); return e && std::strcmp(e, value) == 0; };
+  const auto env_starts = [](const char* name, char c) { const char* e = std::getenv(name); return e && e[0] == c; };
+  // the grid barrier: 2 = two-level arrival, the pollers watch the top counter (round 6); 1 = the same with a release
+  // word (round 5; OSG_CFR_SUB_BARRIER=release); 0 = round 4's flat counter (OSG_CFR_SUB_FLAT_BARRIER=1)
+  const int barrier = env_starts("OSG_CFR_SUB_FLAT_BARRIER", '1') ? 0 : (env_is("OSG_CFR_SUB_BARRIER", "release") ? 1 : 2);
+  SubTree sp{p.G, p.L, p.NL, p.nloc, p.desc, p.fc, p.aux, p.ND, p.ndec, p.dec_row, p.mem_off, p.rec, p.PL, p.info_off, p.info_list,
+             p.recbuf, barrier, p.bar, s->h_sub_err, 400000000ull /* 4 s at 100 MHz */, nullptr};
+  sp.dec_off = p.dec_off; sp.chance_prob = p.chance_prob; sp.NCP = p.NCP;
+  sp.keep_rows = (p.keep_rows && !env_starts("OSG_CFR_SUB_KEEP_ROWS", '0')) ? 1 : 0;
+  sp.lds_doubles = static_cast<int>(p.lds_bytes / sizeof(double));
+  sp.fold_info = p.fold_info; sp.fold_off = p.fold_off;
+  sp.term_val = p.term_val;
+  sp.prefetch = env_starts("OSG_CFR_SUB_PREFETCH", '0') ? 0 : 1;
+  if (p.forest) {
+    sp.nroot = p.nroot; sp.root_loc = p.root_loc; sp.root_idx = p.root_idx; sp.NR = p.NR;
+    sp.root_value = p.root_value; sp.upper_rec = p.upper_rec;
+  }
+  sp.br_player = s->d_info_player32;
+  if (const char* e = std::getenv("OSG_CFR_SUB_STAMPS"))   // (its value: the stamping workgroup's index + 1)
+    sp.stamp_wg = std::max(0, std::min(p.grid - 1, atoi(e) - 1));
+  return sp;
 }
 
 // The persistent cooperative launch (osg_cfr_iterate's sub_path); br_best != null: ONE CFR-BR pass set on the best responses
 // the evaluation left there (cfr_sub_br_iterate below).
 static int cfr_sub_run(osg_cfr* s, Tables tb, int iters, const int32_t* br_best, osg_cfr_cfg cfg) {
   if (int rc = cfr_sub_error(s)) return rc;
-  const int M = static_cast<int>(s->mem.size());
   Tree tr = s->tree();
-  SmallTree stree{s->d_path_off, s->d_path, M, static_cast<int>(s->path.size())};
-  SubTree sp{s->sub_G, s->sub_L, s->sub_NL, s->d_sub_nloc, s->d_sub_desc, s->d_sub_fc, s->d_sub_aux, s->sub_ND, s->d_sub_ndec,
-             s->d_sub_dec_row, s->d_sub_mem_off,
-             s->d_sub_rec, s->sub_PL, s->d_sub_info_off, s->d_sub_info_list, s->d_sub_recbuf,
-             // the grid barrier: 2 = two-level arrival, the pollers watch the top counter (round 6); 1 = the same with a release
-             // word (round 5; OSG_CFR_SUB_BARRIER=release); 0 = round 4's flat counter (OSG_CFR_SUB_FLAT_BARRIER=1)
-             (std::getenv("OSG_CFR_SUB_FLAT_BARRIER") && std::getenv("OSG_CFR_SUB_FLAT_BARRIER")[0] == '1')
-                 ? 0 : ((std::getenv("OSG_CFR_SUB_BARRIER") && std::strcmp(std::getenv("OSG_CFR_SUB_BARRIER"), "release") == 0) ? 1 : 2),
-             s->d_sub_bar, s->h_sub_err, 400000000ull /* 4 s at 100 MHz */, nullptr};
-  sp.dec_off = s->d_sub_dec_off; sp.chance_prob = s->d_sub_chance_prob; sp.NCP = s->sub_NCP;
-  sp.keep_rows = (s->sub_keep_rows && !(std::getenv("OSG_CFR_SUB_KEEP_ROWS") && std::getenv("OSG_CFR_SUB_KEEP_ROWS")[0] == '0')) ? 1 : 0;
-  sp.lds_doubles = static_cast<int>(s->sub_lds_bytes / sizeof(double));
-  sp.fold_info = s->d_sub_fold_info; sp.fold_off = s->d_sub_fold_off;
-  sp.term_val = s->d_sub_term_val;
-  sp.prefetch = (std::getenv("OSG_CFR_SUB_PREFETCH") && std::getenv("OSG_CFR_SUB_PREFETCH")[0] == '0') ? 0 : 1;
-  if (s->sub_forest) {
-    sp.nroot = s->d_sub_nroot; sp.root_loc = s->d_sub_root_loc; sp.root_idx = s->d_sub_root_idx; sp.NR = s->sub_NR;
-    sp.root_value = s->d_sub_root_value; sp.upper_rec = s->d_sub_upper_rec;
-  }
-  sp.br_best = br_best; sp.br_player = s->d_info_player32;
-  unsigned long long*& d_stamps = s->d_sub_stamps;   // OSG_CFR_SUB_STAMPS=1: phase stamps of one workgroup (tools/probe_cfr_sub.py); the solver's own buffer
-  if (std::getenv("OSG_CFR_SUB_STAMPS")) {
-    sp.stamp_wg = std::max(0, std::min(s->sub_grid - 1, atoi(std::getenv("OSG_CFR_SUB_STAMPS")) - 1));
-    fprintf(stderr, "k_cfr_sub: G %d grid %d NL %d ND %d PL %d K %d forest %d NR %d\n", s->sub_G, s->sub_grid, s->sub_NL, s->sub_ND, s->sub_PL, s->sub_K, s->sub_forest ? 1 : 0, s->sub_NR);
-    if (!d_stamps) OSG_HIP(hipMalloc(reinterpret_cast<void**>(&d_stamps), sizeof(unsigned long long) * (8 * kMaxPlayers + 2 * kMaxPlayers * 1024)));
-    sp.stamps = d_stamps;
+  SmallTree stree = small_tree_of(s);
+  SubTree sp = sub_tree_of(s);
+  sp.br_best = br_best;
+  if (std::getenv("OSG_CFR_SUB_STAMPS")) {   // phase stamps of one workgroup (tools/probe_cfr_sub.py); the solver's own buffer
+    fprintf(stderr, "k_cfr_sub: G %d grid %d NL %d ND %d PL %d K %d forest %d NR %d\n", s->sub.G, s->sub.grid, s->sub.NL, s->sub.ND, s->sub.PL, s->sub.K, s->sub.forest ? 1 : 0, s->sub.NR);
+    if (!s->sub.stamps) OSG_HIP(s->sub.stamps.alloc(8 * kMaxPlayers + 2 * kMaxPlayers * 1024));
+    sp.stamps = s->sub.stamps;
   }
   hipStream_t st = s->ctx->stream;
-  const int per_launch = std::max(1, (1 << 30) / std::max(1, 2 * s->P * s->sub_grid));  // the arrival counter is 32 bits
+  const int per_launch = std::max(1, (1 << 30) / std::max(1, 2 * s->P * s->sub.grid));  // the arrival counter is 32 bits
   const double* disc0 = nullptr;
   if (!br_best)
     if (int rc = cfr_discount_table(s, s->iteration, iters, &disc0)) return rc;
   for (int done = 0; done < iters; done += per_launch) {
     int now = std::min(per_launch, iters - done), it0 = s->iteration + done;
-    OSG_HIP(hipMemsetAsync(s->d_sub_bar, 0, sizeof(unsigned int) * kSubBarWords, st));
+    OSG_HIP(hipMemsetAsync(s->sub.bar, 0, sizeof(unsigned int) * kSubBarWords, st));
     const double* disc = disc0 ? disc0 + 3 * static_cast<size_t>(done) : nullptr;
     void* args[] = {&tr, &stree, &sp, &tb, &now, &it0, &cfg, &disc};
-    const void* kern = cfr_sub_kernel_of(s->sub_K, br_best != nullptr, disc != nullptr);
+    const void* kern = cfr_sub_kernel_of(s->sub.K, br_best != nullptr, disc != nullptr);
     // (OSG_CFR_PLAIN_LAUNCH=1 as for k_cfr_split: an ordinary launch, for hosts that own the device — and for runs under
     // rocprofv3 --kernel-trace, where a process that made a cooperative launch crashes in an exit handler)
     static const bool plain = std::getenv("OSG_CFR_PLAIN_LAUNCH") && std::getenv("OSG_CFR_PLAIN_LAUNCH")[0] == '1';
-    if (plain) OSG_HIP(hipLaunchKernel(kern, dim3(static_cast<unsigned>(s->sub_grid)), dim3(kSubThreads), args, s->sub_lds_bytes, st));
-    else OSG_HIP(hipLaunchCooperativeKernel(kern, dim3(static_cast<unsigned>(s->sub_grid)), dim3(kSubThreads), args,
-                                            static_cast<unsigned>(s->sub_lds_bytes), st));
+    if (plain) OSG_HIP(hipLaunchKernel(kern, dim3(static_cast<unsigned>(s->sub.grid)), dim3(kSubThreads), args, s->sub.lds_bytes, st));
+    else OSG_HIP(hipLaunchCooperativeKernel(kern, dim3(static_cast<unsigned>(s->sub.grid)), dim3(kSubThreads), args,
+                                            static_cast<unsigned>(s->sub.lds_bytes), st));
   }
   if (sp.stamps) {
     unsigned long long h[8 * kMaxPlayers];
@@ -1204,27 +1210,27 @@ static int cfr_sub_run(osg_cfr* s, Tables tb, int iters, const int32_t* br_best,
               (h[q * 5 + 1] - h[q * 5]) / 100.0, (h[q * 5 + 2] - h[q * 5 + 1]) / 100.0, (h[q * 5 + 3] - h[q * 5 + 2]) / 100.0,
               (h[q * 5 + 4] - h[q * 5 + 3]) / 100.0, q + 1 < s->P ? (h[(q + 1) * 5] - h[q * 5]) / 100.0 : 0.0);
   }
-  if (sp.stamps && s->sub_grid <= 1024) {   // arrival of every workgroup at the two barriers of each pass (s_memrealtime: one clock for the chip)
-    std::vector<unsigned long long> a(static_cast<size_t>(2) * s->P * s->sub_grid);
+  if (sp.stamps && s->sub.grid <= 1024) {   // arrival of every workgroup at the two barriers of each pass (s_memrealtime: one clock for the chip)
+    std::vector<unsigned long long> a(static_cast<size_t>(2) * s->P * s->sub.grid);
     OSG_HIP(hipMemcpyAsync(a.data(), sp.stamps + 8 * kMaxPlayers, sizeof(unsigned long long) * a.size(), hipMemcpyDeviceToHost, st));
     OSG_HIP(hipStreamSynchronize(st));
     for (int q = 0; q < s->P; ++q)
       for (int w = 0; w < 2; ++w) {
-        const unsigned long long* v = a.data() + static_cast<size_t>(q * 2 + w) * s->sub_grid;
+        const unsigned long long* v = a.data() + static_cast<size_t>(q * 2 + w) * s->sub.grid;
         unsigned long long lo = v[0], hi = v[0];
         int last = 0;
-        for (int g = 0; g < s->sub_grid; ++g) { if (v[g] < lo) lo = v[g]; if (v[g] > hi) { hi = v[g]; last = g; } }
+        for (int g = 0; g < s->sub.grid; ++g) { if (v[g] < lo) lo = v[g]; if (v[g] > hi) { hi = v[g]; last = g; } }
         int late1 = 0, late2 = 0, late_big = 0;
-        for (int g = 0; g < s->sub_grid; ++g) { late1 += hi - v[g] <= 100; late2 += hi - v[g] <= 200; late_big += (hi - v[g] <= 200 && g < 64); }
+        for (int g = 0; g < s->sub.grid; ++g) { late1 += hi - v[g] <= 100; late2 += hi - v[g] <= 200; late_big += (hi - v[g] <= 200 && g < 64); }
         fprintf(stderr, "k_cfr_sub pass %d barrier %c arrivals (us after the first): last %.2f (workgroup %d); within 1 us of the last: %d, within 2 us: %d (%d of them among workgroups 0-63); wg 0 %.2f, 32 %.2f, 100 %.2f, 200 %.2f, %d %.2f\n",
-                q, w ? 'B' : 'A', (hi - lo) / 100.0, last, late1, late2, late_big, (v[0] - lo) / 100.0, (v[std::min(32, s->sub_grid - 1)] - lo) / 100.0,
-                (v[std::min(100, s->sub_grid - 1)] - lo) / 100.0, (v[std::min(200, s->sub_grid - 1)] - lo) / 100.0, s->sub_grid - 1, (v[s->sub_grid - 1] - lo) / 100.0);
+                q, w ? 'B' : 'A', (hi - lo) / 100.0, last, late1, late2, late_big, (v[0] - lo) / 100.0, (v[std::min(32, s->sub.grid - 1)] - lo) / 100.0,
+                (v[std::min(100, s->sub.grid - 1)] - lo) / 100.0, (v[std::min(200, s->sub.grid - 1)] - lo) / 100.0, s->sub.grid - 1, (v[s->sub.grid - 1] - lo) / 100.0);
       }
   }
   s->iteration += iters;
-  if (br_best) s->last_kernel = s->sub_forest ? "k_cfr_sub<forest,br>" : (s->sub_G < s->sub_G0 ? "k_cfr_sub<packed,br>" : "k_cfr_sub<br>");
-  else if (disc0) s->last_kernel = s->sub_forest ? "k_cfr_sub<forest,dcfr>" : (s->sub_G < s->sub_G0 ? "k_cfr_sub<packed,dcfr>" : "k_cfr_sub<dcfr>");
-  else s->last_kernel = s->sub_forest ? "k_cfr_sub<forest>" : (s->sub_G < s->sub_G0 ? "k_cfr_sub<packed>" : "k_cfr_sub");
+  if (br_best) s->last_kernel = s->sub.forest ? "k_cfr_sub<forest,br>" : (s->sub.G < s->sub.G0 ? "k_cfr_sub<packed,br>" : "k_cfr_sub<br>");
+  else if (disc0) s->last_kernel = s->sub.forest ? "k_cfr_sub<forest,dcfr>" : (s->sub.G < s->sub.G0 ? "k_cfr_sub<packed,dcfr>" : "k_cfr_sub<dcfr>");
+  else s->last_kernel = s->sub.forest ? "k_cfr_sub<forest>" : (s->sub.G < s->sub.G0 ? "k_cfr_sub<packed>" : "k_cfr_sub");
   return OSG_OK;
 }
 int cfr_sub_iterate(osg_cfr* s, Tables tb, int iters) { return cfr_sub_run(s, tb, iters, nullptr, s->cfg); }
@@ -1236,7 +1242,7 @@ int cfr_sub_iterate(osg_cfr* s, Tables tb, int iters) { return cfr_sub_run(s, tb
 int cfr_sub_br_iterate(osg_cfr* s, Tables tb, const EvalArrays& ea, osg_cfr_cfg cfg, int iters) {
   for (int it = 0; it < iters; ++it) {
     if (int rc = launch_grid_eval(s, ea, s->cur(), false, nullptr, true)) return rc;
-    if (int rc = cfr_sub_run(s, tb, 1, s->d_best, cfg)) return rc;
+    if (int rc = cfr_sub_run(s, tb, 1, s->eval.best, cfg)) return rc;
   }
   return OSG_OK;
 }
@@ -1287,14 +1293,14 @@ int cfr_grid_br_iterate(osg_cfr* s, Tables tb, const EvalArrays& ea, osg_cfr_cfg
   g.t = s->tree(); g.path_off = s->d_path_off; g.path = s->d_path; g.meta = s->d_meta32;
   g.info_player = s->d_info_player32; g.value = s->d_value; g.dreg = s->d_node_delta;
   g.dpol = s->d_node_delta + M * s->A; g.skip = s->d_skip; g.tb = tb; g.M = static_cast<int>(M);
-  double* d_eff = ea.out + 2 * s->P;   // (the evaluation's policy scratch: [I, A], free here)
+  double* d_eff = eval_policy_slot(s);   // (the evaluation's policy scratch: [I, A], free here)
   g.pol = d_eff;
   auto blocks = [](int n) { return dim3(static_cast<unsigned>((n + 255) / 256)); };
   k_gcfr_init_values<<<blocks(s->H), dim3(256), 0, st>>>(g);
   for (int it = 0; it < iters; ++it) {
     if (int rc = launch_grid_eval(s, ea, s->cur(), false, nullptr, true)) return rc;
     for (int upd = 0; upd < s->P; ++upd) {
-      k_gcfr_effpol<<<blocks(s->I), dim3(256), 0, st>>>(g, upd, s->d_best, d_eff);
+      k_gcfr_effpol<<<blocks(s->I), dim3(256), 0, st>>>(g, upd, s->eval.best, d_eff);
       for (int l = s->D - 2; l >= 0; --l) {
         const int begin = s->level_off[l], end = s->level_off[l + 1];
         k_gcfr_level<<<blocks(end - begin), dim3(256), 0, st>>>(g, begin, end, upd, upd + 1);

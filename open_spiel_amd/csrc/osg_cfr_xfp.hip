@@ -135,24 +135,6 @@ k_xfp_small(Tree t, EvalArrays ea, int n_path, double* pol_global, int32_t* best
   xfp_stage(best_global, ea.best, t.I);
 }
 
-EvalArrays xfp_eval_arrays(const osg_cfr* s) {   // as osg_cfr_br_iterate lays them out
-  const size_t M = s->mem.size();
-  EvalArrays ea;
-  ea.path_off = s->d_path_off; ea.path = s->d_path; ea.info_level = s->d_info_level; ea.mem_index = s->d_mem_index;
-  ea.M = static_cast<int>(M);
-  ea.value = s->d_eval;
-  ea.brv = ea.value + static_cast<size_t>(s->H) * s->P;
-  ea.cf = ea.brv + s->H;
-  ea.out = ea.cf + M;
-  ea.best = s->d_best;
-  return ea;
-}
-
-int xfp_eval_threads(const osg_cfr* s) {
-  const int threads = ((s->max_level_width + 63) / 64) * 64;
-  return std::max(64, std::min(threads, 1024));
-}
-
 size_t xfp_small_lds_bytes(const osg_cfr* s) {
   XfpResident r;
   return xfp_resident(nullptr, s->H, s->I, s->A, s->P, s->D, static_cast<int>(s->mem.size()), static_cast<int>(s->path.size()), &r);
@@ -160,7 +142,7 @@ size_t xfp_small_lds_bytes(const osg_cfr* s) {
 
 // The fused form takes what k_policy_eval would evaluate (no jobs, not the grid) when the resident arrays fit.
 bool xfp_takes_the_fused_form(const osg_cfr* s) {
-  return s->cfg.kernel == 0 && !(s->jobs_ok && OSG_EVAL_JOBS_ENABLED()) && !eval_takes_the_grid(s) &&
+  return s->cfg.kernel == 0 && !(s->jobs.ok && OSG_EVAL_JOBS_ENABLED()) && !eval_takes_the_grid(s) &&
          xfp_small_lds_bytes(s) <= kXfpLdsLimit;
 }
 
@@ -168,8 +150,8 @@ bool xfp_takes_the_fused_form(const osg_cfr* s) {
 // level and phase, 1 and 3 one workgroup, otherwise what osg_cfr_br_iterate picks.
 int xfp_best_responses(osg_cfr* s, const EvalArrays& ea) {
   if (s->cfg.kernel == 2) return launch_grid_eval(s, ea, s->cur(), false, nullptr, true);
-  const bool jobs = s->jobs_ok && OSG_EVAL_JOBS_ENABLED() && s->cfg.kernel != 1 && s->cfg.kernel != 3;
-  return cfr_best_responses_to_current(s, ea, xfp_eval_threads(s), jobs);
+  const bool jobs = s->jobs.ok && OSG_EVAL_JOBS_ENABLED() && s->cfg.kernel != 1 && s->cfg.kernel != 3;
+  return cfr_best_responses_to_current(s, ea, jobs);
 }
 
 const char* xfp_general_name(const osg_cfr* s) {
@@ -180,26 +162,23 @@ const char* xfp_general_name(const osg_cfr* s) {
   return "k_xfp<k_policy_eval>";
 }
 
-double* xfp_reach_buffer(const osg_cfr* s) { return s->d_reach; }   // [H, P + 1] doubles, free between CFR launches: 2 I <= H
-
-void launch_reach(const osg_cfr* s) {
+void launch_reach(const osg_cfr* s, double* reach) {
   const unsigned blocks = static_cast<unsigned>((s->I + kXfpThreads - 1) / kXfpThreads);
-  k_xfp_reach<<<dim3(blocks), dim3(kXfpThreads), 0, s->ctx->stream>>>(s->tree(), s->d_path_off, s->d_path, s->cur(), s->d_best,
-                                                                      xfp_reach_buffer(s));
+  k_xfp_reach<<<dim3(blocks), dim3(kXfpThreads), 0, s->ctx->stream>>>(s->tree(), s->d_path_off, s->d_path, s->cur(), s->eval.best, reach);
 }
-void launch_update(const osg_cfr* s, double alpha) {
+void launch_update(const osg_cfr* s, const double* reach, double alpha) {
   const unsigned blocks = static_cast<unsigned>((s->I + kXfpThreads - 1) / kXfpThreads);
-  k_xfp_update<<<dim3(blocks), dim3(kXfpThreads), 0, s->ctx->stream>>>(s->tree(), s->cur(), s->d_best, xfp_reach_buffer(s), alpha);
+  k_xfp_update<<<dim3(blocks), dim3(kXfpThreads), 0, s->ctx->stream>>>(s->tree(), s->cur(), s->eval.best, reach, alpha);
 }
 
-int xfp_refusal(const osg_cfr* s, const char* who) {
+// What every entry point refuses, and the [2, I] reach scratch (borrowed from d_reach) of those it serves.
+int xfp_refusal(const osg_cfr* s, const char* who, double** reach) {
   const std::string w = who;
   if (s->cfg.solver != 0) return set_error(OSG_ERR_INVALID, w + ": needs a CFRSolverBase table (solver 0), not an MCCFR solver");
   if (s->B != 1) return set_error(OSG_ERR_UNSUPPORTED, w + ": one solver per object (replicas > 1)");
   if (s->dcfr) return set_error(OSG_ERR_INVALID, w + ": fictitious play has no discounting, this solver discounts (osg_cfr_set_discounting)");
   if (!s->eval_ok) return set_error(OSG_ERR_UNSUPPORTED, w + ": an information state spans several tree levels");
-  if (2 * static_cast<size_t>(s->I) > static_cast<size_t>(s->H) * (s->P + 1))
-    return set_error(OSG_ERR_UNSUPPORTED, w + ": more information states than the reach buffer holds");
+  if (int rc = xfp_reach_in_reach(s, w, reach)) return rc;
   return cfr_sub_error(s);
 }
 
@@ -211,7 +190,7 @@ int xfp_upload_best(osg_cfr* s, const int32_t* h_best_index, const char* who) {
                                             std::to_string(i) + " (" + std::to_string(h_best_index[i]) + ", legal actions " +
                                             std::to_string(s->nact[i]) + ")");
   hipStream_t st = s->ctx->stream;
-  OSG_HIP(hipMemcpyAsync(s->d_best, h_best_index, sizeof(int32_t) * s->I, hipMemcpyHostToDevice, st));
+  OSG_HIP(hipMemcpyAsync(s->eval.best, h_best_index, sizeof(int32_t) * s->I, hipMemcpyHostToDevice, st));
   OSG_HIP(hipStreamSynchronize(st));   // (the caller's array may be pageable and die with the call)
   return OSG_OK;
 }
@@ -223,10 +202,11 @@ extern "C" {
 int osg_xfp_iterate(osg_cfr* s, int iters) {
   if (!s || iters < 0) return set_error(OSG_ERR_INVALID, "osg_xfp_iterate: bad argument");
   if (mmd_mode(s)) return set_error(OSG_ERR_INVALID, "osg_xfp_iterate: the solver is in mirror-descent mode (osg_mmd_set_params); fictitious play would overwrite its policy table");
-  if (int rc = xfp_refusal(s, "osg_xfp_iterate")) return rc;
+  double* reach = nullptr;
+  if (int rc = xfp_refusal(s, "osg_xfp_iterate", &reach)) return rc;
   if (iters == 0) return OSG_OK;
   hipStream_t st = s->ctx->stream;
-  EvalArrays ea = xfp_eval_arrays(s);
+  EvalArrays ea = eval_arrays_of(s);
   if (xfp_takes_the_fused_form(s)) {
     const size_t lds = xfp_small_lds_bytes(s);
     if (raise_lds_cap(reinterpret_cast<const void*>(&k_xfp_small), static_cast<int>(lds)) != hipSuccess) {
@@ -235,19 +215,14 @@ int osg_xfp_iterate(osg_cfr* s, int iters) {
     }
     for (int done = 0; done < iters; done += kXfpItersPerLaunch) {
       const int n = std::min(kXfpItersPerLaunch, iters - done);
-      // (the stream may still be reading h_disc / d_disc for the previous launch)
+      // (the stream may still be reading h_iter_table / d_iter_table for the previous launch)
       OSG_HIP(hipStreamSynchronize(st));
-      if (static_cast<size_t>(n) > s->disc_cap) {
-        if (s->d_disc) OSG_HIP(hipFree(s->d_disc));
-        s->d_disc = nullptr; s->disc_cap = 0;
-        OSG_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_disc), sizeof(double) * kXfpItersPerLaunch));
-        s->disc_cap = kXfpItersPerLaunch;
-      }
-      s->h_disc.resize(n);
-      for (int k = 0; k < n; ++k) s->h_disc[k] = xfp_alpha(s->iteration + k + 1);
-      OSG_HIP(hipMemcpyAsync(s->d_disc, s->h_disc.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
-      k_xfp_small<<<dim3(1), dim3(xfp_eval_threads(s)), lds, st>>>(s->tree(), ea, static_cast<int>(s->path.size()), s->cur(), s->d_best,
-                                                                    s->d_disc, n);
+      OSG_HIP(s->d_iter_table.ensure(kXfpItersPerLaunch));
+      s->h_iter_table.resize(n);
+      for (int k = 0; k < n; ++k) s->h_iter_table[k] = xfp_alpha(s->iteration + k + 1);
+      OSG_HIP(hipMemcpyAsync(s->d_iter_table, s->h_iter_table.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+      k_xfp_small<<<dim3(1), dim3(level_threads(s)), lds, st>>>(s->tree(), ea, static_cast<int>(s->path.size()), s->cur(), s->eval.best,
+                                                                    s->d_iter_table, n);
       OSG_HIP(hipGetLastError());
       s->iteration += n;
     }
@@ -256,9 +231,9 @@ int osg_xfp_iterate(osg_cfr* s, int iters) {
   }
   for (int it = 0; it < iters; ++it) {
     if (int rc = xfp_best_responses(s, ea)) return rc;
-    launch_reach(s);
+    launch_reach(s, reach);
     ++s->iteration;
-    launch_update(s, xfp_alpha(s->iteration));
+    launch_update(s, reach, xfp_alpha(s->iteration));
   }
   OSG_HIP(hipGetLastError());
   s->last_kernel = xfp_general_name(s);
@@ -267,11 +242,12 @@ int osg_xfp_iterate(osg_cfr* s, int iters) {
 
 int osg_xfp_update(osg_cfr* s, const int32_t* h_best_index) {
   if (!s || !h_best_index) return set_error(OSG_ERR_INVALID, "osg_xfp_update: null argument");
-  if (int rc = xfp_refusal(s, "osg_xfp_update")) return rc;
+  double* reach = nullptr;
+  if (int rc = xfp_refusal(s, "osg_xfp_update", &reach)) return rc;
   if (int rc = xfp_upload_best(s, h_best_index, "osg_xfp_update")) return rc;
-  launch_reach(s);
+  launch_reach(s, reach);
   ++s->iteration;
-  launch_update(s, xfp_alpha(s->iteration));
+  launch_update(s, reach, xfp_alpha(s->iteration));
   OSG_HIP(hipGetLastError());
   s->last_kernel = "k_xfp_update";
   return OSG_OK;
@@ -279,17 +255,18 @@ int osg_xfp_update(osg_cfr* s, const int32_t* h_best_index) {
 
 int osg_xfp_reaches(osg_cfr* s, const int32_t* h_best_index, double* h_avg_reach, double* h_br_reach) {
   if (!s || !h_avg_reach || !h_br_reach) return set_error(OSG_ERR_INVALID, "osg_xfp_reaches: null argument");
-  if (int rc = xfp_refusal(s, "osg_xfp_reaches")) return rc;
+  double* reach = nullptr;
+  if (int rc = xfp_refusal(s, "osg_xfp_reaches", &reach)) return rc;
   hipStream_t st = s->ctx->stream;
   if (h_best_index) {
     if (int rc = xfp_upload_best(s, h_best_index, "osg_xfp_reaches")) return rc;
   } else {
-    if (int rc = xfp_best_responses(s, xfp_eval_arrays(s))) return rc;
+    if (int rc = xfp_best_responses(s, eval_arrays_of(s))) return rc;
   }
-  launch_reach(s);
+  launch_reach(s, reach);
   OSG_HIP(hipGetLastError());
-  OSG_HIP(hipMemcpyAsync(h_avg_reach, xfp_reach_buffer(s), sizeof(double) * s->I, hipMemcpyDeviceToHost, st));
-  OSG_HIP(hipMemcpyAsync(h_br_reach, xfp_reach_buffer(s) + s->I, sizeof(double) * s->I, hipMemcpyDeviceToHost, st));
+  OSG_HIP(hipMemcpyAsync(h_avg_reach, reach, sizeof(double) * s->I, hipMemcpyDeviceToHost, st));
+  OSG_HIP(hipMemcpyAsync(h_br_reach, reach + s->I, sizeof(double) * s->I, hipMemcpyDeviceToHost, st));
   OSG_HIP(hipStreamSynchronize(st));
   return OSG_OK;
 }

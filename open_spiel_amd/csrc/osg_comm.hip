@@ -202,12 +202,12 @@ struct osg_comm {
   // one-shot kind (osg_comm_oneshot_create): the local window, the peers' mappings, the call counter
   bool oneshot = false, connected = false;
   int64_t cap = 0;                        // doubles per slot
-  void* window = nullptr;                 // data | flags, one fine-grained allocation
+  osg::DeviceArray<char> window;               // data | flags, one fine-grained allocation
   size_t window_bytes = 0, flags_offset = 0;
   void* mapped[kOneShotMaxWorld] = {};    // peers' windows as opened here (own entry = window)
   OneShotPeers peers{};
   unsigned long long seq = 0;
-  unsigned int* h_err = nullptr;          // pinned host word the kernel raises on a timeout
+  osg::PinnedArray<unsigned int> h_err;      // pinned host word the kernel raises on a timeout
   unsigned long long timeout_ticks = 0;
   // the asynchronous form (osg_allreduce_sum_f64_begin / osg_allreduce_end): the collective runs on the
   // communicator's own stream between two events, so kernels issued on the context's stream meanwhile overlap it
@@ -227,7 +227,7 @@ static int OneShotLaunch(osg_comm* c, T* d_buf, int64_t n, hipStream_t stream, c
     return set_error(OSG_ERR_INVALID, std::string(what) + ": message longer than the window's slot (max_doubles at creation; "
                                                           "at most 32768 elements per call)");
   // raised by an EARLIER call's kernel (system-scope store into pinned host memory: read here without a copy)
-  if (__atomic_load_n(c->h_err, __ATOMIC_RELAXED) != 0)
+  if (__atomic_load_n(c->h_err.get(), __ATOMIC_RELAXED) != 0)
     return set_error(OSG_ERR_HIP, std::string(what) + ": an earlier one-shot all-reduce timed out waiting for a peer "
                                                       "(OSG_ONESHOT_TIMEOUT_MS); the communicator is unusable");
   const unsigned blocks = static_cast<unsigned>((n + kOneShotChunk - 1) / kOneShotChunk);
@@ -280,13 +280,12 @@ int osg_comm_destroy(osg_comm* c) {
     if (c->side) (void)hipStreamSynchronize(c->side);
     for (int s = 0; s < c->world; ++s)
       if (s != c->rank && c->mapped[s]) (void)hipIpcCloseMemHandle(c->mapped[s]);
-    if (c->window) (void)hipFree(c->window);
-    if (c->h_err) (void)hipHostFree(c->h_err);
     if (c->produced) (void)hipEventDestroy(c->produced);
     if (c->reduced) (void)hipEventDestroy(c->reduced);
     if (c->side) (void)hipStreamDestroy(c->side);
-    osg::ctx_release(c->ctx);
-    delete c;
+    osg_ctx* ctx = c->ctx;
+    delete c;                // the window and the error word go first:
+    osg::ctx_release(ctx);   // the context's device resources may go with its last reference
     return OSG_OK;
   }
   RcclApi* api = nullptr;
@@ -299,8 +298,9 @@ int osg_comm_destroy(osg_comm* c) {
   if (c->produced) hipEventDestroy(c->produced);
   if (c->reduced) hipEventDestroy(c->reduced);
   if (c->side) hipStreamDestroy(c->side);
-  osg::ctx_release(c->ctx);
+  osg_ctx* ctx = c->ctx;
   delete c;
+  osg::ctx_release(ctx);
   return rc;
 }
 
@@ -320,14 +320,12 @@ int osg_comm_oneshot_create(osg_ctx* ctx, int rank, int world, int64_t max_doubl
   c->flags_offset = (sizeof(double) * 2 * world * c->cap + 255) & ~size_t{255};
   c->window_bytes = c->flags_offset + sizeof(unsigned long long) * 2 * world * kOneShotMaxBlocks;
   // fine-grained: peers' write-through stores and this rank's system-scope loads meet in memory, not in a cache
-  hipError_t e = hipExtMallocWithFlags(&c->window, c->window_bytes, hipDeviceMallocFinegrained);
+  hipError_t e = c->window.alloc_finegrained(c->window_bytes);
   if (e == hipSuccess) e = hipMemset(c->window, 0, c->window_bytes);
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->h_err), sizeof(unsigned int), hipHostMallocMapped);
+  if (e == hipSuccess) e = c->h_err.alloc(1);
   if (e == hipSuccess) *c->h_err = 0;
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
-    if (c->window) (void)hipFree(c->window);
-    if (c->h_err) (void)hipHostFree(c->h_err);
     delete c;
     return set_error(OSG_ERR_NOMEM, std::string("osg_comm_oneshot_create: ") + hipGetErrorString(e));
   }
@@ -391,7 +389,7 @@ int osg_comm_check(osg_comm* c) {
   OSG_HIP(hipSetDevice(c->ctx->device));
   if (c->side) OSG_HIP(hipStreamSynchronize(c->side));
   OSG_HIP(hipStreamSynchronize(c->ctx->stream));
-  if (c->oneshot && __atomic_load_n(c->h_err, __ATOMIC_RELAXED) != 0)
+  if (c->oneshot && __atomic_load_n(c->h_err.get(), __ATOMIC_RELAXED) != 0)
     return set_error(OSG_ERR_HIP, "osg_comm_check: a one-shot all-reduce timed out waiting for a peer (OSG_ONESHOT_TIMEOUT_MS); the "
                                   "buffer of that call holds NaN / INT32_MIN in the chunks that were not reduced and the "
                                   "communicator is unusable");

@@ -13,6 +13,7 @@
 
 #include "../../include/osg_abi.h"
 #include "osg_common.h"
+#include "osg_device_buffer.h"
 #include "osg_game_boards.h"
 #include "osg_game_poker.h"
 #include "osg_sample.h"
@@ -172,6 +173,26 @@ struct osg_batch {
     if (e__ != hipSuccess)                                                         \
       return osg::set_error(OSG_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
   } while (0)
+
+namespace osg {
+// A failed allocation as the project's codes: a call site that reported OSG_ERR_HIP goes through OSG_HIP(buf.alloc(n))
+// as before; one that reported OSG_ERR_NOMEM with the runtime's text goes through this.
+inline int nomem_error(hipError_t e, const std::string& who = std::string()) {
+  return e == hipSuccess ? OSG_OK : set_error(OSG_ERR_NOMEM, who + hipGetErrorString(e));
+}
+// A host vector into a fresh device array of the same length.
+template <class T>
+int upload(const std::vector<T>& v, DeviceArray<T>& d, hipStream_t stream) {
+  OSG_HIP(d.alloc(v.size()));
+  if (!v.empty()) {
+    OSG_HIP(hipMemcpyAsync(d.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+    // The callers pass vectors that die when they return, and a large copy from pageable memory may still be reading
+    // the host buffer after the call (seen once as a GPU fault at a host address with an 87 MB vector): wait.
+    if (v.size() * sizeof(T) > (64u << 10)) OSG_HIP(hipStreamSynchronize(stream));
+  }
+  return OSG_OK;
+}
+}  // namespace osg
 
 // Scratch helpers (device + pinned host staging owned by the context).
 int osg_ctx_scratch(osg_ctx* ctx, size_t bytes, void** out);

@@ -32,17 +32,18 @@ struct osg_mcts_tree {
   int cap = 0, gc_nodes = 0, A = 0, P = 0, widest = 0;
   double max_utility = 0;
   bool board = false;
-  char* d_mem = nullptr;        // pool planes + per-root search state
+  DeviceArray<char> d_mem;      // pool planes + per-root search state
   size_t bytes = 0;
-  double* d_logs = nullptr;
+  DeviceArray<double> d_logs;
   int logs_n = 0;
   // the tree's own request / answer buffers, for hosts that hold no device memory (osg_mcts_tree_advance_host)
+  DeviceArray<char> d_own;         // made at the first call that needs them; the three below are its parts
   double* d_own_prior = nullptr;   // [n, A]
   double* d_own_value = nullptr;   // [n, P]
   uint8_t* d_own_request = nullptr;
   // flag 8: the evaluator answers a value request with the leaf's PRIOR as well (one network forward gives both,
   // vpevaluator.cc:60-85 caches them per state): the prior is kept per (root, simulation) until the leaf is expanded
-  double* d_stash = nullptr;       // [n, stash_slots, A]
+  DeviceArray<double> d_stash;     // [n, stash_slots, A]
   int stash_slots = 0;
 };
 
@@ -908,12 +909,9 @@ int osg_mcts_tree_create(const osg_batch* roots, const osg_mcts_cfg* cfg_in, int
     gc_nodes = std::max(2, cfg_in->max_nodes);
     cap = std::min<int64_t>(never, gc_nodes + 32 * per_sim);
   }
-  // every failure path below goes through here: what has been allocated so far goes with the handle
+  // every failure path below goes through here: the handle's buffers go with it (no context reference is held yet)
   auto fail = [&](int code) {
     if (t->roots) osg_batch_destroy(t->roots);
-    if (t->d_mem) (void)hipFree(t->d_mem);
-    if (t->d_stash) (void)hipFree(t->d_stash);
-    if (t->d_logs) (void)hipFree(t->d_logs);
     delete t;
     return code;
   };
@@ -941,11 +939,11 @@ int osg_mcts_tree_create(const osg_batch* roots, const osg_mcts_cfg* cfg_in, int
   t->cap = static_cast<int>(cap);
   t->gc_nodes = static_cast<int>(gc_nodes);
   t->bytes = pool_bytes(cap, t->n);
-  e = hipMalloc(reinterpret_cast<void**>(&t->d_mem), t->bytes);
-  if (e != hipSuccess) { t->d_mem = nullptr; return fail(set_error(OSG_ERR_NOMEM, std::string("MCTS trees: ") + hipGetErrorString(e))); }
+  e = t->d_mem.alloc(t->bytes);
+  if (e != hipSuccess) { return fail(set_error(OSG_ERR_NOMEM, std::string("MCTS trees: ") + hipGetErrorString(e))); }
   if (flags & 8) {
-    e = hipMalloc(reinterpret_cast<void**>(&t->d_stash), stash_bytes);
-    if (e != hipSuccess) { t->d_stash = nullptr; return fail(set_error(OSG_ERR_NOMEM, std::string("MCTS prior stash: ") + hipGetErrorString(e))); }
+    e = t->d_stash.alloc(stash_bytes / sizeof(double));
+    if (e != hipSuccess) { return fail(set_error(OSG_ERR_NOMEM, std::string("MCTS prior stash: ") + hipGetErrorString(e))); }
   }
   int rc = osg_batch_create(ctx, d.canonical, roots->n, &t->roots);
   if (rc == OSG_OK) rc = osg_batch_copy(t->roots, roots);
@@ -955,20 +953,18 @@ int osg_mcts_tree_create(const osg_batch* roots, const osg_mcts_cfg* cfg_in, int
   std::vector<double> logs(t->logs_n);
   logs[0] = 0.0;
   for (int i = 1; i < t->logs_n; ++i) logs[i] = std::log(static_cast<double>(i));
-  e = hipMalloc(reinterpret_cast<void**>(&t->d_logs), sizeof(double) * t->logs_n);
-  if (e != hipSuccess) t->d_logs = nullptr;
+  e = t->d_logs.alloc(t->logs_n);
   if (e == hipSuccess) e = hipMemcpy(t->d_logs, logs.data(), sizeof(double) * t->logs_n, hipMemcpyHostToDevice);
   // the roots' players (status query on the copy)
-  int8_t* d_cur = nullptr;
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_cur), static_cast<size_t>(t->n));
+  DeviceArray<int8_t> d_cur;
+  if (e == hipSuccess) e = d_cur.alloc(static_cast<size_t>(t->n));
   if (e != hipSuccess) return fail(set_error(OSG_ERR_NOMEM, hipGetErrorString(e)));
   rc = osg_status_query(t->roots, d_cur, nullptr, nullptr, 0);
   if (rc == OSG_OK) {
     k_mcts_tree_init<<<dim3(static_cast<unsigned>((t->n + 255) / 256)), dim3(256), 0, ctx->stream>>>(make_pool(t), d_cur, t->n);
     if (hipGetLastError() != hipSuccess) rc = set_error(OSG_ERR_HIP, "k_mcts_tree_init");
   }
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_cur);
+  (void)hipStreamSynchronize(ctx->stream);   // (d_cur is read until here)
   if (rc) return fail(rc);
   osg::ctx_retain(ctx);
   *out = t;
@@ -979,12 +975,9 @@ int osg_mcts_tree_destroy(osg_mcts_tree* t) {
   if (!t) return OSG_OK;
   (void)hipStreamSynchronize(t->ctx->stream);
   if (t->roots) osg_batch_destroy(t->roots);
-  (void)hipFree(t->d_mem);
-  (void)hipFree(t->d_logs);
-  if (t->d_own_prior) (void)hipFree(t->d_own_prior);
-  if (t->d_stash) (void)hipFree(t->d_stash);
-  osg::ctx_release(t->ctx);
-  delete t;
+  osg_ctx* ctx = t->ctx;
+  delete t;                // the tree's buffers go first:
+  osg::ctx_release(ctx);   // the context's device resources may go with its last reference
   return OSG_OK;
 }
 
@@ -1045,12 +1038,10 @@ int osg_mcts_tree_advance(osg_mcts_tree* t, osg_batch* leaf, const double* d_pri
 }
 
 static int own_buffers(osg_mcts_tree* t) {
-  if (t->d_own_prior) return OSG_OK;
+  if (t->d_own) return OSG_OK;
   const size_t bytes = sizeof(double) * static_cast<size_t>(t->n) * (t->A + t->P) + static_cast<size_t>(t->n) + 64;
-  char* m = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&m), bytes);
-  if (e != hipSuccess) return set_error(OSG_ERR_NOMEM, hipGetErrorString(e));
-  t->d_own_prior = reinterpret_cast<double*>(m);
+  if (int rc = nomem_error(t->d_own.alloc(bytes))) return rc;
+  t->d_own_prior = reinterpret_cast<double*>(t->d_own.get());
   t->d_own_value = t->d_own_prior + static_cast<size_t>(t->n) * t->A;
   t->d_own_request = reinterpret_cast<uint8_t*>(t->d_own_value + static_cast<size_t>(t->n) * t->P);
   return OSG_OK;

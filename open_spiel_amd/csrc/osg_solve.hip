@@ -40,27 +40,17 @@ constexpr bool solve_served() {
   return std::is_same<G, Ttt>::value || is_c4<G>::value || (solve_hex_nw<G>::value >= 1 && solve_hex_nw<G>::value <= 2);
 }
 
-struct DevBuf {   // a device allocation that goes with its scope
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
-  ~DevBuf() { reset(); }
-  void reset() { if (p) (void)hipFree(p); p = nullptr; }
-  hipError_t alloc(size_t bytes) { reset(); return hipMalloc(&p, bytes ? bytes : 1); }
-  template <class T> T* as() const { return static_cast<T*>(p); }
-};
-inline int dev_alloc(DevBuf& buf, size_t bytes) {
-  const hipError_t e = buf.alloc(bytes);
-  return e == hipSuccess ? OSG_OK : set_error(OSG_ERR_NOMEM, std::string("osg_solve: ") + hipGetErrorString(e));
-}
+using Bytes = DeviceArray<unsigned char>;   // state records (their word type comes with the game) and rocprim's scratch
+template <class W> W* words_of(const Bytes& b) { return reinterpret_cast<W*>(b.get()); }
+template <class T>
+int dev_alloc(DeviceArray<T>& buf, size_t n) { return nomem_error(buf.alloc(n), "osg_solve: "); }
 
 struct Level {
   int64_t n = 0, edges = 0;
-  DevBuf words, key_lo, key_hi;       // the records (SoA, stride n) and keys, ascending by key
-  DevBuf edge_off, edge_action, edge_child;   // [n + 1] i64 (level-local), [edges] i32, [edges] i64 (global, -1 dropped)
+  Bytes words;                        // the records (SoA, stride n), ascending by key
+  DeviceArray<uint64_t> key_lo, key_hi;
+  DeviceArray<int64_t> edge_off, edge_child;   // [n + 1] (level-local), [edges] (global, -1 dropped)
+  DeviceArray<int32_t> edge_action;            // [edges]
 };
 
 template <class G>
@@ -198,6 +188,7 @@ k_solve_lookup(typename G::Params p, const typename G::word_t* words, int64_t nq
 }  // namespace
 
 struct osg_solve {
+  struct CtxRef { osg_ctx* ctx = nullptr; ~CtxRef() { if (ctx) ctx_release(ctx); } } held;   // first member: dropped last, after every buffer
   osg_ctx* ctx = nullptr;
   GameSpec spec;
   int depth_limit = -1;
@@ -205,16 +196,14 @@ struct osg_solve {
   int mask_words = kMaskWords;
   int64_t n = 0, edges = 0, terminals = 0;
   std::vector<int64_t> level_off;    // [levels + 1]
-  std::vector<DevBuf> level_words;   // the records of each level (SoA, stride = the level's size)
-  DevBuf key_lo, key_hi, d_level_off, edge_off, edge_action, edge_child, value, optimal, distance;
+  std::vector<Bytes> level_words;    // the records of each level (SoA, stride = the level's size)
+  DeviceArray<uint64_t> key_lo, key_hi;
+  DeviceArray<int64_t> d_level_off, edge_off, edge_child;
+  DeviceArray<int32_t> edge_action, distance;
+  DeviceArray<double> value;
+  DeviceArray<uint32_t> optimal;
   bool wide = false;
-  ~osg_solve() {
-    if (ctx) {
-      (void)hipStreamSynchronize(ctx->stream);
-      level_words.clear();
-      ctx_release(ctx);
-    }
-  }
+  ~osg_solve() { if (ctx) (void)hipStreamSynchronize(ctx->stream); }   // (then the buffers go, then the context reference)
 };
 
 namespace {
@@ -228,9 +217,9 @@ int read_i64(osg_ctx* ctx, const int64_t* d, int64_t* h) {
 int scan_i64(osg_ctx* ctx, const int64_t* in, int64_t* out, int64_t count) {
   size_t bytes = 0;
   OSG_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, int64_t{0}, static_cast<size_t>(count), rocprim::plus<int64_t>(), ctx->stream));
-  DevBuf tmp;
+  Bytes tmp;
   if (int rc = dev_alloc(tmp, bytes)) return rc;
-  OSG_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, int64_t{0}, static_cast<size_t>(count), rocprim::plus<int64_t>(), ctx->stream));
+  OSG_HIP(rocprim::exclusive_scan(tmp.get(), bytes, in, out, int64_t{0}, static_cast<size_t>(count), rocprim::plus<int64_t>(), ctx->stream));
   OSG_HIP(hipStreamSynchronize(ctx->stream));   // tmp goes with this scope
   return OSG_OK;
 }
@@ -238,9 +227,9 @@ int scan_i64(osg_ctx* ctx, const int64_t* in, int64_t* out, int64_t count) {
 int sort_pairs(osg_ctx* ctx, const uint64_t* k_in, uint64_t* k_out, const uint32_t* v_in, uint32_t* v_out, int64_t m, int bits) {
   size_t bytes = 0;
   OSG_HIP(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, static_cast<size_t>(m), 0u, static_cast<unsigned>(bits), ctx->stream));
-  DevBuf tmp;
+  Bytes tmp;
   if (int rc = dev_alloc(tmp, bytes)) return rc;
-  OSG_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, k_in, k_out, v_in, v_out, static_cast<size_t>(m), 0u, static_cast<unsigned>(bits), ctx->stream));
+  OSG_HIP(rocprim::radix_sort_pairs(tmp.get(), bytes, k_in, k_out, v_in, v_out, static_cast<size_t>(m), 0u, static_cast<unsigned>(bits), ctx->stream));
   OSG_HIP(hipStreamSynchronize(ctx->stream));
   return OSG_OK;
 }
@@ -264,23 +253,23 @@ int solve_run(osg_solve* s, const typename G::Params& P, int64_t max_states) {
     Level& L = levels[0];
     L.n = 1;
     if (int rc = dev_alloc(L.words, sizeof(W) * state_words)) return rc;
-    if (int rc = dev_alloc(L.key_lo, sizeof(uint64_t))) return rc;
-    if (wide) if (int rc = dev_alloc(L.key_hi, sizeof(uint64_t))) return rc;
-    k_solve_root<G><<<dim3(1), dim3(kSolveBlock), 0, st>>>(P, L.words.as<W>(), L.key_lo.as<uint64_t>(), L.key_hi.as<uint64_t>());
+    if (int rc = dev_alloc(L.key_lo, 1)) return rc;
+    if (wide) if (int rc = dev_alloc(L.key_hi, 1)) return rc;
+    k_solve_root<G><<<dim3(1), dim3(kSolveBlock), 0, st>>>(P, words_of<W>(L.words), L.key_lo.get(), L.key_hi.get());
     OSG_HIP(hipGetLastError());
   }
   int64_t total = 1, total_edges = 0;
   for (int d = 0;; ++d) {
     Level& L = levels[d];
-    DevBuf count;
-    if (int rc = dev_alloc(count, sizeof(int64_t) * (L.n + 1))) return rc;
-    if (int rc = dev_alloc(L.edge_off, sizeof(int64_t) * (L.n + 1))) return rc;
-    k_solve_count<G><<<dim3(solve_grid(L.n + 1)), dim3(kSolveBlock), 0, st>>>(P, L.words.as<W>(), L.n, count.as<int64_t>());
+    DeviceArray<int64_t> count;
+    if (int rc = dev_alloc(count, L.n + 1)) return rc;
+    if (int rc = dev_alloc(L.edge_off, L.n + 1)) return rc;
+    k_solve_count<G><<<dim3(solve_grid(L.n + 1)), dim3(kSolveBlock), 0, st>>>(P, words_of<W>(L.words), L.n, count.get());
     OSG_HIP(hipGetLastError());
-    if (int rc = scan_i64(ctx, count.as<int64_t>(), L.edge_off.as<int64_t>(), L.n + 1)) return rc;
+    if (int rc = scan_i64(ctx, count.get(), L.edge_off.get(), L.n + 1)) return rc;
     count.reset();
     int64_t m = 0;
-    if (int rc = read_i64(ctx, L.edge_off.as<int64_t>() + L.n, &m)) return rc;
+    if (int rc = read_i64(ctx, L.edge_off.get() + L.n, &m)) return rc;
     L.edges = m;
     total_edges += m;
     if (m == 0) break;
@@ -295,49 +284,51 @@ int solve_run(osg_solve* s, const typename G::Params& P, int64_t max_states) {
                                             std::to_string(d + 1) + " plies");
     if (m > (int64_t{1} << 31) - 1)   // edge indices are 32-bit values of the sort
       return set_error(OSG_ERR_UNSUPPORTED, "osg_solve_create: a level with 2^31 or more children is not enumerated");
-    if (int rc = dev_alloc(L.edge_action, sizeof(int32_t) * m)) return rc;
-    if (int rc = dev_alloc(L.edge_child, sizeof(int64_t) * m)) return rc;
-    DevBuf child_words, lo, hi, index, lo_s, hi_s, index_s;
+    if (int rc = dev_alloc(L.edge_action, m)) return rc;
+    if (int rc = dev_alloc(L.edge_child, m)) return rc;
+    Bytes child_words;
+    DeviceArray<uint64_t> lo, hi, lo_s, hi_s;
+    DeviceArray<uint32_t> index, index_s;
     if (int rc = dev_alloc(child_words, sizeof(W) * state_words * m)) return rc;
-    if (int rc = dev_alloc(lo, sizeof(uint64_t) * m)) return rc;
-    if (int rc = dev_alloc(index, sizeof(uint32_t) * m)) return rc;
-    if (int rc = dev_alloc(lo_s, sizeof(uint64_t) * m)) return rc;
-    if (int rc = dev_alloc(index_s, sizeof(uint32_t) * m)) return rc;
-    if (wide) { if (int rc = dev_alloc(hi, sizeof(uint64_t) * m)) return rc; if (int rc = dev_alloc(hi_s, sizeof(uint64_t) * m)) return rc; }
+    if (int rc = dev_alloc(lo, m)) return rc;
+    if (int rc = dev_alloc(index, m)) return rc;
+    if (int rc = dev_alloc(lo_s, m)) return rc;
+    if (int rc = dev_alloc(index_s, m)) return rc;
+    if (wide) { if (int rc = dev_alloc(hi, m)) return rc; if (int rc = dev_alloc(hi_s, m)) return rc; }
     k_solve_expand<G><<<dim3(solve_grid(m)), dim3(kSolveBlock), 0, st>>>(
-        P, L.words.as<W>(), L.n, L.edge_off.as<int64_t>(), m, d, s->depth_limit, s->include_terminals ? 1 : 0, child_words.as<W>(),
-        lo.as<uint64_t>(), hi.as<uint64_t>(), L.edge_action.as<int32_t>(), index.as<uint32_t>());
+        P, words_of<W>(L.words), L.n, L.edge_off.get(), m, d, s->depth_limit, s->include_terminals ? 1 : 0, words_of<W>(child_words),
+        lo.get(), hi.get(), L.edge_action.get(), index.get());
     OSG_HIP(hipGetLastError());
-    if (int rc = sort_pairs(ctx, lo.as<uint64_t>(), lo_s.as<uint64_t>(), index.as<uint32_t>(), index_s.as<uint32_t>(), m, bits_lo)) return rc;
+    if (int rc = sort_pairs(ctx, lo.get(), lo_s.get(), index.get(), index_s.get(), m, bits_lo)) return rc;
     if (wide) {   // least significant word first; the second, stable pass orders by the high word
-      DevBuf hi_g;
-      if (int rc = dev_alloc(hi_g, sizeof(uint64_t) * m)) return rc;
-      k_solve_gather<<<dim3(solve_grid(m)), dim3(kSolveBlock), 0, st>>>(hi.as<uint64_t>(), index_s.as<uint32_t>(), m, hi_g.as<uint64_t>());
+      DeviceArray<uint64_t> hi_g;
+      if (int rc = dev_alloc(hi_g, m)) return rc;
+      k_solve_gather<<<dim3(solve_grid(m)), dim3(kSolveBlock), 0, st>>>(hi.get(), index_s.get(), m, hi_g.get());
       OSG_HIP(hipGetLastError());
-      if (int rc = sort_pairs(ctx, hi_g.as<uint64_t>(), hi_s.as<uint64_t>(), index_s.as<uint32_t>(), index.as<uint32_t>(), m, bits_hi)) return rc;
-      k_solve_gather<<<dim3(solve_grid(m)), dim3(kSolveBlock), 0, st>>>(lo.as<uint64_t>(), index.as<uint32_t>(), m, lo_s.as<uint64_t>());
+      if (int rc = sort_pairs(ctx, hi_g.get(), hi_s.get(), index_s.get(), index.get(), m, bits_hi)) return rc;
+      k_solve_gather<<<dim3(solve_grid(m)), dim3(kSolveBlock), 0, st>>>(lo.get(), index.get(), m, lo_s.get());
       OSG_HIP(hipGetLastError());
-      std::swap(index.p, index_s.p);
+      std::swap(index, index_s);
     }
-    DevBuf head, pos;
-    if (int rc = dev_alloc(head, sizeof(int64_t) * (m + 1))) return rc;
-    if (int rc = dev_alloc(pos, sizeof(int64_t) * (m + 1))) return rc;
-    k_solve_heads<<<dim3(solve_grid(m + 1)), dim3(kSolveBlock), 0, st>>>(lo_s.as<uint64_t>(), hi_s.as<uint64_t>(), m, head.as<int64_t>());
+    DeviceArray<int64_t> head, pos;
+    if (int rc = dev_alloc(head, m + 1)) return rc;
+    if (int rc = dev_alloc(pos, m + 1)) return rc;
+    k_solve_heads<<<dim3(solve_grid(m + 1)), dim3(kSolveBlock), 0, st>>>(lo_s.get(), hi_s.get(), m, head.get());
     OSG_HIP(hipGetLastError());
-    if (int rc = scan_i64(ctx, head.as<int64_t>(), pos.as<int64_t>(), m + 1)) return rc;
+    if (int rc = scan_i64(ctx, head.get(), pos.get(), m + 1)) return rc;
     int64_t u = 0;
-    if (int rc = read_i64(ctx, pos.as<int64_t>() + m, &u)) return rc;
+    if (int rc = read_i64(ctx, pos.get() + m, &u)) return rc;
     if (total + u > max_states)
       return set_error(OSG_ERR_UNSUPPORTED, "osg_solve_create: the game has more states than max_states (" + std::to_string(max_states) +
                                             "): " + std::to_string(total + u) + " after " + std::to_string(d + 1) + " plies");
     Level N;
     N.n = u;
     if (int rc = dev_alloc(N.words, sizeof(W) * state_words * u)) return rc;
-    if (int rc = dev_alloc(N.key_lo, sizeof(uint64_t) * u)) return rc;
-    if (wide) if (int rc = dev_alloc(N.key_hi, sizeof(uint64_t) * u)) return rc;
+    if (int rc = dev_alloc(N.key_lo, u)) return rc;
+    if (wide) if (int rc = dev_alloc(N.key_hi, u)) return rc;
     k_solve_compact<G><<<dim3(solve_grid(m)), dim3(kSolveBlock), 0, st>>>(
-        P, child_words.as<W>(), m, index_s.as<uint32_t>(), lo_s.as<uint64_t>(), hi_s.as<uint64_t>(), pos.as<int64_t>(), u, total,
-        N.words.as<W>(), N.key_lo.as<uint64_t>(), N.key_hi.as<uint64_t>(), L.edge_child.as<int64_t>());
+        P, words_of<W>(child_words), m, index_s.get(), lo_s.get(), hi_s.get(), pos.get(), u, total,
+        words_of<W>(N.words), N.key_lo.get(), N.key_hi.get(), L.edge_child.get());
     OSG_HIP(hipGetLastError());
     OSG_HIP(hipStreamSynchronize(st));   // the level's workspaces go here
     if (u == 0) break;
@@ -351,27 +342,27 @@ int solve_run(osg_solve* s, const typename G::Params& P, int64_t max_states) {
   s->edges = total_edges;
   s->level_off.assign(nl + 1, 0);
   for (int d = 0; d < nl; ++d) s->level_off[d + 1] = s->level_off[d] + levels[d].n;
-  if (int rc = dev_alloc(s->key_lo, sizeof(uint64_t) * total)) return rc;
-  if (wide) if (int rc = dev_alloc(s->key_hi, sizeof(uint64_t) * total)) return rc;
-  if (int rc = dev_alloc(s->d_level_off, sizeof(int64_t) * (nl + 1))) return rc;
-  if (int rc = dev_alloc(s->edge_off, sizeof(int64_t) * (total + 1))) return rc;
-  if (int rc = dev_alloc(s->edge_action, sizeof(int32_t) * total_edges)) return rc;
-  if (int rc = dev_alloc(s->edge_child, sizeof(int64_t) * total_edges)) return rc;
-  if (int rc = dev_alloc(s->value, sizeof(double) * total)) return rc;
-  if (int rc = dev_alloc(s->optimal, sizeof(uint32_t) * s->mask_words * total)) return rc;
-  if (int rc = dev_alloc(s->distance, sizeof(int32_t) * total)) return rc;
-  OSG_HIP(hipMemcpyAsync(s->d_level_off.p, s->level_off.data(), sizeof(int64_t) * (nl + 1), hipMemcpyHostToDevice, st));
+  if (int rc = dev_alloc(s->key_lo, total)) return rc;
+  if (wide) if (int rc = dev_alloc(s->key_hi, total)) return rc;
+  if (int rc = dev_alloc(s->d_level_off, nl + 1)) return rc;
+  if (int rc = dev_alloc(s->edge_off, total + 1)) return rc;
+  if (int rc = dev_alloc(s->edge_action, total_edges)) return rc;
+  if (int rc = dev_alloc(s->edge_child, total_edges)) return rc;
+  if (int rc = dev_alloc(s->value, total)) return rc;
+  if (int rc = dev_alloc(s->optimal, s->mask_words * total)) return rc;
+  if (int rc = dev_alloc(s->distance, total)) return rc;
+  OSG_HIP(hipMemcpyAsync(s->d_level_off.get(), s->level_off.data(), sizeof(int64_t) * (nl + 1), hipMemcpyHostToDevice, st));
   int64_t ebase = 0;
   for (int d = 0; d < nl; ++d) {
     Level& L = levels[d];
     const int64_t o = s->level_off[d];
-    OSG_HIP(hipMemcpyAsync(s->key_lo.as<uint64_t>() + o, L.key_lo.p, sizeof(uint64_t) * L.n, hipMemcpyDeviceToDevice, st));
-    if (wide) OSG_HIP(hipMemcpyAsync(s->key_hi.as<uint64_t>() + o, L.key_hi.p, sizeof(uint64_t) * L.n, hipMemcpyDeviceToDevice, st));
-    k_solve_shift<<<dim3(solve_grid(L.n + 1)), dim3(kSolveBlock), 0, st>>>(L.edge_off.as<int64_t>(), L.n + 1, ebase, s->edge_off.as<int64_t>() + o);
+    OSG_HIP(hipMemcpyAsync(s->key_lo.get() + o, L.key_lo.get(), sizeof(uint64_t) * L.n, hipMemcpyDeviceToDevice, st));
+    if (wide) OSG_HIP(hipMemcpyAsync(s->key_hi.get() + o, L.key_hi.get(), sizeof(uint64_t) * L.n, hipMemcpyDeviceToDevice, st));
+    k_solve_shift<<<dim3(solve_grid(L.n + 1)), dim3(kSolveBlock), 0, st>>>(L.edge_off.get(), L.n + 1, ebase, s->edge_off.get() + o);
     OSG_HIP(hipGetLastError());
     if (L.edges > 0) {
-      OSG_HIP(hipMemcpyAsync(s->edge_action.as<int32_t>() + ebase, L.edge_action.p, sizeof(int32_t) * L.edges, hipMemcpyDeviceToDevice, st));
-      OSG_HIP(hipMemcpyAsync(s->edge_child.as<int64_t>() + ebase, L.edge_child.p, sizeof(int64_t) * L.edges, hipMemcpyDeviceToDevice, st));
+      OSG_HIP(hipMemcpyAsync(s->edge_action.get() + ebase, L.edge_action.get(), sizeof(int32_t) * L.edges, hipMemcpyDeviceToDevice, st));
+      OSG_HIP(hipMemcpyAsync(s->edge_child.get() + ebase, L.edge_child.get(), sizeof(int64_t) * L.edges, hipMemcpyDeviceToDevice, st));
     }
     ebase += L.edges;
   }
@@ -383,19 +374,19 @@ int solve_run(osg_solve* s, const typename G::Params& P, int64_t max_states) {
   }
 
   // backward
-  DevBuf term;
-  if (int rc = dev_alloc(term, sizeof(unsigned long long))) return rc;
-  OSG_HIP(hipMemsetAsync(term.p, 0, sizeof(unsigned long long), st));
+  DeviceArray<unsigned long long> term;
+  if (int rc = dev_alloc(term, 1)) return rc;
+  OSG_HIP(hipMemsetAsync(term.get(), 0, sizeof(unsigned long long), st));
   for (int d = nl - 1; d >= 0; --d) {
     const int64_t n = s->level_off[d + 1] - s->level_off[d];
     k_solve_level<G><<<dim3(solve_grid(n)), dim3(kSolveBlock), 0, st>>>(
-        P, s->level_words[d].as<W>(), n, s->level_off[d], s->edge_off.as<int64_t>(), s->edge_action.as<int32_t>(),
-        s->edge_child.as<int64_t>(), s->value.as<double>(), s->optimal.as<uint32_t>(), s->mask_words, s->distance.as<int32_t>(),
-        term.as<unsigned long long>());
+        P, words_of<W>(s->level_words[d]), n, s->level_off[d], s->edge_off.get(), s->edge_action.get(),
+        s->edge_child.get(), s->value.get(), s->optimal.get(), s->mask_words, s->distance.get(),
+        term.get());
     OSG_HIP(hipGetLastError());
   }
   unsigned long long h_term = 0;
-  OSG_HIP(hipMemcpyAsync(&h_term, term.p, sizeof(h_term), hipMemcpyDeviceToHost, st));
+  OSG_HIP(hipMemcpyAsync(&h_term, term.get(), sizeof(h_term), hipMemcpyDeviceToHost, st));
   OSG_HIP(hipStreamSynchronize(st));
   s->terminals = static_cast<int64_t>(h_term);
   return OSG_OK;
@@ -436,6 +427,7 @@ extern "C" int osg_solve_create(osg_ctx* ctx, const char* game_string, int32_t d
   }
   s->ctx = ctx;
   ctx_retain(ctx);
+  s->held.ctx = ctx;
   s->depth_limit = depth_limit;
   s->include_terminals = include_terminals != 0;
   osg_solve* raw = s.get();
@@ -482,7 +474,7 @@ extern "C" int osg_solve_states(const osg_solve* s, osg_batch* dst) {
     const int64_t o = s->level_off[d], n = s->level_off[d + 1] - o;
     for (int k = 0; k < planes; ++k)
       OSG_HIP(hipMemcpyAsync(static_cast<char*>(dst->d_words) + (static_cast<size_t>(k) * s->n + o) * wb,
-                             s->level_words[d].as<char>() + static_cast<size_t>(k) * n * wb, static_cast<size_t>(n) * wb,
+                             words_of<char>(s->level_words[d]) + static_cast<size_t>(k) * n * wb, static_cast<size_t>(n) * wb,
                              hipMemcpyDeviceToDevice, dst->ctx->stream));
   }
   return OSG_OK;
@@ -490,23 +482,23 @@ extern "C" int osg_solve_states(const osg_solve* s, osg_batch* dst) {
 
 extern "C" int osg_solve_values(const osg_solve* s, double* value, int on_host) {
   if (!s || !value) return set_error(OSG_ERR_INVALID, "osg_solve_values: null argument");
-  return copy_out(const_cast<osg_solve*>(s), value, s->value.p, sizeof(double) * s->n, on_host);
+  return copy_out(const_cast<osg_solve*>(s), value, s->value.get(), sizeof(double) * s->n, on_host);
 }
 
 extern "C" int osg_solve_optimal(const osg_solve* s, uint32_t* mask, int32_t* distance, int on_host) {
   if (!s) return set_error(OSG_ERR_INVALID, "osg_solve_optimal: null argument");
   osg_solve* m = const_cast<osg_solve*>(s);
-  if (mask) if (int rc = copy_out(m, mask, s->optimal.p, sizeof(uint32_t) * s->mask_words * s->n, on_host)) return rc;
-  if (distance) if (int rc = copy_out(m, distance, s->distance.p, sizeof(int32_t) * s->n, on_host)) return rc;
+  if (mask) if (int rc = copy_out(m, mask, s->optimal.get(), sizeof(uint32_t) * s->mask_words * s->n, on_host)) return rc;
+  if (distance) if (int rc = copy_out(m, distance, s->distance.get(), sizeof(int32_t) * s->n, on_host)) return rc;
   return OSG_OK;
 }
 
 extern "C" int osg_solve_edges(const osg_solve* s, int64_t* edge_off, int32_t* action, int64_t* child, int on_host) {
   if (!s) return set_error(OSG_ERR_INVALID, "osg_solve_edges: null argument");
   osg_solve* m = const_cast<osg_solve*>(s);
-  if (edge_off) if (int rc = copy_out(m, edge_off, s->edge_off.p, sizeof(int64_t) * (s->n + 1), on_host)) return rc;
-  if (action && s->edges) if (int rc = copy_out(m, action, s->edge_action.p, sizeof(int32_t) * s->edges, on_host)) return rc;
-  if (child && s->edges) if (int rc = copy_out(m, child, s->edge_child.p, sizeof(int64_t) * s->edges, on_host)) return rc;
+  if (edge_off) if (int rc = copy_out(m, edge_off, s->edge_off.get(), sizeof(int64_t) * (s->n + 1), on_host)) return rc;
+  if (action && s->edges) if (int rc = copy_out(m, action, s->edge_action.get(), sizeof(int32_t) * s->edges, on_host)) return rc;
+  if (child && s->edges) if (int rc = copy_out(m, child, s->edge_child.get(), sizeof(int64_t) * s->edges, on_host)) return rc;
   return OSG_OK;
 }
 
@@ -529,8 +521,8 @@ extern "C" int osg_solve_lookup(const osg_solve* s, const osg_batch* query, int6
         if constexpr (!solve_served<G>()) return set_error(OSG_ERR_UNSUPPORTED, "osg_solve_lookup: no enumeration for this game layout");
         else {
           k_solve_lookup<G><<<dim3(solve_grid(nq)), dim3(kSolveBlock), 0, ctx->stream>>>(
-              P, static_cast<const typename G::word_t*>(query->d_words), nq, s->d_level_off.as<int64_t>(), levels,
-              s->key_lo.as<uint64_t>(), s->wide ? s->key_hi.as<uint64_t>() : nullptr, d_index);
+              P, static_cast<const typename G::word_t*>(query->d_words), nq, s->d_level_off.get(), levels,
+              s->key_lo.get(), s->wide ? s->key_hi.get() : nullptr, d_index);
           return OSG_OK;
         }
       })) return rc;
