@@ -685,7 +685,7 @@ int osg_information_state_string(const osg_batch* b, int64_t index, int player, 
     return set_error(OSG_ERR_INVALID, "this game provides no information state string");
   if (player < 0 || player >= d.num_players) return set_error(OSG_ERR_INVALID, "player id out of range");
   uint64_t w[5] = {0, 0, 0, 0, 0};   // (leduc_poker with 4+ players: five plane words)
-  const char* base = static_cast<const char*>(b->d_words);
+  const char* base = static_cast<const char*>(b->words());
   for (int k = 0; k < d.state_words; ++k)
     OSG_HIP(hipMemcpyAsync(&w[k], base + (static_cast<size_t>(k) * b->n + index) * sizeof(uint64_t), sizeof(uint64_t),
                            hipMemcpyDeviceToHost, b->ctx->stream));
@@ -702,7 +702,7 @@ int osg_observation_string(const osg_batch* b, int64_t index, int player, char* 
   const osg_game_desc& d = b->spec.desc;
   if (player < 0 || player >= d.num_players) return set_error(OSG_ERR_INVALID, "player id out of range");
   uint64_t w[4 * 12 + 1] = {0};   // (hex 19 x 19: 4 planes of 12 words and the meta word)
-  const char* base = static_cast<const char*>(b->d_words);
+  const char* base = static_cast<const char*>(b->words());
   for (int k = 0; k < d.state_words; ++k)
     OSG_HIP(hipMemcpyAsync(&w[k], base + (static_cast<size_t>(k) * b->n + index) * d.state_word_bytes, d.state_word_bytes,
                            hipMemcpyDeviceToHost, b->ctx->stream));
@@ -786,7 +786,7 @@ namespace {
 // The packed words of one state, on the host.
 int fetch_state_words(const osg_batch* b, int64_t index, uint64_t* w) {
   const osg_game_desc& d = b->spec.desc;
-  const char* base = static_cast<const char*>(b->d_words);
+  const char* base = static_cast<const char*>(b->words());
   for (int k = 0; k < d.state_words; ++k)
     OSG_HIP(hipMemcpyAsync(&w[k], base + (static_cast<size_t>(k) * b->n + index) * d.state_word_bytes, d.state_word_bytes,
                            hipMemcpyDeviceToHost, b->ctx->stream));

@@ -1,6 +1,6 @@
 // Owners of device and pinned host memory: an allocation goes with the object (or scope) that holds its owner, so a
 // handle type keeps no list of what to free and a failure path frees nothing by hand.  These are the only places
-// outside the context's own grow-only buffers that call the runtime's allocation functions.
+// that call the runtime's allocation functions.
 #ifndef OSG_DEVICE_BUFFER_H_
 #define OSG_DEVICE_BUFFER_H_
 

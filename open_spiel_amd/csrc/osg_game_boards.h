@@ -1,6 +1,6 @@
 // Device-side rules of the three perfect-information board games, on bitboards.
 // Each struct restates one reference State implementation for ONE state held in
-// registers; the kernels in osg_kernels.hip map them over SoA batches.
+// registers; the kernels of the batch units (osg_batch_internal.h) map them over SoA batches.
 //
 //   Ttt : open_spiel/games/tic_tac_toe/tic_tac_toe.{h,cc}
 //   C4  : open_spiel/games/connect_four/connect_four.{h,cc}

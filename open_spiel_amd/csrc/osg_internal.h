@@ -76,7 +76,7 @@ int for_hex(Spec& spec, F&& f) {
 }
 // The concrete game type a spec names: f(TypeTag<G>, its G::Params).  Every layout is here (the hex boards above 128
 // actions, connect_four above 64 board bits and leduc_poker with 4+ players included): the batch entry points of
-// osg_kernels.hip — states, masks, steps, tensors, random steps, rollouts, environment steps — and the lane-per-root
+// osg_batch_internal.h's units — states, masks, steps, tensors, random steps, rollouts, environment steps — and the lane-per-root
 // searches of osg_mcts.hip / osg_mcts_step.hip go through it.  The wave-per-root search and the solvers' tree builder
 // serve fewer layouts and keep switches of their own.
 template <class F>
@@ -136,17 +136,13 @@ struct osg_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  unsigned long long* d_illegal = nullptr;  // device counter of illegal applies
-  void* d_scratch = nullptr;                // reusable staging buffer
-  size_t scratch_bytes = 0;
-  void* h_pinned = nullptr;
-  size_t pinned_bytes = 0;
-  void* d_mcts_pool = nullptr;              // MCTS node pool, grow-only, reused across searches
-  size_t mcts_pool_bytes = 0;
-  double* d_mcts_logs = nullptr;            // log(n) table shared with the host libm
-  int mcts_logs_n = 0;
-  int32_t* d_mcts_queue = nullptr;          // wave-per-root search as a work queue: [0] next ticket, [1..256] the cost
-  int64_t mcts_queue_roots = 0;             // histogram / bucket offsets, then the root order [roots] (grow-only)
+  osg::DeviceArray<unsigned long long> d_illegal;  // device counter of illegal applies
+  // Grow-only, reused from call to call (osg::ctx_grow); osg_ctx_trim gives the scratch, the pool and the queue back.
+  osg::DeviceArray<unsigned char> d_scratch;       // reusable staging buffer
+  osg::DeviceArray<unsigned char> d_mcts_pool;     // MCTS node pool, reused across searches
+  osg::DeviceArray<double> d_mcts_logs;            // log(n) table shared with the host libm
+  osg::DeviceArray<int32_t> d_mcts_queue;          // wave-per-root search as a work queue: [0] next ticket, [1..256] the cost
+                                                   // histogram / bucket offsets, then the root order [roots]
   int num_cus = 0;
   // Lifetime: the creator holds one reference, every batch / solver / communicator made on the context
   // another; osg_ctx_destroy drops the creator's, and the device resources go with the last one, so a
@@ -157,14 +153,18 @@ struct osg_ctx {
 namespace osg {
 void ctx_retain(osg_ctx* ctx);
 void ctx_release(osg_ctx* ctx);
+// Growth of one of the context's grow-only buffers: a request beyond the capacity waits for the context's stream (a
+// queued kernel may still use the old block) and reallocates, contents lost; any other request does nothing.
+template <class T>
+hipError_t ctx_grow(osg_ctx* ctx, DeviceArray<T>& buf, size_t n);
 }
 
 struct osg_batch {
   osg_ctx* ctx = nullptr;
   osg::GameSpec spec;
   int64_t n = 0;
-  void* d_words = nullptr;  // state_words planes of n elements
-  size_t bytes = 0;
+  osg::DeviceArray<unsigned char> d_words;  // state_words planes of n elements (u32 or u64: the game's word type)
+  void* words() const { return d_words.get(); }
 };
 
 #define OSG_HIP(call)                                                              \
@@ -194,8 +194,11 @@ int upload(const std::vector<T>& v, DeviceArray<T>& d, hipStream_t stream) {
 }
 }  // namespace osg
 
-// Scratch helpers (device + pinned host staging owned by the context).
+// The context's staging buffer, at least `bytes` long (grows by half again beyond a request it cannot hold).
 int osg_ctx_scratch(osg_ctx* ctx, size_t bytes, void** out);
-int osg_ctx_pinned(osg_ctx* ctx, size_t bytes, void** out);
+namespace osg {
+// Offsets of the pieces a caller carves out of it: multiples of 256 bytes, like the allocation itself.
+inline size_t align_up(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
+}  // namespace osg
 
 #endif  // OSG_INTERNAL_H_

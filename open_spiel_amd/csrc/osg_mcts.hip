@@ -384,10 +384,10 @@ extern "C" int osg_mcts_search(const osg_batch* roots, const osg_mcts_cfg* cfg_i
     cap = never;
   }
   if (cap < 1 + widest) cap = 1 + widest;
-  if (static_cast<size_t>(cap) * n * (gc_nodes > 0 ? 28 : 24) > ctx->mcts_pool_bytes) {
+  if (static_cast<size_t>(cap) * n * (gc_nodes > 0 ? 28 : 24) > ctx->d_mcts_pool.size()) {
     size_t free_b = 0, total_b = 0;
     OSG_HIP(hipMemGetInfo(&free_b, &total_b));
-    free_b += ctx->mcts_pool_bytes;  // the old pool is released before the new one is allocated
+    free_b += ctx->d_mcts_pool.size();  // the old pool is released before the new one is allocated
     if (gc_nodes > 0) {
       if (static_cast<size_t>(cap) * n * 28 > free_b * 9 / 10)
         return set_error(OSG_ERR_NOMEM, "osg_mcts_search: max_nodes slots per root do not fit the free HBM");
@@ -401,16 +401,8 @@ extern "C" int osg_mcts_search(const osg_batch* roots, const osg_mcts_cfg* cfg_i
   cfg.max_nodes = static_cast<int32_t>(cap);
   const size_t slots = static_cast<size_t>(cap) * n;
   const size_t pool_bytes = slots * per_node;
-  if (pool_bytes > ctx->mcts_pool_bytes) {
-    OSG_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_mcts_pool) OSG_HIP(hipFree(ctx->d_mcts_pool));
-    ctx->d_mcts_pool = nullptr;
-    ctx->mcts_pool_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->d_mcts_pool, pool_bytes);
-    if (e != hipSuccess) return set_error(OSG_ERR_NOMEM, std::string("MCTS node pool: ") + hipGetErrorString(e));
-    ctx->mcts_pool_bytes = pool_bytes;
-  }
-  char* pool_mem = static_cast<char*>(ctx->d_mcts_pool);
+  if (int rc = nomem_error(ctx_grow(ctx, ctx->d_mcts_pool, pool_bytes), "MCTS node pool: ")) return rc;
+  char* pool_mem = reinterpret_cast<char*>(ctx->d_mcts_pool.get());
   Pool pool;
   pool.total = reinterpret_cast<double*>(pool_mem);
   pool.meta = reinterpret_cast<uint32_t*>(pool_mem + slots * 8);
@@ -428,24 +420,18 @@ extern "C" int osg_mcts_search(const osg_batch* roots, const osg_mcts_cfg* cfg_i
 
   // log(parent explore_count) from the host libm: the CPU oracle (and the reference) call
   // std::log, so sharing the table makes UCT values bit-equal.  Cached in the context.
-  if (cfg.max_simulations + 2 > ctx->mcts_logs_n) {
-    const int want = cfg.max_simulations + 2;
+  if (const size_t want = static_cast<size_t>(cfg.max_simulations) + 2; want > ctx->d_mcts_logs.size()) {
     std::vector<double> logs(want);
     logs[0] = 0.0;
-    for (int i = 1; i < want; ++i) logs[i] = std::log(static_cast<double>(i));
-    OSG_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_mcts_logs) OSG_HIP(hipFree(ctx->d_mcts_logs));
-    ctx->d_mcts_logs = nullptr;
-    ctx->mcts_logs_n = 0;
-    OSG_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_mcts_logs), want * sizeof(double)));
+    for (size_t i = 1; i < want; ++i) logs[i] = std::log(static_cast<double>(i));
+    OSG_HIP(ctx_grow(ctx, ctx->d_mcts_logs, want));
     OSG_HIP(hipMemcpy(ctx->d_mcts_logs, logs.data(), want * sizeof(double), hipMemcpyHostToDevice));
-    ctx->mcts_logs_n = want;
   }
   const double* d_logs = ctx->d_mcts_logs;
 
   // host-side outputs are staged through scratch
   size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~static_cast<size_t>(255); return o; };
+  auto carve = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
   const size_t o_best = carve(sizeof(int32_t) * n), o_vis = carve(sizeof(int32_t) * n * A),
                o_rew = carve(sizeof(double) * n * A), o_out = carve(static_cast<size_t>(n) * A),
                o_stats = carve(sizeof(double) * n * 4);
@@ -474,7 +460,7 @@ extern "C" int osg_mcts_search(const osg_batch* roots, const osg_mcts_cfg* cfg_i
           return for_game(roots->spec, [&](auto g, const auto& P) {
             using G = typename decltype(g)::type;
             k_mcts<G, decltype(brd)::value><<<dim3(grid), dim3(kBlockM), shuffle_lds, ctx->stream>>>(
-                P, static_cast<const typename G::word_t*>(roots->d_words), n, d.num_players, A, cfg,
+                P, static_cast<const typename G::word_t*>(roots->words()), n, d.num_players, A, cfg,
                 d.max_utility, d_logs, pool, d_best, d_vis, d_rew, d_out, d_stats);
             return OSG_OK;
           });

@@ -1016,8 +1016,8 @@ int osg_mcts_tree_advance(osg_mcts_tree* t, osg_batch* leaf, const double* d_pri
       return for_game(t->roots->spec, [&](auto g, const auto& P) {
         using G = typename decltype(g)::type;
         k_mcts_advance<G, decltype(board)::value, decltype(co)::value><<<dim3(blocks), dim3(threads), lds, st>>>(
-            P, static_cast<const typename G::word_t*>(t->roots->d_words),
-            static_cast<typename G::word_t*>(leaf->d_words), t->n, d.num_players, t->A, t->cfg,
+            P, static_cast<const typename G::word_t*>(t->roots->words()),
+            static_cast<typename G::word_t*>(leaf->words()), t->n, d.num_players, t->A, t->cfg,
             t->flags, t->max_utility, t->d_logs, pool, d_prior, d_value, d_request,
             max_new_simulations, stride);
         return OSG_OK;
@@ -1083,7 +1083,7 @@ int osg_mcts_tree_rollout_values(osg_mcts_tree* t, const osg_batch* leaf, double
   if (int rc = for_game(t->roots->spec, [&](auto g, const auto& P) {
         using G = typename decltype(g)::type;
         k_mcts_tree_rollout<G><<<dim3(grid), dim3(kBlockM), 0, t->ctx->stream>>>(
-            P, static_cast<const typename G::word_t*>(leaf->d_words), t->n, t->P, t->cfg, pool.phase,
+            P, static_cast<const typename G::word_t*>(leaf->words()), t->n, t->P, t->cfg, pool.phase,
             pool.sims, d_value, lane_stride);
         return OSG_OK;
       })) return rc;

@@ -1465,7 +1465,7 @@ int launch(const typename G::Params& P, const osg_batch* roots, const osg_mcts_c
   osg_ctx* ctx = roots->ctx;
   hipStream_t st = ctx->stream;
   const int64_t n = roots->n;
-  const auto* words = static_cast<const typename G::word_t*>(roots->d_words);
+  const auto* words = static_cast<const typename G::word_t*>(roots->words());
   const bool gc = pool.gc_nodes > 1 && pool.remap;
   const Schedule sc = schedule_from_env(wave_wpe<G, kHexFill>());
   if (ctx->num_cus == 0) {
@@ -1492,13 +1492,7 @@ int launch(const typename G::Params& P, const osg_batch* roots, const osg_mcts_c
     return OSG_OK;
   }
   if constexpr (kQueue) {
-  if (ctx->mcts_queue_roots < n) {
-    if (ctx->d_mcts_queue) OSG_HIP(hipFree(ctx->d_mcts_queue));
-    ctx->d_mcts_queue = nullptr;
-    ctx->mcts_queue_roots = 0;
-    OSG_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_mcts_queue), sizeof(int32_t) * (kQueueHeader + static_cast<size_t>(n))));
-    ctx->mcts_queue_roots = n;
-  }
+  OSG_HIP(ctx_grow(ctx, ctx->d_mcts_queue, kQueueHeader + static_cast<size_t>(n)));
   int32_t* ticket = ctx->d_mcts_queue;
   int32_t* hist = ctx->d_mcts_queue + 1;
   int32_t* order = ctx->d_mcts_queue + kQueueHeader;

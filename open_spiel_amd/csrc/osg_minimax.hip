@@ -182,7 +182,7 @@ extern "C" int osg_alpha_beta_search(const osg_batch* roots, const osg_ab_cfg* c
       blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, static_cast<int64_t>(kAbStackBudget / (per_lane * kAbBlock))));
       const int64_t lanes = blocks * kAbBlock;
       size_t off = 0;
-      auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~static_cast<size_t>(255); return o; };
+      auto carve = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
       const size_t o_ticket = carve(sizeof(unsigned long long)), o_stack = carve(per_lane * lanes),
                    o_value = carve(on_host ? sizeof(double) * n : 0), o_nodes = carve(on_host ? sizeof(int64_t) * n : 0),
                    o_best = carve(on_host ? sizeof(int32_t) * n : 0), o_status = carve(on_host ? static_cast<size_t>(n) : 0);
@@ -195,7 +195,7 @@ extern "C" int osg_alpha_beta_search(const osg_batch* roots, const osg_ab_cfg* c
       uint8_t* d_status = on_host ? reinterpret_cast<uint8_t*>(sc + o_status) : status;
       OSG_HIP(hipMemsetAsync(sc + o_ticket, 0, sizeof(unsigned long long), ctx->stream));
       k_alpha_beta<G><<<dim3(static_cast<unsigned>(blocks)), dim3(kAbBlock), 0, ctx->stream>>>(
-          P, static_cast<const typename G::word_t*>(roots->d_words), n, cfg,
+          P, static_cast<const typename G::word_t*>(roots->words()), n, cfg,
           reinterpret_cast<unsigned long long*>(sc + o_ticket), reinterpret_cast<uint64_t*>(sc + o_stack), stack_plies,
           d_value, d_best, d_nodes, d_status);
       OSG_HIP(hipGetLastError());

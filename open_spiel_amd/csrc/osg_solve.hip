@@ -473,7 +473,7 @@ extern "C" int osg_solve_states(const osg_solve* s, osg_batch* dst) {
   for (size_t d = 0; d + 1 < s->level_off.size(); ++d) {
     const int64_t o = s->level_off[d], n = s->level_off[d + 1] - o;
     for (int k = 0; k < planes; ++k)
-      OSG_HIP(hipMemcpyAsync(static_cast<char*>(dst->d_words) + (static_cast<size_t>(k) * s->n + o) * wb,
+      OSG_HIP(hipMemcpyAsync(static_cast<char*>(dst->words()) + (static_cast<size_t>(k) * s->n + o) * wb,
                              words_of<char>(s->level_words[d]) + static_cast<size_t>(k) * n * wb, static_cast<size_t>(n) * wb,
                              hipMemcpyDeviceToDevice, dst->ctx->stream));
   }
@@ -521,7 +521,7 @@ extern "C" int osg_solve_lookup(const osg_solve* s, const osg_batch* query, int6
         if constexpr (!solve_served<G>()) return set_error(OSG_ERR_UNSUPPORTED, "osg_solve_lookup: no enumeration for this game layout");
         else {
           k_solve_lookup<G><<<dim3(solve_grid(nq)), dim3(kSolveBlock), 0, ctx->stream>>>(
-              P, static_cast<const typename G::word_t*>(query->d_words), nq, s->d_level_off.get(), levels,
+              P, static_cast<const typename G::word_t*>(query->words()), nq, s->d_level_off.get(), levels,
               s->key_lo.get(), s->wide ? s->key_hi.get() : nullptr, d_index);
           return OSG_OK;
         }

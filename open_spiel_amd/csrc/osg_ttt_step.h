@@ -4,7 +4,7 @@
 // LegalActions (tic_tac_toe.cc:138-148) and the status byte.  BOTH players' eight lines are tested in one pass
 // over the packed word: the two 9-bit boards sit 16 bits apart and no shift below reaches from one into a
 // tested bit of the other.  Host + device so that a CPU test can drive exactly this code over random games
-// (tests/test_c4_step_host.py); the kernel is k_step_vec<Ttt, ...> in osg_kernels.hip.
+// (tests/test_c4_step_host.py); the kernel is k_step_vec<Ttt, ...> in osg_step.hip.
 #ifndef OSG_TTT_STEP_H_
 #define OSG_TTT_STEP_H_
 

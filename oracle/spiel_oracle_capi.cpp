@@ -420,7 +420,7 @@ int osgo_random_playouts(void* g, uint64_t seed, int64_t n, int L, int W,
 }
 
 // ---------------------------------------------------------------------------
-// SURVEY.md 8(d) synthetic benchmark inputs: the CPU side of osg_synth_batch (open_spiel_amd/csrc/osg_kernels.hip
+// SURVEY.md 8(d) synthetic benchmark inputs: the CPU side of osg_synth_batch (open_spiel_amd/csrc/osg_playout.hip
 // k_synth), restated call for call so that the batch a benchmark times on the device can be regenerated and
 // checked state for state:
 //   rng = CounterRng(seed, first + i, "SYNTH"); depth = rng.Below(depth_mod);

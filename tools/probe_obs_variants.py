@@ -1,4 +1,4 @@
-"""Tensor-pack kernels per library variant (tools/build_variant.sh with SRC=osg_kernels): python tools/probe_obs_variants.py lib1.so lib2.so"""
+"""Tensor-pack kernels per library variant (tools/build_variant.sh with SRC=osg_observation): python tools/probe_obs_variants.py lib1.so lib2.so"""
 import os, subprocess, sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CHILD = r'''

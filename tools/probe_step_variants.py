@@ -1,4 +1,4 @@
-"""A/B of the connect_four fused step over library variants (tools/build_variant.sh with SRC=osg_kernels):
+"""A/B of the connect_four fused step over library variants (tools/build_variant.sh with SRC=osg_step):
 HIP-event time per launch at 2^20 and 2^24 states, each library in its own process."""
 import glob, os, subprocess, sys
 HERE = os.path.dirname(os.path.abspath(__file__))

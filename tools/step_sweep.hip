@@ -30,7 +30,7 @@ __device__ __forceinline__ uint32_t open_mul(uint64_t x, uint64_t o) {
 template <int V>
 __device__ __forceinline__ void step_v(const G::Params& p, uint64_t& x, uint64_t& o, int a, uint32_t& m, uint32_t& st) {
   if (V == 5) { const uint32_t r = c4_fused_step(x, o, (uint32_t)a); m = r & 0xFF; st = r >> 8; return; }  // round 2: osg_c4_step.h
-  if (V == 3) {  // the round-1 logic (osg_kernels.hip k_step_c4x2): result flags in plane 0's top byte
+  if (V == 3) {  // the round-1 logic (osg_step.hip k_step_c4x2): result flags in plane 0's top byte
     G::State s = G::unpack(x, o);
     bool term = G::terminal(p, s);
     bool illegal = false;
