@@ -6,12 +6,14 @@
 // itself sequential.  The SIMT-efficient unit of parallelism is therefore the
 // root: 64 independent searches per wavefront, every lane running the same
 // select / expand / rollout / backup code on its own tree.  (A wave-per-root
-// layout with children spread over lanes keeps 63 of 64 lanes idle during the
-// playout, which is >90 % of the work; see DESIGN.md.)
+// layout spreads a node's children over the lanes and leaves 63 of 64 lanes idle
+// in a move-by-move playout; where the playout itself is lane-parallel — hex
+// without the swap rule: one random fill of the board — it is the faster one and
+// layout = 0 picks it, osg_mcts_wave.hip)
 //
 // Tree storage in HBM: a node pool of `cap` nodes per root, struct-of-arrays and — since round 6 — root-major
 // (field[root * cap + node]): a lane scans and writes runs of its own tree (rounds 1-5: root-minor, which coalesces
-// across lanes only near the root; see the macros in k_mcts).
+// across lanes only near the root; see k_mcts).
 //   meta   u32  action | (player+1)<<8 | nchild<<12 | has_outcome<<20 | code<<21 | terminal<<23
 //   first  u32  index of the first child (children are contiguous)
 //   parent u32
@@ -21,7 +23,7 @@
 #include <cmath>
 #include <vector>
 
-#include "osg_mcts_internal.h"
+#include "osg_mcts_lane.h"
 
 using namespace osg;
 
@@ -43,30 +45,23 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
   act_t* sh = reinterpret_cast<act_t*>(s_shuffle) + threadIdx.x;
   (void)sh;
   const uint64_t gr = static_cast<uint64_t>(cfg.index_offset + r);
-  // Node i of this lane's root in every plane: i * NR + RB.  Round 6: ROOT-MAJOR (field[root * cap + node], the wave layout's
-  // form: NR = 1, RB = root * cap) — a root's nodes are contiguous, so a lane's scan of a node's children and the stores of
-  // an expansion walk ONE run of memory (32 children's counts per 128-byte line) instead of one line per child and field;
-  // root-minor (field[node * n_roots + root]: NR = n_roots, RB = root; rounds 1-5) coalesces across lanes only while the
-  // lanes stand on the same node index, i.e. near the root.  2^16 roots (profiles/r06zf_*, r06zi_*): hex(9) x 512
-  // simulations 4.5e8 -> 7.2e8, 11 x 11 2.2e8 -> 4.4e8, 13 x 13 1.2e8 -> 2.9e8, tic_tac_toe x 1000 8.2e8 -> 9.9e8,
-  // connect_four x 256 1.35e9 -> 1.42e9 simulations/s; SHORT searches of narrow games stay near the root and keep
-  // root-minor (connect_four x 32: 2.78e9 against 2.27e9, tic_tac_toe x 100: 2.09e9 against 1.89e9): the host picks
-  // (pool.root_major; OSG_MCTS_ROOT_MAJOR=0/1 forces one).
-  const int64_t NR = pool.root_major ? 1 : pool.n_roots, RB = pool.root_major ? r * static_cast<int64_t>(pool.cap) : r;
-#define META(i) pool.meta[static_cast<int64_t>(i) * NR + RB]
-#define FIRST(i) pool.first[static_cast<int64_t>(i) * NR + RB]
-#define PARENT(i) pool.parent[static_cast<int64_t>(i) * NR + RB]
-#define COUNT(i) pool.count[static_cast<int64_t>(i) * NR + RB]
-#define TOTAL(i) pool.total[static_cast<int64_t>(i) * NR + RB]
+  // This lane's tree.  Round 6: ROOT-MAJOR (field[root * cap + node], the wave layout's form) — a root's nodes are
+  // contiguous, so a lane's scan of a node's children and the stores of an expansion walk ONE run of memory (32 children's
+  // counts per 128-byte line) instead of one line per child and field; root-minor (field[node * n + root]; rounds 1-5)
+  // coalesces across lanes only while the lanes stand on the same node index, i.e. near the root.  2^16 roots
+  // (profiles/r06zf_*, r06zi_*): hex(9) x 512 simulations 4.5e8 -> 7.2e8, 11 x 11 2.2e8 -> 4.4e8, 13 x 13 1.2e8 -> 2.9e8,
+  // tic_tac_toe x 1000 8.2e8 -> 9.9e8, connect_four x 256 1.35e9 -> 1.42e9 simulations/s; SHORT searches of narrow games
+  // stay near the root and keep root-minor (connect_four x 32: 2.78e9 against 2.27e9, tic_tac_toe x 100: 2.09e9 against
+  // 1.89e9): the host picks (pool.root_major; OSG_MCTS_ROOT_MAJOR=0/1 forces one).
+  const LaneNodes<Pool> nodes(pool, r);
 
   const typename G::State root_state = G::load(p, base, n, r);
   const int root_player = G::current_player(p, root_state);
-  META(0) = mw_make<kWide>(0xFF, root_player, 0);  // mcts.cc:356-357: root = (kInvalidAction, CurrentPlayer(), 1)
-  FIRST(0) = 0; PARENT(0) = kNoNode; COUNT(0) = 0; TOTAL(0) = 0.0;
+  nodes.meta(0) = mw_make<kWide>(0xFF, root_player, 0);  // mcts.cc:356-357: root = (kInvalidAction, CurrentPlayer(), 1)
+  nodes.first(0) = 0; nodes.parent(0) = kNoNode; nodes.count(0) = 0; nodes.total(0) = 0.0;
   uint32_t used = 1;       // = the reference's nodes_: 1 + the children blocks allocated (mcts.cc:299,354)
   int gc_limit = kMinGcLimit;
   int sims_done = 0;
-#define REMAP(i) pool.remap[static_cast<int64_t>(i) * NR + RB]
 
   for (int sim = 0; sim < cfg.max_simulations; ++sim) {
     Rng trng(cfg.seed ^ kTreeSalt, gr, static_cast<uint64_t>(sim));
@@ -76,9 +71,9 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
     bool term;
     for (;;) {
       term = G::terminal(p, s);
-      const uint32_t cnt = COUNT(node);
+      const uint32_t cnt = nodes.count(node);
       if (term || cnt == 0) break;
-      uint32_t meta = META(node);
+      uint32_t meta = nodes.meta(node);
       const int cur = G::current_player(p, s);
       if (mw_nchild<kWide>(meta) == 0) {  // expand: children = Prior(state), shuffled (mcts.cc:281-299)
         const LegalMask legal = G::legal(p, s);
@@ -107,26 +102,17 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
           sh[j * kBlockM] = ai;
         }
         for (int k = 0; k < c; ++k) {
-          META(first + k) = mw_make<kWide>(static_cast<int>(sh[k * kBlockM]), cur, 0);
-          FIRST(first + k) = 0; PARENT(first + k) = node; COUNT(first + k) = 0; TOTAL(first + k) = 0.0;
+          nodes.meta(first + k) = mw_make<kWide>(static_cast<int>(sh[k * kBlockM]), cur, 0);
+          nodes.first(first + k) = 0; nodes.parent(first + k) = node; nodes.count(first + k) = 0; nodes.total(first + k) = 0.0;
         }
         } else {   // (boards from 16 x 16 on: two-byte entries x 362 children x 64 lanes would cost the kernel a wavefront per CU — 19 x 19: 2.9e8 -> 1.5e8)
-        for (int k = 0; k < c; ++k) {
-          META(first + k) = mw_make<kWide>(select_action(legal, k), cur, 0);
-          FIRST(first + k) = 0; PARENT(first + k) = node; COUNT(first + k) = 0; TOTAL(first + k) = 0.0;
-        }
-        for (int i = c - 1; i >= 1; --i) {  // Fisher-Yates == std::shuffle's role (order only)
-          const int j = static_cast<int>(trng.below(static_cast<uint32_t>(i + 1)));
-          const uint32_t mi = META(first + i), mj = META(first + j);
-          META(first + i) = mj;
-          META(first + j) = mi;
-        }
+        expand_on_pool<kWide>(nodes, legal, c, cur, node, first, trng);
         }
         meta = mw_make<kWide>(static_cast<int>(mw_action<kWide>(meta)), m_player(meta), c) | (meta & kMetaOutcomeBits);
-        META(node) = meta;
-        FIRST(node) = first;
+        nodes.meta(node) = meta;
+        nodes.first(node) = first;
       }
-      const uint32_t first = FIRST(node);
+      const uint32_t first = nodes.first(node);
       const int c = mw_nchild<kWide>(meta);
       uint32_t chosen = first, chosen_meta = 0;
       bool have_meta = false;
@@ -134,7 +120,7 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
         const LegalMask legal = G::legal(p, s);
         const int a = sample_action_chance<G>(p, s, legal, trng);
         for (int k = 0; k < c; ++k)
-          if (static_cast<int>(mw_action<kWide>(META(first + k))) == a) { chosen = first + k; break; }
+          if (static_cast<int>(mw_action<kWide>(nodes.meta(first + k))) == a) { chosen = first + k; break; }
       } else {  // arg-max of UCTValue, first maximum wins (mcts.cc:324-341, 90-101)
         double best = -INFINITY;
         const double logn = log_table[cnt];
@@ -154,7 +140,7 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
         bool scan_only = false;
         if (!puct) {
           const uint32_t at = first + static_cast<uint32_t>(c - 1);
-          scan_only = COUNT(at) == 0 && !m_has_outcome(META(at));
+          scan_only = nodes.count(at) == 0 && !m_has_outcome(nodes.meta(at));
         }
         bool settled = false;   // an unvisited child was found: the arg-max is decided
         for (int k0 = 0; k0 < c && !settled; k0 += kChunk) {
@@ -163,9 +149,9 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
 #pragma unroll
           for (int j = 0; j < kChunk; ++j) {
             const uint32_t at = first + static_cast<uint32_t>(k0 + j < c ? k0 + j : c - 1);
-            cm[j] = META(at);
-            cc[j] = COUNT(at);
-            ct[j] = scan_only ? 0.0 : TOTAL(at);
+            cm[j] = nodes.meta(at);
+            cc[j] = nodes.count(at);
+            ct[j] = scan_only ? 0.0 : nodes.total(at);
           }
 #pragma unroll
           for (int j = 0; j < kChunk; ++j) {
@@ -182,7 +168,7 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
           }
         }
       }
-      G::apply(p, s, static_cast<int>(mw_action<kWide>(have_meta ? chosen_meta : META(chosen))));
+      G::apply(p, s, static_cast<int>(mw_action<kWide>(have_meta ? chosen_meta : nodes.meta(chosen))));
       node = chosen;
     }
     // ---- evaluate (mcts.cc:372-381) ----
@@ -190,9 +176,7 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
     bool solved = false;
     if (term) {
       G::returns(p, s, returns);
-      uint32_t meta = META(node) | (1u << 20) | (1u << 23);
-      if (kBoard) meta = (meta & ~(3u << 21)) | (static_cast<uint32_t>(static_cast<int>(returns[0]) + 1) << 21);
-      META(node) = meta;
+      mark_terminal_leaf<kBoard>(nodes, node, returns);
       solved = cfg.solve != 0;
     } else {  // RandomRolloutEvaluator::Evaluate (mcts.cc:43-72)
       for (int q = 0; q < num_players; ++q) returns[q] = 0.0;
@@ -205,119 +189,14 @@ k_mcts(typename G::Params p, const typename G::word_t* base, int64_t n, int num_
       for (int q = 0; q < num_players; ++q) returns[q] /= cfg.n_rollouts;
     }
     // ---- backup (mcts.cc:383-435) ----
-    for (uint32_t v = node; v != kNoNode; v = PARENT(v)) {
-      uint32_t meta = META(v);
-      int pl = m_player(meta);
-      for (uint32_t up = v; pl == kChancePlayer;) {  // chance node: use the parent decision player
-        up = PARENT(up);
-        if (up == kNoNode) { pl = 0; break; }
-        pl = m_player(META(up));
-      }
-      TOTAL(v) += returns[(pl < 0 || pl >= num_players) ? 0 : pl];  // (a terminal root has no player)
-      COUNT(v) += 1;
-      if (kBoard && solved && mw_nchild<kWide>(meta) > 0) {  // MCTS-Solver, max^n over proven children
-        const uint32_t first = FIRST(v);
-        const int c = mw_nchild<kWide>(meta);
-        const int mover = m_player(META(first));
-        bool all_solved = true, have = false;
-        double best = 0.0;
-        int best_code = 0;
-        for (int k = 0; k < c; ++k) {
-          const uint32_t cm = META(first + k);
-          if (!m_has_outcome(cm)) { all_solved = false; continue; }
-          const double val = outcome_value<true>(cm, 1, 0.0, mover);
-          if (!have || val > best) { have = true; best = val; best_code = m_code(cm); }
-        }
-        if (have && (all_solved || best == max_utility)) {
-          META(v) = (meta & ~(3u << 21)) | (1u << 20) | (static_cast<uint32_t>(best_code) << 21);
-        } else {
-          solved = false;
-        }
-      } else if (!kBoard) {
-        solved = false;
-      }
-    }
+    backup_and_solve<kBoard, kWide>(nodes, node, returns, num_players, max_utility, solved, /*counted=*/false);
     ++sims_done;
-    const uint32_t rm = META(0);
-    if ((m_has_outcome(rm) && !m_terminal(rm)) || mw_nchild<kWide>(rm) == 1) break;  // mcts.cc:437-440
-    if (m_terminal(rm)) break;  // a terminal root: nothing to search
-    // ---- GarbageCollect (mcts.cc:441-482): when nodes_ >= max_nodes_, every node with explore_count <
-    // gc_limit_ loses its children.  Visit counts never grow from parent to child, so a node survives
-    // exactly when its parent's count reaches the limit; the survivors are compacted in index order
-    // (children blocks stay contiguous, parents stay below their children).
-    if (pool.gc_nodes > 1 && used >= static_cast<uint32_t>(pool.gc_nodes)) {
-      const uint32_t limit = static_cast<uint32_t>(gc_limit);
-      uint32_t w = 1;
-      REMAP(0) = 0;
-      for (uint32_t i = 1; i < used; ++i) {
-        const bool alive = COUNT(PARENT(i)) >= limit;
-        REMAP(i) = alive ? w : kNoNode;
-        w += alive ? 1u : 0u;
-      }
-      for (uint32_t i = 0; i < used; ++i) {
-        const uint32_t to = REMAP(i);
-        if (to == kNoNode) continue;
-        uint32_t meta = META(i), first = FIRST(i);
-        const uint32_t cnt = COUNT(i), par = PARENT(i);
-        const double tot = TOTAL(i);
-        if (mw_nchild<kWide>(meta) > 0) {
-          if (cnt < limit) { meta = mw_clear_children<kWide>(meta); first = 0; }   // children.clear(); the outcome stays
-          else first = REMAP(first);
-        }
-        META(to) = meta; FIRST(to) = first; COUNT(to) = cnt; TOTAL(to) = tot;
-        PARENT(to) = i == 0 ? kNoNode : REMAP(par);
-      }
-      used = w;
-      gc_limit = next_gc_limit(gc_limit, used, pool.gc_nodes);
-    }
+    if (search_is_over<kWide>(nodes.meta(0))) break;  // mcts.cc:437-440
+    garbage_collect<kWide>(nodes, pool.gc_nodes, used, gc_limit);
   }
 
-  // ---- results: BestChild by CompareFinal (mcts.cc:114-143) + per-action statistics ----
-  const uint32_t rm = META(0);
-  const int c = mw_nchild<kWide>(rm);
-  const uint32_t first = FIRST(0);
-  if (child_visits) for (int a = 0; a < num_actions; ++a) child_visits[r * num_actions + a] = 0;
-  if (child_reward) for (int a = 0; a < num_actions; ++a) child_reward[r * num_actions + a] = 0.0;
-  if (child_outcome) for (int a = 0; a < num_actions; ++a) child_outcome[r * num_actions + a] = 3;
-  int best = -1;
-  double b_out = 0.0, b_tot = 0.0;
-  uint32_t b_cnt = 0;
-  for (int k = 0; k < c; ++k) {
-    const uint32_t cm = META(first + k);
-    const uint32_t cc = COUNT(first + k);
-    const double ct = TOTAL(first + k);
-    const int a = static_cast<int>(mw_action<kWide>(cm));
-    const bool has = m_has_outcome(cm);
-    const int pl = m_player(cm);
-    const double out = (has && pl >= 0 && cc > 0) ? outcome_value<kBoard>(cm, cc, ct, pl)
-                                                  : ((has && kBoard && pl >= 0) ? outcome_value<true>(cm, 1, 0.0, pl) : 0.0);
-    // strict "a < b" ordering, first maximum kept (std::max_element)
-    const bool better = best < 0 || (b_out != out ? b_out < out : (b_cnt != cc ? b_cnt < cc : b_tot < ct));
-    if (better) { best = a; b_out = out; b_cnt = cc; b_tot = ct; }
-    if (a < num_actions) {
-      if (child_visits) child_visits[r * num_actions + a] = static_cast<int32_t>(cc);
-      if (child_reward) child_reward[r * num_actions + a] = ct;
-      if (child_outcome) {
-        int8_t code = 2;
-        if (has && kBoard && root_player >= 0) code = static_cast<int8_t>(outcome_value<true>(cm, 1, 0.0, root_player));
-        child_outcome[r * num_actions + a] = code;
-      }
-    }
-  }
-  if (best_action) best_action[r] = best;
-  if (root_stats) {
-    root_stats[r * 4 + 0] = static_cast<double>(COUNT(0));
-    root_stats[r * 4 + 1] = static_cast<double>(used);
-    root_stats[r * 4 + 2] = (kBoard && m_has_outcome(rm) && root_player >= 0) ? outcome_value<true>(rm, 1, 0.0, root_player)
-                                                                              : NAN;
-    root_stats[r * 4 + 3] = static_cast<double>(sims_done);
-  }
-#undef REMAP
-#undef META
-#undef FIRST
-#undef PARENT
-#undef COUNT
-#undef TOTAL
+  write_root_results<kBoard, kWide>(nodes, r, num_actions, root_player, used, sims_done,
+                                    MctsOut{best_action, child_visits, child_reward, child_outcome, root_stats}, nullptr);
 }
 
 }  // namespace
@@ -384,33 +263,24 @@ extern "C" int osg_mcts_search(const osg_batch* roots, const osg_mcts_cfg* cfg_i
     cap = never;
   }
   if (cap < 1 + widest) cap = 1 + widest;
-  if (static_cast<size_t>(cap) * n * (gc_nodes > 0 ? 28 : 24) > ctx->d_mcts_pool.size()) {
+  if (pool_layout(cap, n, gc_nodes > 0).bytes > ctx->d_mcts_pool.size()) {
     size_t free_b = 0, total_b = 0;
     OSG_HIP(hipMemGetInfo(&free_b, &total_b));
     free_b += ctx->d_mcts_pool.size();  // the old pool is released before the new one is allocated
     if (gc_nodes > 0) {
-      if (static_cast<size_t>(cap) * n * 28 > free_b * 9 / 10)
+      if (pool_layout(cap, n, true).bytes > free_b * 9 / 10)
         return set_error(OSG_ERR_NOMEM, "osg_mcts_search: max_nodes slots per root do not fit the free HBM");
-    } else if (static_cast<size_t>(cap) * n * 24 > free_b * 6 / 10) {
-      cap = static_cast<int64_t>(free_b * 6 / 10 / (static_cast<size_t>(n) * 28));
+    } else if (pool_layout(cap, n, false).bytes > free_b * 6 / 10) {
+      cap = static_cast<int64_t>(free_b * 6 / 10 / pool_layout(1, n, true).bytes);   // (a pool that collects has a remap plane)
       if (cap < 2 + 2 * widest) cap = 2 + 2 * widest;
       gc_nodes = cap - widest;  // collect before a simulation's expansion could overrun the slots
     }
   }
-  const size_t per_node = gc_nodes > 0 ? 28 : 24;
   cfg.max_nodes = static_cast<int32_t>(cap);
-  const size_t slots = static_cast<size_t>(cap) * n;
-  const size_t pool_bytes = slots * per_node;
-  if (int rc = nomem_error(ctx_grow(ctx, ctx->d_mcts_pool, pool_bytes), "MCTS node pool: ")) return rc;
-  char* pool_mem = reinterpret_cast<char*>(ctx->d_mcts_pool.get());
-  Pool pool;
-  pool.total = reinterpret_cast<double*>(pool_mem);
-  pool.meta = reinterpret_cast<uint32_t*>(pool_mem + slots * 8);
-  pool.first = pool.meta + slots;
-  pool.parent = pool.first + slots;
-  pool.count = pool.parent + slots;
-  pool.remap = gc_nodes > 0 ? pool.count + slots : nullptr;
-  pool.n_roots = n;
+  const PoolLayout lay = pool_layout(cap, n, gc_nodes > 0);
+  if (int rc = nomem_error(ctx_grow(ctx, ctx->d_mcts_pool, lay.bytes), "MCTS node pool: ")) return rc;
+  Pool pool = lay.planes(reinterpret_cast<char*>(ctx->d_mcts_pool.get()));
+  pool.n = n;
   {
     const char* e = std::getenv("OSG_MCTS_ROOT_MAJOR");
     pool.root_major = e ? (e[0] == '1' ? 1 : 0) : ((widest <= 16 && cfg.max_simulations <= 128) ? 0 : 1);

@@ -1,5 +1,5 @@
-// Declarations shared by the two MCTS layouts (osg_mcts.hip: one lane per root,
-// osg_mcts_wave.hip: one wavefront per root).
+// Declarations shared by the MCTS layouts (osg_mcts.hip and osg_mcts_step.hip: one lane per root, their shared steps
+// in osg_mcts_lane.h; osg_mcts_wave.hip: one wavefront per root).
 #ifndef OSG_MCTS_INTERNAL_H_
 #define OSG_MCTS_INTERNAL_H_
 
@@ -13,18 +13,52 @@ constexpr int kBlockM = 64;  // one wave per block: searches differ in length, k
 constexpr uint64_t kTreeSalt = 0x7265655F73616C74ULL;  // stream separation for the tree-policy RNG
 constexpr uint32_t kNoNode = 0xFFFFFFFFu;
 
-struct Pool {
+// The node planes of a lane-per-root or wave-per-root search: struct-of-arrays over (root, node).
+struct NodePool {
   uint32_t* meta;
   uint32_t* first;
   uint32_t* parent;
   uint32_t* count;
   double* total;
   uint32_t* remap;   // old -> new node index during garbage collection; null when GC cannot trigger
-  int64_t n_roots;
+  int64_t n;         // roots
   int cap;           // slots per root
   int gc_nodes;      // the reference's max_nodes_ (mcts.cc:214): garbage-collect when nodes_ >= gc_nodes; 0 = never
-  int root_major = 1;  // lane-per-root kernel: a root's nodes contiguous (1) or field[node * n_roots + root] (0); the wave kernel is root-major
+  int root_major;    // a root's nodes contiguous (1: field[root * cap + node]) or field[node * n + root] (0); the wave kernel is root-major
+  // where node i of root r lives in every plane
+  OSG_HD int64_t stride() const { return root_major ? 1 : n; }
+  OSG_HD int64_t offset(int64_t r) const { return root_major ? r * static_cast<int64_t>(cap) : r; }
+  OSG_HD int64_t at(uint32_t i, int64_t r) const { return static_cast<int64_t>(i) * stride() + offset(r); }
 };
+// osg_mcts_search's pool (k_mcts, k_mcts_wave): the planes alone, carved from the context's grow-only buffer.
+struct Pool : NodePool { static constexpr bool kHasPrior = false; };
+
+template <class T> void set_plane(T*& field, char* mem, size_t offset) { field = reinterpret_cast<T*>(mem + offset); }
+// Where the planes start inside the pool's one allocation (total first: 8-byte aligned), and how long it is.
+struct PoolLayout {
+  size_t total, meta, first, parent, count, remap, bytes;
+  bool has_remap;
+  Pool planes(char* mem) const {   // (the pool's sizes are the caller's to fill in)
+    Pool pool{};
+    set_plane(pool.total, mem, total); set_plane(pool.meta, mem, meta); set_plane(pool.first, mem, first);
+    set_plane(pool.parent, mem, parent); set_plane(pool.count, mem, count);
+    if (has_remap) set_plane(pool.remap, mem, remap);
+    return pool;
+  }
+};
+constexpr PoolLayout pool_layout(int64_t cap, int64_t n, bool with_remap) {
+  const size_t slots = static_cast<size_t>(cap) * static_cast<size_t>(n);
+  PoolLayout l{};
+  auto take = [at = size_t{0}](size_t& field, size_t bytes) mutable { field = at; at += bytes; };
+  take(l.total, slots * sizeof(double)); take(l.meta, slots * sizeof(uint32_t)); take(l.first, slots * sizeof(uint32_t));
+  take(l.parent, slots * sizeof(uint32_t)); take(l.count, slots * sizeof(uint32_t));
+  take(l.remap, with_remap ? slots * sizeof(uint32_t) : 0); take(l.bytes, 0);
+  l.has_remap = with_remap;
+  return l;
+}
+static_assert(pool_layout(10, 3, false).bytes == 10 * 3 * 24 && pool_layout(10, 3, true).bytes == 10 * 3 * 28, "bytes per node");
+static_assert(pool_layout(1, 65536, true).bytes == size_t{65536} * 28 && pool_layout(131073, 65536, false).bytes == size_t{131073} * 65536 * 24, "");
+static_assert(pool_layout(7, 5, true).meta == 7 * 5 * 8 && pool_layout(7, 5, true).remap == 7 * 5 * 24, "total, then four words, then remap");
 constexpr int kMinGcLimit = 5;  // mcts.cc:30 MIN_GC_LIMIT
 
 // gc_limit_ *= (nodes_ > max_nodes_ / 2 ? 1.25 : 0.9), as an int, at least MIN_GC_LIMIT (mcts.cc:456-458)
@@ -76,20 +110,21 @@ OSG_D double outcome_value(uint32_t meta, uint32_t count, double total, int play
 
 
 // Wave-wide maximum of an fp32 value as a DPP reduction (gfx9 row_shr 1, 2, 4, 8, row_bcast 15 / 31; identity -infinity),
-// handed back wave-uniform.  All 64 lanes must be active.  (The fp32 filter of the UCT arg-max: k_mcts_wave's
+// handed back wave-uniform.  All 64 lanes must be active.  A NaN input loses every v_max, so the result is the maximum of
+// the other lanes and a caller that filters by it falls back to its exact path.  (The fp32 filter of the UCT arg-max: k_mcts_wave's
 // select_child, k_mcts_advance's lockstep search.)
 template <int kCtrl, int kRowMask>
-OSG_D float dpp_maxf_step_(float v) {
+OSG_D float dpp_maxf_step(float v) {
   const int o = __builtin_amdgcn_update_dpp(static_cast<int>(0xFF800000u), __float_as_int(v), kCtrl, kRowMask, 0xf, false);
   return fmaxf(__int_as_float(o), v);
 }
-OSG_D float wave_max_f32_dpp(float v) {
-  v = dpp_maxf_step_<0x111, 0xf>(v);
-  v = dpp_maxf_step_<0x112, 0xf>(v);
-  v = dpp_maxf_step_<0x114, 0xf>(v);
-  v = dpp_maxf_step_<0x118, 0xf>(v);
-  v = dpp_maxf_step_<0x142, 0xa>(v);
-  v = dpp_maxf_step_<0x143, 0xc>(v);
+OSG_D float wave_max_f32(float v) {
+  v = dpp_maxf_step<0x111, 0xf>(v);
+  v = dpp_maxf_step<0x112, 0xf>(v);
+  v = dpp_maxf_step<0x114, 0xf>(v);
+  v = dpp_maxf_step<0x118, 0xf>(v);
+  v = dpp_maxf_step<0x142, 0xa>(v);
+  v = dpp_maxf_step<0x143, 0xc>(v);
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 

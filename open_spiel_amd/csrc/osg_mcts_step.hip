@@ -19,7 +19,8 @@
 #include <cstring>
 #include <vector>
 
-#include "osg_mcts_internal.h"
+#include "osg_batch_internal.h"
+#include "osg_mcts_lane.h"
 
 using namespace osg;
 
@@ -52,14 +53,15 @@ namespace {
 enum Phase : uint8_t { kNewSimulation = 0, kWantPrior = 1, kWantValue = 2, kFinished = 3 };
 constexpr int kScanChunk = 8;  // children whose statistics are requested together in the descent
 
-struct StepPool {
-  double* total;    // [cap, n]
+// The trees of osg_mcts_tree_*: the node planes plus a prior per node, each root's search state between launches, and
+// the prior stash.  Root-minor (field[node * n + root]) by default — this kernel runs ONE simulation per launch for every
+// root, the lanes stand on the same node indices near the root most of the time and root-minor coalesces those
+// accesses; root-major (a root's nodes contiguous: what k_mcts gained a factor 2 from in round 6, whole searches in one
+// launch) measured SLOWER here — hex(9) 1.39e8 -> 1.1e8, connect_four with a network 1.97e8 -> 1.70e8 simulations/s
+// (profiles/r06zg_*, r06zh_*).  OSG_STEP_ROOT_MAJOR=1 selects it.
+struct StepPool : NodePool {
+  static constexpr bool kHasPrior = true;
   double* prior;    // [cap, n]
-  uint32_t* meta;
-  uint32_t* first;
-  uint32_t* parent;
-  uint32_t* count;
-  uint32_t* remap;
   // per-root search state
   uint64_t* rng;    // tree-policy stream position of the running simulation
   uint32_t* used;
@@ -67,17 +69,6 @@ struct StepPool {
   int32_t* gc_limit;
   int32_t* sims;
   uint8_t* phase;
-  int64_t n;
-  int cap, gc_nodes;
-  // where node i of root r lives in every plane: root-minor (field[node * n + root]) by default — this kernel runs ONE
-  // simulation per launch for every root, the lanes stand on the same node indices near the root most of the time and
-  // root-minor coalesces those accesses; root-major (a root's nodes contiguous: what k_mcts gained a factor 2 from in
-  // round 6, whole searches in one launch) measured SLOWER here — hex(9) 1.39e8 -> 1.1e8, connect_four with a network
-  // 1.97e8 -> 1.70e8 simulations/s (profiles/r06zg_*, r06zh_*).  OSG_STEP_ROOT_MAJOR=1 selects it.
-  int root_major;
-  OSG_HD int64_t at(uint32_t i, int64_t r) const {
-    return root_major ? r * static_cast<int64_t>(cap) + static_cast<int64_t>(i) : static_cast<int64_t>(i) * n + r;
-  }
   double* stash;      // [n, stash_slots, A] or null (flag 8)
   int stash_slots;
 };
@@ -164,18 +155,36 @@ struct NodeRef {
     return v;
   }
   OSG_D T operator+=(T v) const { return *this = static_cast<T>(*this) + v; }
+  // A store by the CALLING lane (the assignment above is lane 0's alone): where lanes write different nodes.
+  OSG_D void lane_store(T v) const {
+    if (kCoop && in_lds) *l = v;
+    else *g = v;
+  }
 };
-// A store by the CALLING lane (the reference object's assignment is lane 0's alone): where lanes write different nodes.
-template <bool kCoop, class T>
-OSG_D void node_store(T* lds_plane, T* pool_plane, uint32_t i, int64_t NR, int64_t RB, T v) {   // (NR, RB: StepPool::at as stride and offset)
-  if (kCoop && i < static_cast<uint32_t>(kLdsNodes)) lds_plane[i] = v;
-  else pool_plane[static_cast<int64_t>(i) * NR + RB] = v;
-}
-template <bool kCoop, class T>
-OSG_D NodeRef<T, kCoop> node_ref(T* lds_plane, T* pool_plane, uint32_t i, int64_t NR, int64_t RB) {
-  const bool in_lds = kCoop && i < static_cast<uint32_t>(kLdsNodes);
-  return {lds_plane + (in_lds ? i : 0u), pool_plane + static_cast<int64_t>(i) * NR + RB, in_lds};
-}
+// One search's tree as k_mcts_advance sees it: every field of node i through a NodeRef.  (kCoop: node i < kLdsNodes lives
+// in LDS, the others — and every node of the batch form — in the pool.  A reference object that branches on the index: a
+// select between the two ADDRESSES made every access a flat one, slower than the pool itself — 5.1e4 against 7.3e4
+// simulations/s; with the branch the LDS side is a ds_read / ds_write.)
+template <bool kCoop>
+struct StepNodes {
+  static constexpr bool kHasPrior = true;
+  LdsTree lt;
+  const StepPool& pool;
+  LaneSpan span;
+  OSG_D StepNodes(const LdsTree& lt_, const StepPool& pool_, int64_t r) : lt(lt_), pool(pool_), span(pool_, r) {}
+  template <class T>
+  OSG_D NodeRef<T, kCoop> ref(T* lds_plane, T* pool_plane, uint32_t i) const {
+    const bool in_lds = kCoop && i < static_cast<uint32_t>(kLdsNodes);
+    return {lds_plane + (in_lds ? i : 0u), pool_plane + span.at(i), in_lds};
+  }
+  OSG_D NodeRef<uint32_t, kCoop> meta(uint32_t i) const { return ref(lt.meta, pool.meta, i); }
+  OSG_D NodeRef<uint32_t, kCoop> first(uint32_t i) const { return ref(lt.first, pool.first, i); }
+  OSG_D NodeRef<uint32_t, kCoop> parent(uint32_t i) const { return ref(lt.parent, pool.parent, i); }
+  OSG_D NodeRef<uint32_t, kCoop> count(uint32_t i) const { return ref(lt.count, pool.count, i); }
+  OSG_D NodeRef<double, kCoop> total(uint32_t i) const { return ref(lt.total, pool.total, i); }
+  OSG_D double& prior(uint32_t i) const { return pool.prior[span.at(i)]; }   // (the pool only: PUCT reads it, UCT with playouts never)
+  OSG_D uint32_t& remap(uint32_t i) const { return pool.remap[span.at(i)]; }
+};
 template <class G>
 OSG_D void coop_playouts(const typename G::Params& p, const osg_mcts_cfg& cfg, int num_players, uint64_t gr, CoopBox<G>* box,
                          const StepPool& pool, const LdsTree& lt) {
@@ -244,25 +253,14 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
     // (all 64 lanes of the first wavefront go on, in lockstep: one search, its state replicated over the lanes)
   }
   CoopLeave coop_leave{kCoop ? &coop_box.seq : nullptr, kCoop ? &coop_box.exit : nullptr, &coop_box.used, &used};
-  uint32_t coop_seq = 0;
   const int64_t slot = static_cast<int64_t>(blockIdx.x) * kBlockM + threadIdx.x;
   if (!kCoop && lane_stride > 1 && (threadIdx.x % lane_stride) != 0) return;
   const int64_t r = kCoop ? 0 : slot / lane_stride;
   if (r >= n) return;
   const uint64_t gr = static_cast<uint64_t>(cfg.index_offset + r);
-  const int64_t NR = pool.root_major ? 1 : pool.n, RB = pool.root_major ? r * static_cast<int64_t>(pool.cap) : r;   // node i at i * NR + RB (StepPool::at)
   const bool host_priors = (flags & 1) != 0, through_chance = (flags & 2) != 0, own_rollouts = (flags & 4) != 0;
   const bool stashing = pool.stash != nullptr;
-// (kCoop: node i < kLdsNodes lives in LDS, the others — and every node of the batch form — in the pool.  A reference
-// object that branches on the index: a select between the two ADDRESSES made every access a flat one, slower than the
-// pool itself — 5.1e4 against 7.3e4 simulations/s; with the branch the LDS side is a ds_read / ds_write.)
-#define META(i) node_ref<kCoop>(lt.meta, pool.meta, static_cast<uint32_t>(i), NR, RB)
-#define FIRST(i) node_ref<kCoop>(lt.first, pool.first, static_cast<uint32_t>(i), NR, RB)
-#define PARENT(i) node_ref<kCoop>(lt.parent, pool.parent, static_cast<uint32_t>(i), NR, RB)
-#define COUNT(i) node_ref<kCoop>(lt.count, pool.count, static_cast<uint32_t>(i), NR, RB)
-#define TOTAL(i) node_ref<kCoop>(lt.total, pool.total, static_cast<uint32_t>(i), NR, RB)
-#define PRIOR(i) pool.prior[static_cast<int64_t>(i) * NR + RB]   /* (the pool only: PUCT reads it, UCT with playouts never) */
-#define REMAP(i) pool.remap[static_cast<int64_t>(i) * NR + RB]
+  const StepNodes<kCoop> nodes(lt, pool, r);
   uint8_t phase = pool.phase[r];
   if (phase == kFinished) { request[r] = 0; return; }
   // A search parked on a request whose answer the caller did not bring (NULL prior / value pointer) stays
@@ -297,6 +295,12 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
     if (c == 0 || used + static_cast<uint32_t>(c) > static_cast<uint32_t>(pool.cap)) return false;  // nothing to expand / slots exhausted (see osg_mcts.hip)
     const uint32_t first = used;
     used += c;
+    const auto prior_of = [&](int a) -> double {
+      if (cur == kChancePlayer) return G::chance_prob(p, s, a);   // Prior() of a chance node: ChanceOutcomes()
+      if (stashed) return stashed[a];                               // the prior that came with the node's evaluation
+      if (from_host) return prior_in[r * num_actions + a];
+      return 1.0 / c;                                               // RandomRolloutEvaluator::Prior (mcts.cc:74-87)
+    };
     if (kCoop && c <= 64) {   // (wider nodes — hex 9 x 9 and up — take the sequential form below, in lockstep)
       // lane k makes child k; the shuffle (mcts.cc:294, Fisher-Yates on the tree-policy stream, the same draws in the
       // same order) runs on the lanes' registers — lane L tracks which child ends in slot L — and every lane then
@@ -310,44 +314,20 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
       }
       if (L < c) {
         const int a = select_action(legal, mine);
-        double pr;
-        if (cur == kChancePlayer) pr = G::chance_prob(p, s, a);
-        else if (stashed) pr = stashed[a];
-        else if (from_host) pr = prior_in[r * num_actions + a];
-        else pr = 1.0 / c;
         const uint32_t at = first + static_cast<uint32_t>(L);
-        node_store<kCoop>(lt.meta, pool.meta, at, NR, r, mw_make<kWide>(a, cur, 0));
-        node_store<kCoop>(lt.first, pool.first, at, NR, r, 0u);
-        node_store<kCoop>(lt.parent, pool.parent, at, NR, r, node);
-        node_store<kCoop>(lt.count, pool.count, at, NR, r, 0u);
-        node_store<kCoop>(lt.total, pool.total, at, NR, r, 0.0);
-        PRIOR(at) = pr;
+        nodes.meta(at).lane_store(mw_make<kWide>(a, cur, 0));
+        nodes.first(at).lane_store(0u);
+        nodes.parent(at).lane_store(node);
+        nodes.count(at).lane_store(0u);
+        nodes.total(at).lane_store(0.0);
+        nodes.prior(at) = prior_of(a);
       }
-      const uint32_t meta = META(node);
-      META(node) = mw_make<kWide>(static_cast<int>(mw_action<kWide>(meta)), m_player(meta), c) | (meta & kMetaOutcomeBits);
-      FIRST(node) = first;
-      return true;
+    } else {
+      expand_on_pool<kWide>(nodes, legal, c, cur, node, first, trng, prior_of);
     }
-    for (int k = 0; k < c; ++k) {
-      const int a = select_action(legal, k);
-      double pr;
-      if (cur == kChancePlayer) pr = G::chance_prob(p, s, a);       // Prior() of a chance node: ChanceOutcomes()
-      else if (stashed) pr = stashed[a];                            // the prior that came with the node's evaluation
-      else if (from_host) pr = prior_in[r * num_actions + a];
-      else pr = 1.0 / c;                                            // RandomRolloutEvaluator::Prior (mcts.cc:74-87)
-      META(first + k) = mw_make<kWide>(a, cur, 0);
-      FIRST(first + k) = 0; PARENT(first + k) = node; COUNT(first + k) = 0; TOTAL(first + k) = 0.0; PRIOR(first + k) = pr;
-    }
-    for (int i = c - 1; i >= 1; --i) {  // the shuffle (mcts.cc:294), Fisher-Yates on the tree-policy stream
-      const int j = static_cast<int>(trng.below(static_cast<uint32_t>(i + 1)));
-      const uint32_t mi = META(first + i), mj = META(first + j);
-      const double pi = PRIOR(first + i), pj = PRIOR(first + j);
-      META(first + i) = mj; META(first + j) = mi;
-      PRIOR(first + i) = pj; PRIOR(first + j) = pi;
-    }
-    const uint32_t meta = META(node);
-    META(node) = mw_make<kWide>(static_cast<int>(mw_action<kWide>(meta)), m_player(meta), c) | (meta & kMetaOutcomeBits);
-    FIRST(node) = first;
+    const uint32_t meta = nodes.meta(node);
+    nodes.meta(node) = mw_make<kWide>(static_cast<int>(mw_action<kWide>(meta)), m_player(meta), c) | (meta & kMetaOutcomeBits);
+    nodes.first(node) = first;
     return true;
   };
 
@@ -387,7 +367,7 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
         // unexpanded node's first-child field is free: it holds the stash slot + 1
         double* slot = pool.stash + (static_cast<size_t>(r) * pool.stash_slots + sims_done) * num_actions;
         for (int a = 0; a < num_actions; ++a) slot[a] = prior_in[r * num_actions + a];
-        FIRST(node) = static_cast<uint32_t>(sims_done) + 1u;
+        nodes.first(node) = static_cast<uint32_t>(sims_done) + 1u;
       }
     } else {
       // ---- ApplyTreePolicy (mcts.cc:273-351) ----
@@ -397,14 +377,14 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
       uint32_t n_cnt = 0, n_meta = 0, n_first = 0;
       for (;;) {
         term = G::terminal(p, s);
-        const uint32_t cnt = carried ? n_cnt : COUNT(node);
+        const uint32_t cnt = carried ? n_cnt : nodes.count(node);
         const int cur = term ? kTerminalPlayer : G::current_player(p, s);
         if (!resume_expand && !((!term && cnt > 0) || (!term && cur == kChancePlayer && through_chance))) break;
-        uint32_t meta = carried ? n_meta : META(node);
+        uint32_t meta = carried ? n_meta : nodes.meta(node);
         bool expanded_now = false;
         if (mw_nchild<kWide>(meta) == 0) {
           const MaskT<G::kMaskW> legal = G::legal(p, s);
-          const uint32_t slot1 = (stashing && cur != kChancePlayer && !resume_expand) ? (carried ? n_first : FIRST(node)) : 0u;
+          const uint32_t slot1 = (stashing && cur != kChancePlayer && !resume_expand) ? (carried ? n_first : nodes.first(node)) : 0u;
           const double* stashed =
               slot1 ? pool.stash + (static_cast<size_t>(r) * pool.stash_slots + (slot1 - 1u)) * num_actions : nullptr;
           if (cur != kChancePlayer && host_priors && !resume_expand && !stashed) {  // Prior(state) comes from the host
@@ -415,11 +395,11 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
           const bool ok = expand(legal, cur, resume_expand, stashed);
           resume_expand = false;
           if (!ok) break;
-          meta = META(node);
+          meta = nodes.meta(node);
           expanded_now = true;
         }
         resume_expand = false;
-        const uint32_t first = (carried && !expanded_now) ? n_first : FIRST(node);
+        const uint32_t first = (carried && !expanded_now) ? n_first : nodes.first(node);
         const int c = mw_nchild<kWide>(meta);
         uint32_t chosen = first, chosen_meta = 0, chosen_cnt = 0, chosen_first = 0;
         bool have_chosen_meta = false;
@@ -427,7 +407,7 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
           const MaskT<G::kMaskW> legal = G::legal(p, s);
           const int a = sample_action_chance<G>(p, s, legal, trng);
           for (int k = 0; k < c; ++k)
-            if (static_cast<int>(mw_action<kWide>(META(first + k))) == a) { chosen = first + k; break; }
+            if (static_cast<int>(mw_action<kWide>(nodes.meta(first + k))) == a) { chosen = first + k; break; }
         } else {  // arg-max of UCTValue / PUCTValue, first maximum wins (mcts.cc:324-341, 90-112)
           double best = -INFINITY;
           const double logn = log_table[cnt];
@@ -450,7 +430,7 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
             if (!puct && c <= 64) {
               const int k = static_cast<int>(threadIdx.x);
               const uint32_t at = first + static_cast<uint32_t>(k < c ? k : c - 1);
-              const uint32_t cm = META(at), cc = COUNT(at), cf = FIRST(at);
+              const uint32_t cm = nodes.meta(at), cc = nodes.count(at), cf = nodes.first(at);
               const unsigned long long unvisited = __ballot(k < c && cc == 0 && !m_has_outcome(cm));
               if (unvisited != 0ull) {
                 const int src = __builtin_ctzll(unvisited);
@@ -466,14 +446,14 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
                 // maximum.  One such child: the arg-max.  Several without a proven outcome and with IDENTICAL (count,
                 // total): their fp64 values are one number, the lowest index wins as in the scan.  Anything else takes the
                 // fp64 butterfly below — so the ~150 dependent fp64 instructions per level are rarely run.
-                const double ct = TOTAL(at);
+                const double ct = nodes.total(at);
                 const bool has = m_has_outcome(cm);
                 const float lf = static_cast<float>(logn), cf32 = static_cast<float>(cfg.uct_c);
                 const float rc = __builtin_amdgcn_rcpf(static_cast<float>(cc));
                 float a = has ? static_cast<float>(outcome_value<true>(cm, cc, ct, m_player(cm)))
                               : static_cast<float>(ct) * rc + cf32 * __builtin_amdgcn_sqrtf(lf * rc);
                 a = k < c ? a : -INFINITY;
-                const float top = wave_max_f32_dpp(a);
+                const float top = wave_max_f32(a);
                 const float floor_v = top - 0x1p-18f * (1.0f + fabsf(cf32) * __builtin_amdgcn_sqrtf(lf));
                 const unsigned long long near = __ballot(a >= floor_v);
                 const int n_near = __builtin_popcountll(near);
@@ -496,11 +476,11 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
             for (int k0 = 0; !decided && k0 < c; k0 += 64) {
               const int k = k0 + static_cast<int>(threadIdx.x);
               const uint32_t at = first + static_cast<uint32_t>(k < c ? k : c - 1);
-              const uint32_t cm = META(at), cc = COUNT(at), cf = FIRST(at);
-              const double ct = TOTAL(at);
+              const uint32_t cm = nodes.meta(at), cc = nodes.count(at), cf = nodes.first(at);
+              const double ct = nodes.total(at);
               double v;
               if (m_has_outcome(cm)) v = outcome_value<kBoard>(cm, cc, ct, m_player(cm));
-              else if (puct) v = (cc != 0 ? ct / cc : 0.0) + cfg.uct_c * PRIOR(at) * sqrt_n / (cc + 1);
+              else if (puct) v = (cc != 0 ? ct / cc : 0.0) + cfg.uct_c * nodes.prior(at) * sqrt_n / (cc + 1);
               else if (cc == 0) v = INFINITY;
               else v = ct / cc + cfg.uct_c * sqrt(logn / cc);
               if (k < c && v > bv) { bv = v; bk = static_cast<uint32_t>(k); bm = cm; bc = cc; bf = cf; }
@@ -522,7 +502,7 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
           bool scan_only = false, settled = false;
           if (!kCoop && !puct) {
             const uint32_t at = first + static_cast<uint32_t>(c - 1);
-            scan_only = COUNT(at) == 0 && !m_has_outcome(META(at));
+            scan_only = nodes.count(at) == 0 && !m_has_outcome(nodes.meta(at));
           }
           for (int k0 = 0; !kCoop && k0 < c && !settled; k0 += kScanChunk) {
             uint32_t cm[kScanChunk], cc[kScanChunk], cf[kScanChunk];
@@ -530,11 +510,11 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
 #pragma unroll
             for (int j = 0; j < kScanChunk; ++j) {
               const uint32_t at = first + static_cast<uint32_t>(k0 + j < c ? k0 + j : c - 1);
-              cm[j] = META(at);
-              cc[j] = COUNT(at);
-              cf[j] = FIRST(at);
-              ct[j] = scan_only ? 0.0 : TOTAL(at);
-              cp[j] = scan_only ? 0.0 : PRIOR(at);
+              cm[j] = nodes.meta(at);
+              cc[j] = nodes.count(at);
+              cf[j] = nodes.first(at);
+              ct[j] = scan_only ? 0.0 : nodes.total(at);
+              cp[j] = scan_only ? 0.0 : nodes.prior(at);
             }
 #pragma unroll
             for (int j = 0; j < kScanChunk; ++j) {
@@ -555,7 +535,7 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
             }
           }
         }
-        G::apply(p, s, static_cast<int>(mw_action<kWide>(have_chosen_meta ? chosen_meta : META(chosen))));
+        G::apply(p, s, static_cast<int>(mw_action<kWide>(have_chosen_meta ? chosen_meta : nodes.meta(chosen))));
         node = chosen;
         if (kCoop) {
           ++path_depth;
@@ -569,9 +549,7 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
       // ---- evaluate (mcts.cc:372-381) ----
       if (term) {
         G::returns(p, s, returns);
-        uint32_t meta = META(node) | (1u << 20) | (1u << 23);
-        if (kBoard) meta = (meta & ~(3u << 21)) | (static_cast<uint32_t>(static_cast<int>(returns[0]) + 1) << 21);
-        META(node) = meta;
+        mark_terminal_leaf<kBoard>(nodes, node, returns);
         solved = cfg.solve != 0;
       } else if (own_rollouts) {
         // RandomRolloutEvaluator::Evaluate (mcts.cc:43-72) right here, on the streams k_mcts_tree_rollout draws
@@ -624,91 +602,26 @@ k_mcts_advance(typename G::Params p, const typename G::word_t* root_words, typen
     if (kCoop && kBoard && path_ok) {   // two players, no chance nodes: a node's player is in its own header
       if (static_cast<int>(threadIdx.x) <= path_depth) {
         const uint32_t v = path_node;
-        const int pl = m_player(static_cast<uint32_t>(META(v)));
-        const double t = static_cast<double>(TOTAL(v)) + returns[(pl < 0 || pl >= num_players) ? 0 : pl];  // (a terminal root has no player)
-        const uint32_t cn = static_cast<uint32_t>(COUNT(v)) + 1u;
-        node_store<kCoop>(lt.total, pool.total, v, NR, RB, t);
-        node_store<kCoop>(lt.count, pool.count, v, NR, RB, cn);
+        const int pl = m_player(static_cast<uint32_t>(nodes.meta(v)));
+        const double t = static_cast<double>(nodes.total(v)) + returns[(pl < 0 || pl >= num_players) ? 0 : pl];  // (a terminal root has no player)
+        const uint32_t cn = static_cast<uint32_t>(nodes.count(v)) + 1u;
+        nodes.total(v).lane_store(t);
+        nodes.count(v).lane_store(cn);
       }
       asm volatile("" ::: "memory");
       counted = true;
     }
-    for (uint32_t v = node; v != kNoNode && !(counted && !solved); v = PARENT(v)) {
-      uint32_t meta = META(v);
-      int pl = m_player(meta);
-      for (uint32_t up = v; pl == kChancePlayer;) {
-        up = PARENT(up);
-        if (up == kNoNode) { pl = 0; break; }
-        pl = m_player(META(up));
-      }
-      if (!counted) {
-        TOTAL(v) += returns[(pl < 0 || pl >= num_players) ? 0 : pl];  // (a terminal root has no player)
-        COUNT(v) += 1;
-      }
-      if (kBoard && solved && mw_nchild<kWide>(meta) > 0) {
-        const uint32_t first = FIRST(v);
-        const int c = mw_nchild<kWide>(meta);
-        const int mover = m_player(META(first));
-        bool all_solved = true, have = false;
-        double best = 0.0;
-        int best_code = 0;
-        for (int k = 0; k < c; ++k) {
-          const uint32_t cm = META(first + k);
-          if (!m_has_outcome(cm)) { all_solved = false; continue; }
-          const double val = outcome_value<true>(cm, 1, 0.0, mover);
-          if (!have || val > best) { have = true; best = val; best_code = m_code(cm); }
-        }
-        if (have && (all_solved || best == max_utility)) {
-          META(v) = (meta & ~(3u << 21)) | (1u << 20) | (static_cast<uint32_t>(best_code) << 21);
-        } else {
-          solved = false;
-        }
-      } else if (!kBoard) {
-        solved = false;
-      }
-    }
+    backup_and_solve<kBoard, kWide>(nodes, node, returns, num_players, max_utility, solved, counted);
     solved = false;
     ++sims_done;
     phase = kNewSimulation;
     OSG_PROF(3);
-    const uint32_t rm = META(0);
-    if ((m_has_outcome(rm) && !m_terminal(rm)) || mw_nchild<kWide>(rm) == 1 || m_terminal(rm)) {  // mcts.cc:437-440
+    if (search_is_over<kWide>(nodes.meta(0))) {  // mcts.cc:437-440
       park(kFinished, 0);
       return;
     }
-    if (pool.gc_nodes > 1 && used >= static_cast<uint32_t>(pool.gc_nodes)) {  // GarbageCollect (see osg_mcts.hip)
-      const uint32_t limit = static_cast<uint32_t>(gc_limit);
-      uint32_t w = 1;
-      REMAP(0) = 0;
-      for (uint32_t i = 1; i < used; ++i) {
-        const bool alive = COUNT(PARENT(i)) >= limit;
-        REMAP(i) = alive ? w : kNoNode;
-        w += alive ? 1u : 0u;
-      }
-      for (uint32_t i = 0; i < used; ++i) {
-        const uint32_t to = REMAP(i);
-        if (to == kNoNode) continue;
-        uint32_t meta = META(i), first = FIRST(i);
-        const uint32_t cnt = COUNT(i), par = PARENT(i);
-        const double tot = TOTAL(i), pri = PRIOR(i);
-        if (mw_nchild<kWide>(meta) > 0) {
-          if (cnt < limit) { meta = mw_clear_children<kWide>(meta); first = 0; }
-          else first = REMAP(first);
-        }
-        META(to) = meta; FIRST(to) = first; COUNT(to) = cnt; TOTAL(to) = tot; PRIOR(to) = pri;
-        PARENT(to) = i == 0 ? kNoNode : REMAP(par);
-      }
-      used = w;
-      gc_limit = next_gc_limit(gc_limit, used, pool.gc_nodes);
-    }
+    garbage_collect<kWide>(nodes, pool.gc_nodes, used, gc_limit);
   }
-#undef META
-#undef FIRST
-#undef PARENT
-#undef COUNT
-#undef TOTAL
-#undef PRIOR
-#undef REMAP
 }
 
 // RandomRolloutEvaluator::Evaluate (mcts.cc:43-72) for the parked leaves, on the fused kernel's streams:
@@ -742,59 +655,12 @@ k_mcts_tree_results(StepPool pool, int64_t n, int num_actions, int32_t* best_act
                     double* child_reward, int8_t* child_outcome, double* child_prior, double* root_stats) {
   const int64_t r = static_cast<int64_t>(blockIdx.x) * kBlockM + threadIdx.x;
   if (r >= n) return;
-  const int64_t NR = pool.root_major ? 1 : pool.n, RB = pool.root_major ? r * static_cast<int64_t>(pool.cap) : r;   // node i at i * NR + RB (StepPool::at)
-#define META(i) pool.meta[static_cast<int64_t>(i) * NR + RB]
-#define FIRST(i) pool.first[static_cast<int64_t>(i) * NR + RB]
-#define COUNT(i) pool.count[static_cast<int64_t>(i) * NR + RB]
-#define TOTAL(i) pool.total[static_cast<int64_t>(i) * NR + RB]
-#define PRIOR(i) pool.prior[static_cast<int64_t>(i) * NR + RB]
-  const uint32_t rm = META(0);
+  const LaneNodes<StepPool> nodes(pool, r);
+  const uint32_t rm = nodes.meta(0);
   const int root_player = m_terminal(rm) ? -1 : m_player(rm);  // a terminal root has no player to move
-  const int c = mw_nchild<true>(rm);
-  const uint32_t first = FIRST(0);
-  for (int a = 0; a < num_actions; ++a) {
-    if (child_visits) child_visits[r * num_actions + a] = 0;
-    if (child_reward) child_reward[r * num_actions + a] = 0.0;
-    if (child_outcome) child_outcome[r * num_actions + a] = 3;
-    if (child_prior) child_prior[r * num_actions + a] = 0.0;
-  }
-  int best = -1;
-  double b_out = 0.0, b_tot = 0.0;
-  uint32_t b_cnt = 0;
-  for (int k = 0; k < c; ++k) {
-    const uint32_t cm = META(first + k);
-    const uint32_t cc = COUNT(first + k);
-    const double ct = TOTAL(first + k);
-    const int a = static_cast<int>(mw_action<true>(cm));
-    const bool has = m_has_outcome(cm);
-    const int pl = m_player(cm);
-    const double out = (has && pl >= 0 && cc > 0) ? outcome_value<kBoard>(cm, cc, ct, pl)
-                                                  : ((has && kBoard && pl >= 0) ? outcome_value<true>(cm, 1, 0.0, pl) : 0.0);
-    const bool better = best < 0 || (b_out != out ? b_out < out : (b_cnt != cc ? b_cnt < cc : b_tot < ct));
-    if (better) { best = a; b_out = out; b_cnt = cc; b_tot = ct; }
-    if (a < num_actions) {
-      if (child_visits) child_visits[r * num_actions + a] = static_cast<int32_t>(cc);
-      if (child_reward) child_reward[r * num_actions + a] = ct;
-      if (child_prior) child_prior[r * num_actions + a] = PRIOR(first + k);
-      if (child_outcome) {
-        int8_t code = 2;
-        if (has && kBoard && root_player >= 0) code = static_cast<int8_t>(outcome_value<true>(cm, 1, 0.0, root_player));
-        child_outcome[r * num_actions + a] = code;
-      }
-    }
-  }
-  if (best_action) best_action[r] = best;
-  if (root_stats) {
-    root_stats[r * 4 + 0] = static_cast<double>(COUNT(0));
-    root_stats[r * 4 + 1] = static_cast<double>(pool.used[r]);
-    root_stats[r * 4 + 2] = (kBoard && m_has_outcome(rm) && root_player >= 0) ? outcome_value<true>(rm, 1, 0.0, root_player) : NAN;
-    root_stats[r * 4 + 3] = static_cast<double>(pool.sims[r]);
-  }
-#undef META
-#undef FIRST
-#undef COUNT
-#undef TOTAL
-#undef PRIOR
+  // (the nine-bit fields are read whatever the game: they are zero where it has at most 255 actions)
+  write_root_results<kBoard, /*kWide=*/true>(nodes, r, num_actions, root_player, pool.used[r], pool.sims[r],
+                                             MctsOut{best_action, child_visits, child_reward, child_outcome, root_stats}, child_prior);
 }
 
 __global__ void __launch_bounds__(256) k_mcts_tree_init(StepPool pool, const int8_t* root_player, int64_t n) {
@@ -818,23 +684,37 @@ __global__ void k_mcts_tree_extract(StepPool pool, int64_t r, uint32_t* meta, ui
   }
 }
 
+// Where the planes and the per-root state start inside a tree's one allocation (8-byte fields first, the bytes of
+// `phase` last, 256 bytes to spare), and how long it is.
+struct StepLayout {
+  size_t total, prior, rng, meta, first, parent, count, remap, used, node, gc_limit, sims, phase, bytes;
+};
+constexpr StepLayout step_layout(int64_t cap, int64_t n) {
+  const size_t roots = static_cast<size_t>(n), slots = static_cast<size_t>(cap) * roots;
+  StepLayout l{};
+  auto take = [at = size_t{0}](size_t& field, size_t bytes) mutable { field = at; at += bytes; };
+  take(l.total, slots * sizeof(double)); take(l.prior, slots * sizeof(double)); take(l.rng, roots * sizeof(uint64_t));
+  take(l.meta, slots * sizeof(uint32_t)); take(l.first, slots * sizeof(uint32_t)); take(l.parent, slots * sizeof(uint32_t));
+  take(l.count, slots * sizeof(uint32_t)); take(l.remap, slots * sizeof(uint32_t));
+  take(l.used, roots * sizeof(uint32_t)); take(l.node, roots * sizeof(uint32_t)); take(l.gc_limit, roots * sizeof(int32_t));
+  take(l.sims, roots * sizeof(int32_t)); take(l.phase, roots * sizeof(uint8_t)); take(l.bytes, 0);
+  l.bytes += 256;
+  return l;
+}
+constexpr size_t step_bytes_per_node(int64_t n) { return step_layout(1, n).bytes - step_layout(0, n).bytes; }   // of every root
+static_assert(step_layout(10, 3).bytes == 10 * 3 * 36 + 3 * 25 + 256 && step_layout(1, 1).bytes == 36 + 25 + 256, "");
+static_assert(step_layout(4097, 65536).bytes == size_t{4097} * 65536 * 36 + size_t{65536} * 25 + 256, "");
+static_assert(step_layout(7, 5).meta == 7 * 5 * 16 + 5 * 8 && step_layout(7, 5).phase == 7 * 5 * 36 + 5 * 24, "");
+
 StepPool make_pool(const osg_mcts_tree* t) {
-  StepPool pool;
-  const size_t slots = static_cast<size_t>(t->cap) * t->n;
+  StepPool pool{};
+  const StepLayout l = step_layout(t->cap, t->n);
   char* m = t->d_mem;
-  pool.total = reinterpret_cast<double*>(m); m += slots * 8;
-  pool.prior = reinterpret_cast<double*>(m); m += slots * 8;
-  pool.rng = reinterpret_cast<uint64_t*>(m); m += static_cast<size_t>(t->n) * 8;
-  pool.meta = reinterpret_cast<uint32_t*>(m); m += slots * 4;
-  pool.first = reinterpret_cast<uint32_t*>(m); m += slots * 4;
-  pool.parent = reinterpret_cast<uint32_t*>(m); m += slots * 4;
-  pool.count = reinterpret_cast<uint32_t*>(m); m += slots * 4;
-  pool.remap = reinterpret_cast<uint32_t*>(m); m += slots * 4;
-  pool.used = reinterpret_cast<uint32_t*>(m); m += static_cast<size_t>(t->n) * 4;
-  pool.node = reinterpret_cast<uint32_t*>(m); m += static_cast<size_t>(t->n) * 4;
-  pool.gc_limit = reinterpret_cast<int32_t*>(m); m += static_cast<size_t>(t->n) * 4;
-  pool.sims = reinterpret_cast<int32_t*>(m); m += static_cast<size_t>(t->n) * 4;
-  pool.phase = reinterpret_cast<uint8_t*>(m);
+  set_plane(pool.total, m, l.total); set_plane(pool.prior, m, l.prior); set_plane(pool.rng, m, l.rng);
+  set_plane(pool.meta, m, l.meta); set_plane(pool.first, m, l.first); set_plane(pool.parent, m, l.parent);
+  set_plane(pool.count, m, l.count); set_plane(pool.remap, m, l.remap); set_plane(pool.used, m, l.used);
+  set_plane(pool.node, m, l.node); set_plane(pool.gc_limit, m, l.gc_limit); set_plane(pool.sims, m, l.sims);
+  set_plane(pool.phase, m, l.phase);
   pool.n = t->n;
   pool.cap = t->cap;
   {
@@ -845,10 +725,6 @@ StepPool make_pool(const osg_mcts_tree* t) {
   pool.stash = t->d_stash;
   pool.stash_slots = t->stash_slots;
   return pool;
-}
-
-size_t pool_bytes(int64_t cap, int64_t n) {
-  return static_cast<size_t>(cap) * n * 36 + static_cast<size_t>(n) * (8 + 4 * 4 + 1) + 256;
 }
 
 // Active lanes per wavefront for the lane-per-root kernels.  1 = every lane carries a search (the default).  Spreading
@@ -865,8 +741,8 @@ int lane_stride_for(osg_ctx*, int64_t) {
   return 1;
 }
 
-bool same_game(const osg_batch* a, const osg_batch* b) {
-  return a && b && a->n == b->n && std::strcmp(a->spec.desc.canonical, b->spec.desc.canonical) == 0;
+bool same_game_and_size(const osg_batch* a, const osg_batch* b) {   // (null-safe)
+  return a && b && a->n == b->n && same_game(a, b);
 }
 
 }  // namespace
@@ -930,15 +806,16 @@ int osg_mcts_tree_create(const osg_batch* roots, const osg_mcts_cfg* cfg_in, int
                                            "does not fit the free HBM; search fewer roots per tree or fewer simulations"));
     budget -= stash_bytes;
   }
-  if (pool_bytes(cap, t->n) > budget) {
+  if (step_layout(cap, t->n).bytes > budget) {
     if (gc_nodes > 0) return fail(set_error(OSG_ERR_NOMEM, "osg_mcts_tree_create: max_nodes slots per root do not fit the free HBM"));
-    cap = static_cast<int64_t>((budget - static_cast<size_t>(t->n) * 32) / (static_cast<size_t>(t->n) * 36));
+    // (32 bytes set aside per root: its 25 bytes of search state rounded up, as this limit has always been computed)
+    cap = static_cast<int64_t>((budget - static_cast<size_t>(t->n) * 32) / step_bytes_per_node(t->n));
     if (cap < 2 + 2 * per_sim) return fail(set_error(OSG_ERR_NOMEM, "osg_mcts_tree_create: too many roots for the free HBM"));
     gc_nodes = cap - per_sim;
   }
   t->cap = static_cast<int>(cap);
   t->gc_nodes = static_cast<int>(gc_nodes);
-  t->bytes = pool_bytes(cap, t->n);
+  t->bytes = step_layout(cap, t->n).bytes;
   e = t->d_mem.alloc(t->bytes);
   if (e != hipSuccess) { return fail(set_error(OSG_ERR_NOMEM, std::string("MCTS trees: ") + hipGetErrorString(e))); }
   if (flags & 8) {
@@ -984,7 +861,7 @@ int osg_mcts_tree_destroy(osg_mcts_tree* t) {
 int osg_mcts_tree_advance(osg_mcts_tree* t, osg_batch* leaf, const double* d_prior, const double* d_value,
                           uint8_t* d_request, int max_new_simulations, int64_t* h_counts) {
   if (!t || !leaf || !d_request) return set_error(OSG_ERR_INVALID, "osg_mcts_tree_advance: null argument");
-  if (!same_game(t->roots, leaf)) return set_error(OSG_ERR_INVALID, "osg_mcts_tree_advance: the leaf batch must have the roots' game and size");
+  if (!same_game_and_size(t->roots, leaf)) return set_error(OSG_ERR_INVALID, "osg_mcts_tree_advance: the leaf batch must have the roots' game and size");
   if (max_new_simulations < 0) return set_error(OSG_ERR_INVALID, "osg_mcts_tree_advance: max_new_simulations < 0");
   const int lane_stride = lane_stride_for(t->ctx, t->n);
   const unsigned grid = static_cast<unsigned>((t->n * lane_stride + kBlockM - 1) / kBlockM);
@@ -1076,7 +953,7 @@ int osg_mcts_tree_rollout_values(osg_mcts_tree* t, const osg_batch* leaf, double
     if (rc) return rc;
     d_value = t->d_own_value;
   }
-  if (!same_game(t->roots, leaf)) return set_error(OSG_ERR_INVALID, "osg_mcts_tree_rollout_values: the leaf batch must have the roots' game and size");
+  if (!same_game_and_size(t->roots, leaf)) return set_error(OSG_ERR_INVALID, "osg_mcts_tree_rollout_values: the leaf batch must have the roots' game and size");
   const int lane_stride = lane_stride_for(t->ctx, t->n);
   const unsigned grid = static_cast<unsigned>((t->n * lane_stride + kBlockM - 1) / kBlockM);
   const StepPool pool = make_pool(t);

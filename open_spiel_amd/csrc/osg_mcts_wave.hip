@@ -182,20 +182,6 @@ OSG_D uint32_t dpp_min_step(uint32_t v) {
   const uint32_t o = dpp_move<kCtrl, kRowMask>(0xFFFFFFFFu, v);
   return o < v ? o : v;
 }
-template <int kCtrl, int kRowMask>
-OSG_D float dpp_maxf_step(float v) {
-  const float o = __uint_as_float(dpp_move<kCtrl, kRowMask>(0xFF800000u, __float_as_uint(v)));   // identity: -infinity
-  return fmaxf(o, v);
-}
-OSG_D float wave_max_f32(float v) {  // never NaN-sensitive here: a NaN input loses every v_max and the caller falls back
-  v = dpp_maxf_step<0x111, 0xf>(v);
-  v = dpp_maxf_step<0x112, 0xf>(v);
-  v = dpp_maxf_step<0x114, 0xf>(v);
-  v = dpp_maxf_step<0x118, 0xf>(v);
-  v = dpp_maxf_step<0x142, 0xa>(v);
-  v = dpp_maxf_step<0x143, 0xc>(v);
-  return __uint_as_float(read_lane(__float_as_uint(v), 63));
-}
 OSG_D uint32_t wave_min_u32(uint32_t v) {
   v = dpp_min_step<0x111, 0xf>(v);
   v = dpp_min_step<0x112, 0xf>(v);

@@ -377,7 +377,7 @@ class State:
                     counter_root=-1, counter_seed=0, counter_layout=1, puct=False):
         best = C.c_int64(0)
         root_outcome = C.c_double(0)
-        visits = C.c_int(0)
+        visits, nodes = C.c_int(0), C.c_int(0)
         cap = 512
         ch = np.zeros((cap, 4), np.float64)
         n = _check(lib().osgo_mcts_search(self._h, C.c_double(uct_c), max_simulations, n_rollouts,
@@ -385,9 +385,9 @@ class State:
                                           C.byref(best), C.byref(root_outcome),
                                           _ptr(ch, C.c_double), cap, C.byref(visits),
                                           C.c_int64(counter_root), C.c_uint64(counter_seed),
-                                          int(counter_layout), int(puct)))
+                                          int(counter_layout), int(puct), C.byref(nodes)))
         return dict(best_action=best.value, root_outcome=root_outcome.value,
-                    root_visits=visits.value, children=ch[:n])
+                    root_visits=visits.value, children=ch[:n], nodes=nodes.value)
 
 
 def _mcts_search_stub(self, uct_c, max_simulations, counter_root, counter_seed, max_nodes=0, solve=False, puct=False,

@@ -598,11 +598,12 @@ int osgo_replay_rollouts(void* g, const int16_t* history, int hist_len,
 // *best_action, root outcome (for root player; NaN if unsolved) in *root_outcome.
 // counter_root >= 0: replay mode, all draws from the device's counter streams for
 // that root index with seed `counter_seed` (MCTSBot::UseCounterStreams).
+// *nodes (may be null): nodes_ at the end of the search (a hook of the restatement; -1 over the reference).
 int osgo_mcts_search(void* s, double uct_c, int max_simulations, int n_rollouts,
                      int64_t max_memory_mb, int solve, int seed,
                      int64_t* best_action, double* root_outcome,
                      double* out_children, int cap, int* root_visits,
-                     int64_t counter_root, uint64_t counter_seed, int counter_layout, int puct) {
+                     int64_t counter_root, uint64_t counter_seed, int counter_layout, int puct, int* nodes) {
   return Guard([&] {
     const State& st = *static_cast<StateH*>(s)->state;
     auto ev = std::make_shared<RandomRolloutEvaluator>(n_rollouts, seed);
@@ -618,6 +619,11 @@ int osgo_mcts_search(void* s, double uct_c, int max_simulations, int n_rollouts,
                             counter_layout);
 #endif
     std::unique_ptr<SearchNode> root = bot.MCTSearch(st);
+#ifdef OSGO_GENUINE_REFERENCE
+    if (nodes) *nodes = -1;
+#else
+    if (nodes) *nodes = bot.LastNodeCount();
+#endif
     const double nan = std::numeric_limits<double>::quiet_NaN();
     *best_action = root->children.empty() ? -1 : root->BestChild().action;
     Player rp = st.CurrentPlayer();
