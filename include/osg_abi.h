@@ -88,7 +88,8 @@ int osg_ctx_create(int device, void* stream, int own_stream, osg_ctx** out);
 int osg_ctx_destroy(osg_ctx* ctx);
 int osg_ctx_synchronize(osg_ctx* ctx);
 void* osg_ctx_stream(osg_ctx* ctx);
-/* Give back what the context caches between calls: the MCTS node pool (grow-only otherwise: a search without a
+/* Give back what the context caches between calls: the IS-MCTS workspace (and with it the trees of the last
+ * osg_ismcts_search), the MCTS node pool (grow-only otherwise: a search without a
  * node budget sizes it at 1 + max_simulations x widest-node slots per root, up to 60 % of the free HBM) and the
  * staging buffer.  Waits for the stream first.  The next search allocates again. */
 int osg_ctx_trim(osg_ctx* ctx);
@@ -346,6 +347,62 @@ typedef struct {
 } osg_ab_cfg;
 int osg_alpha_beta_search(const osg_batch* roots, const osg_ab_cfg* cfg, double* value, int32_t* best_action,
                           int64_t* nodes, uint8_t* status, int on_host);
+
+/* ---- information-set MCTS -------------------------------------------------------------------------------------
+ * ISMCTSBot (python/algorithms/ismcts.py; algorithms/is_mcts.{h,cc}) with RandomRolloutEvaluator(n_rollouts) for every
+ * root of a kuhn_poker or leduc_poker batch (every parameter set, 2 or 3 players): one tree per root whose nodes are keyed
+ * by (player to act, InformationStateString), the root state resampled from the searcher's information state before
+ * every simulation (ResampleFromInfostate's rejection loops), one child expanded per visit, and the UCT / PUCT choice
+ * among the children within 1e-5 of the best.  The Python file is followed where the two differ: it draws
+ * randint(len(candidates)) for a single candidate too.  All draws of root i come from ONE stream
+ * Rng(seed, index_offset + i, 0), consumed in the reference's order (csrc/osg_ismcts.h lists it), so a scripted
+ * random_state makes the reference's own bot build the same tree, node for node.
+ *   max_world_samples  <= 0: unlimited (a fresh resample per simulation); k > 0: the first k simulations resample and keep
+ *                      their sample, later ones take samples[below(k)] (ismcts.py:206-217)
+ *   max_nodes          the table of each root; <= 0: as many as the search can create (one per simulation at most).  A
+ *                      root that needs more stops with status 2; nothing is ever written past a table
+ * OSG_ERR_UNSUPPORTED: another game, more than 3 players.  OSG_ERR_INVALID: max_simulations or n_rollouts < 1, an unknown
+ * final_policy_type or child_selection_policy, max_nodes above 2^24, and a root that is a chance node or terminal (the
+ * message names the first such row).
+ * Outputs (host or device by on_host; any may be NULL), A = num_distinct_actions:
+ *   policy [n, A] f64            get_final_policy (ismcts.py:161-204) by action; 0 for an action that is not legal
+ *   sampled_action [n] i32       step_with_policy's draw: one more unit(), a CDF scan over the policy list in ITS order
+ *                                (children in insertion order, then the legal actions never expanded)
+ *   child_visits [n, A] i32, child_return_sum [n, A] f64     of the root's children
+ *   expansion_rank [n, A] i32    the insertion rank of the action's child at the root; -1 = never expanded
+ *   nodes [n] i32                nodes in the root's table
+ *   status [n] u8                0 done; 1 the root was never visited (max_simulations = 1 only evaluates it: the
+ *                                reference's `assert node.total_visits > 0`); 2 the table was full; 3 the record is not a
+ *                                state of the game.  For a status other than 0 the policy is NaN and sampled_action -1.
+ * A root with a single legal action gets policy {a: 1}, no simulation, no draw and 0 nodes (ismcts.py:117-119).
+ *
+ * The trees of a context's last search stay in its workspace until the next search or osg_ctx_trim; `roots` names
+ * them (the same batch, or one of the same game and size on that context):
+ *   osg_ismcts_tree_sizes     host arrays [n]: nodes per root and draws consumed per root (either may be NULL)
+ *   osg_ismcts_tree_download  root `root`'s nodes in creation order (node 0 is the root's) into host arrays of `cap`
+ *                             rows (>= its node count): player, total_visits, and [cap, 3] by action visits, return_sum
+ *                             and expansion rank; `states` (may be NULL; a batch of the same game with >= that many
+ *                             rows) receives in row i the state node i was created from, so that
+ *                             osg_information_state_string(states, i, player[i]) is the node's key.
+ *                             OSG_ERR_UNSUPPORTED when the search had more roots than lanes (a lane's table then holds
+ *                             the last of its roots: 512 lanes per compute unit, fewer for large tables); search fewer roots per call. */
+typedef struct osg_ismcts_cfg {
+  double uct_c;
+  int32_t max_simulations;
+  int32_t n_rollouts;
+  int32_t max_world_samples;       /* <= 0: unlimited */
+  int32_t final_policy_type;       /* 1 NORMALIZED_VISITED_COUNT, 2 MAX_VISIT_COUNT, 3 MAX_VALUE */
+  int32_t child_selection_policy;  /* 1 UCT, 2 PUCT */
+  int32_t max_nodes;
+  uint64_t seed;
+  int64_t index_offset;
+} osg_ismcts_cfg;
+int osg_ismcts_search(const osg_batch* roots, const osg_ismcts_cfg* cfg, double* policy, int32_t* sampled_action,
+                      int32_t* child_visits, double* child_return_sum, int32_t* expansion_rank, int32_t* nodes,
+                      uint8_t* status, int on_host);
+int osg_ismcts_tree_sizes(const osg_batch* roots, int32_t* h_nodes, int64_t* h_draws);
+int osg_ismcts_tree_download(const osg_batch* roots, int64_t root, int64_t cap, osg_batch* states, int32_t* h_player,
+                             int32_t* h_total_visits, int32_t* h_visits, double* h_return_sum, int32_t* h_rank);
 
 /* ---- every reachable position and its game-theoretic value ------------------------------------------------
  * algorithms::GetAllStates (open_spiel/algorithms/get_all_states.h:38-43, get_all_states.cc:28-91;

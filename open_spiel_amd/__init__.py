@@ -3,7 +3,7 @@
 A from-scratch HIP (gfx950) implementation of OpenSpiel's data-parallel hot
 path: batched LegalActions / ApplyAction / IsTerminal / Returns /
 ObservationTensor for tic_tac_toe, connect_four, hex, kuhn_poker and
-leduc_poker, random-rollout evaluation, MCTS and alpha-beta search over batches of roots, and
+leduc_poker, random-rollout evaluation, MCTS, information-set MCTS and alpha-beta search over batches of roots, and
 tabular CFR / Discounted CFR / external-sampling MCCFR / extensive-form fictitious play /
 magnetic mirror descent.  The C-ABI is include/osg_abi.h.
 """
@@ -31,6 +31,9 @@ def __getattr__(name):
     if name in ("Context", "Game", "StateBatch", "SolvedGame", "TabularSolver", "DCFRSolver", "LCFRSolver", "XFPSolver", "MMDSolver"):
         from . import engine
         return getattr(engine, name)
+    if name in ("ISMCTSBot", "ISMCTSFinalPolicyType", "ChildSelectionPolicy"):
+        from . import ismcts
+        return getattr(ismcts, name)
     if name in ("BatchedEnvironment", "TimeStep", "StepType", "ObservationType"):
         from . import vector_env
         return getattr(vector_env, name)

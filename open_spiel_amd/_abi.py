@@ -64,6 +64,20 @@ class AbCfg(C.Structure):
     ]
 
 
+class IsmctsCfg(C.Structure):
+    _fields_ = [
+        ("uct_c", C.c_double),
+        ("max_simulations", C.c_int32),
+        ("n_rollouts", C.c_int32),
+        ("max_world_samples", C.c_int32),
+        ("final_policy_type", C.c_int32),
+        ("child_selection_policy", C.c_int32),
+        ("max_nodes", C.c_int32),
+        ("seed", C.c_uint64),
+        ("index_offset", C.c_int64),
+    ]
+
+
 class CfrCfg(C.Structure):
     _fields_ = [
         ("alternating_updates", C.c_int32),
@@ -129,6 +143,9 @@ SIGNATURES = {
     "osg_rollout": (INT, [VP, U64, I64, INT, VP, VP, INT]),
     "osg_mcts_search": (INT, [VP, C.POINTER(MctsCfg), VP, VP, VP, VP, VP, INT]),
     "osg_alpha_beta_search": (INT, [VP, C.POINTER(AbCfg), VP, VP, VP, VP, INT]),
+    "osg_ismcts_search": (INT, [VP, C.POINTER(IsmctsCfg), VP, VP, VP, VP, VP, VP, VP, INT]),
+    "osg_ismcts_tree_sizes": (INT, [VP, VP, VP]),
+    "osg_ismcts_tree_download": (INT, [VP, I64, I64, VP, VP, VP, VP, VP, VP]),
     "osg_solve_create": (INT, [VP, C.c_char_p, C.c_int32, C.c_int32, I64, C.POINTER(VP)]),
     "osg_solve_destroy": (INT, [VP]),
     "osg_solve_sizes": (INT, [VP, C.POINTER(I64), C.POINTER(C.c_int32), C.POINTER(I64), C.POINTER(I64)]),

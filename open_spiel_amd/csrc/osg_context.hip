@@ -23,7 +23,7 @@ hipError_t ctx_grow(osg_ctx* ctx, DeviceArray<T>& buf, size_t n) {
   if (const hipError_t e = hipStreamSynchronize(ctx->stream); e != hipSuccess) return e;
   return buf.alloc(n);
 }
-template hipError_t ctx_grow(osg_ctx*, DeviceArray<unsigned char>&, size_t);  // d_scratch, d_mcts_pool
+template hipError_t ctx_grow(osg_ctx*, DeviceArray<unsigned char>&, size_t);  // d_scratch, d_mcts_pool, d_ismcts
 template hipError_t ctx_grow(osg_ctx*, DeviceArray<double>&, size_t);         // d_mcts_logs
 template hipError_t ctx_grow(osg_ctx*, DeviceArray<int32_t>&, size_t);        // d_mcts_queue
 
@@ -104,6 +104,8 @@ int osg_ctx_trim(osg_ctx* ctx) {
   ctx->d_mcts_pool.reset();
   ctx->d_scratch.reset();
   ctx->d_mcts_queue.reset();
+  ctx->d_ismcts.reset();
+  ctx->ismcts.n = 0;   // the trees of the last information-set search go with their workspace
   return OSG_OK;
 }
 

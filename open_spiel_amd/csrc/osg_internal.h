@@ -132,17 +132,29 @@ int parse_game(const char* game_string, GameSpec* out);
 
 }  // namespace osg
 
+namespace osg {
+// What osg_ismcts_tree_* need of the context's last osg_ismcts_search (n == 0: none): its trees stay in d_ismcts.
+struct IsmctsKept {
+  int64_t n = 0, lanes = 0;   // roots searched; lanes of the launch (lane l held roots l, l + lanes, ...)
+  int max_nodes = 0, node_words = 0;
+  size_t o_draws = 0, o_count = 0, o_table = 0;   // offsets in d_ismcts: draws [n] u32, node counts [n] i32, the tables
+  std::string game;   // canonical string of the roots' game
+};
+}  // namespace osg
+
 struct osg_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   osg::DeviceArray<unsigned long long> d_illegal;  // device counter of illegal applies
-  // Grow-only, reused from call to call (osg::ctx_grow); osg_ctx_trim gives the scratch, the pool and the queue back.
+  // Grow-only, reused from call to call (osg::ctx_grow); osg_ctx_trim gives the scratch, the pools and the queue back.
   osg::DeviceArray<unsigned char> d_scratch;       // reusable staging buffer
   osg::DeviceArray<unsigned char> d_mcts_pool;     // MCTS node pool, reused across searches
   osg::DeviceArray<double> d_mcts_logs;            // log(n) table shared with the host libm
   osg::DeviceArray<int32_t> d_mcts_queue;          // wave-per-root search as a work queue: [0] next ticket, [1..256] the cost
                                                    // histogram / bucket offsets, then the root order [roots]
+  osg::DeviceArray<unsigned char> d_ismcts;        // IS-MCTS node tables, hashes and root samples; kept for osg_ismcts_tree_*
+  osg::IsmctsKept ismcts;
   int num_cus = 0;
   // Lifetime: the creator holds one reference, every batch / solver / communicator made on the context
   // another; osg_ctx_destroy drops the creator's, and the device resources go with the last one, so a
