@@ -758,6 +758,41 @@ typedef struct {
 } osg_action_values_out;       /* any member may be NULL */
 int osg_cfr_action_values(osg_cfr* s, int which_policy, const double* policy, int responder, int on_host,
                           const osg_action_values_out* out);
+/* Populations of policies (PSRO / double oracle, open_spiel/python/algorithms/psro_v2/): `tables` is a stack
+ * [n_tables, I, Amax] of policy tables in the layout which_policy = 2 uses (rows in the solver's infostate order, columns
+ * the row's legal actions ascending, padding cells ignored); "policy k of player p" is table k's rows at p's infostates.
+ * A solver created in any mode may be used: its own tables are neither read nor written.  The games have perfect recall.
+ *
+ * osg_cfr_profile_returns: the payoff-tensor cells expected_game_score.policy_value
+ * (open_spiel/python/algorithms/expected_game_score.py:35-58) gives one tree walk at a time.  profiles is [n_profiles, P]
+ * int32: in profile m player q follows table profiles[m, q], and returns[m, :] = policy_value(root, [policy_{profiles[m, 0]}
+ * .. policy_{profiles[m, P-1]}]).  The whole tensor is the call with the cartesian product, PSRO's update the call with
+ * the new cells.  Computed in sequence form: returns[m, q] = sum over the terminals z of u_q(z) * c(z) * prod_p
+ * plan_{profiles[m, p]}(p's last action before z), plan_k[i, a] = (player's own reach of i under table k) * table k[i, a];
+ * csrc/osg_population.h has the arithmetic and the one order of the sum.  The bits of returns[m, :] depend on the game and
+ * on the P tables profile m names, not on its position, on n_profiles, on the other profiles or tables or on on_host.
+ *
+ * osg_cfr_aggregate_policies: PolicyAggregator.aggregate (open_spiel/python/algorithms/policy_aggregator.py:130-265) for
+ * all players at once: the behavioural policy that is realization-equivalent to every player p mixing its tables with
+ * weights[p, :] ([P, n_tables]).  For infostate i of player p and legal action a, over i's member histories h in the
+ * reference's visiting order and k ascending, acc[i, a] += reach_k(h) * table k[i, a], reach_k(h) = weights[p, k] times
+ * p's own probabilities under table k on h's root path in path order; out[i, a] = (acc[i, a] + epsilon) / sum_a'
+ * (acc[i, a'] + epsilon) (:171-178; the reference's epsilon is 1e-40), padding cells 0.  A table of weight 0 contributes
+ * nothing; a row no table reaches comes out uniform.
+ *
+ * on_host = 1: every pointer is host memory and the call returns when the outputs have arrived.  on_host = 0: every
+ * pointer is device memory and everything is enqueued on the context's stream without waiting (the first population call
+ * on a solver also builds and uploads the terminals' plan indices, which waits).  A refused call writes nothing and sets
+ * osg_last_error: a null pointer, n_tables < 1, a profile index outside [0, n_tables), a negative or non-finite weight,
+ * epsilon < 0 (OSG_ERR_INVALID); more than 2^22 profiles per call, a table stack of more than 2^30 bytes (n_tables * I *
+ * Amax * 8; the solver keeps as much scratch again, and on_host = 1 a device copy of the stack), rows wider than 8 actions
+ * (OSG_ERR_UNSUPPORTED, the message names the limit).  With on_host = 0 the indices and weights are checked on the
+ * device: the refused call's kernels write nothing, and the next population call on the solver returns the error instead
+ * of running.  osg_cfr_last_eval_kernel: "k_pop_returns", "k_pop_aggregate" (one form each). */
+int osg_cfr_profile_returns(osg_cfr* s, const double* tables, int n_tables, const int32_t* profiles, int64_t n_profiles,
+                            int on_host, double* returns /* [n_profiles, P] */);
+int osg_cfr_aggregate_policies(osg_cfr* s, const double* tables, int n_tables, const double* weights /* [P, n_tables] */,
+                               double epsilon, int on_host, double* out_table /* [I, Amax] */);
 /* The flattened tree's edges: parent [H] (-1 at the root) and the action / chance outcome on the edge from the
  * parent [H] (-1 at the root); histories are numbered level by level.  Either may be NULL. */
 int osg_cfr_tree_edges(const osg_cfr* s, int32_t* parent, int32_t* action);

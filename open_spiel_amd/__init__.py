@@ -5,7 +5,8 @@ path: batched LegalActions / ApplyAction / IsTerminal / Returns /
 ObservationTensor for tic_tac_toe, connect_four, hex, kuhn_poker and
 leduc_poker, random-rollout evaluation, MCTS, information-set MCTS and alpha-beta search over batches of roots, and
 tabular CFR / Discounted CFR / external-sampling MCCFR / extensive-form fictitious play /
-magnetic mirror descent.  The C-ABI is include/osg_abi.h.
+magnetic mirror descent, and payoff tensors / policy aggregation / PSRO over populations of policies.
+The C-ABI is include/osg_abi.h.
 """
 from ._abi import OsgError, describe, lib  # noqa: F401
 
@@ -31,6 +32,9 @@ def __getattr__(name):
     if name in ("Context", "Game", "StateBatch", "SolvedGame", "TabularSolver", "DCFRSolver", "LCFRSolver", "XFPSolver", "MMDSolver"):
         from . import engine
         return getattr(engine, name)
+    if name == "PSROSolver":
+        from . import psro
+        return psro.PSROSolver
     if name in ("ISMCTSBot", "ISMCTSFinalPolicyType", "ChildSelectionPolicy"):
         from . import ismcts
         return getattr(ismcts, name)

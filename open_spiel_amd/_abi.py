@@ -203,6 +203,8 @@ SIGNATURES = {
     "osg_cfr_infostate_player": (INT, [VP, I64]),
     "osg_cfr_best_response": (INT, [VP, INT, VP, VP, VP]),
     "osg_cfr_action_values": (INT, [VP, INT, VP, INT, INT, C.POINTER(ActionValuesOut)]),
+    "osg_cfr_profile_returns": (INT, [VP, VP, INT, VP, I64, INT, VP]),
+    "osg_cfr_aggregate_policies": (INT, [VP, VP, INT, VP, C.c_double, INT, VP]),
     "osg_cfr_infostate_key": (INT, [VP, I64, C.c_char_p, INT]),
     "osg_cfr_best_response_history_values": (INT, [VP, INT, VP, INT, VP]),
     "osg_cfr_tree_edges": (INT, [VP, VP, VP]),

@@ -7,6 +7,7 @@
 //   osg_cfr_eval.hip    k_policy_eval, k_geval_*, k_eval_jobs     ExpectedReturns / TabularBestResponse / NashConv
 //   osg_cfr_qvalues.hip k_qvalues_small, k_qv_*       per-infostate action values and reaches of a policy
 //   osg_cfr_mccfr.hip   k_mccfr*, k_os_mccfr*, ...    external / outcome sampling MCCFR and their entry points
+//   osg_cfr_population.hip k_pop_*                    payoff-tensor cells and policy aggregation of a population of tables
 //
 //   osg_cfr_xfp.hip     k_xfp_small, k_xfp_*          extensive-form fictitious play
 //   osg_cfr_mmd.hip     k_mmd_small, k_mmd_*          magnetic mirror descent (MmdState lives there)
@@ -436,6 +437,23 @@ struct ResidentPlan {   // LDS-resident MCCFR traversal (k_mccfr_resident): buil
   DeviceArray<double> uret, uprob;
 };
 
+struct PopulationPlan {   // payoff-tensor cells and policy aggregation (osg_cfr_population.hip): built at the first call
+  bool built = false;
+  int T = 0;                        // terminal histories
+  int compute_units = 0;            // of the context's device
+  DeviceArray<int32_t> term_seq;    // [T, P] the plan index of player p's last action on the terminal's root path, -1: none
+  DeviceArray<double> term_chance;  // [T] the product of the chance probabilities on it
+  DeviceArray<double> term_ret;     // [T, P] Returns()
+  // grow-only, bounded by the limits the entry points state
+  DeviceArray<double> plans;        // [K, I, A] the realization plan of every table of the call
+  DeviceArray<double> tables;       // on_host calls: the caller's stack, weights and profiles on the device, and the results
+  DeviceArray<double> weights;
+  DeviceArray<int32_t> profiles;
+  DeviceArray<double> out;
+  DeviceArray<unsigned int> refused;   // [1] raised by a call's checking kernel: the kernels behind it write nothing
+  PinnedArray<unsigned int> h_refused; // mapped: the same, kept until the next population call reports it
+};
+
 }  // namespace osg_cfr_impl
 
 using namespace osg_cfr_impl;
@@ -506,6 +524,7 @@ struct osg_cfr {
   // per-infostate action values (osg_cfr_qvalues.hip): the results of a call, allocated at the first one
   DeviceArray<double> d_qv_out;
   DeviceArray<int32_t> d_qv_best;
+  PopulationPlan population;
   // magnetic mirror descent (osg_cfr_mmd.hip): built at the first osg_mmd_* call
   std::unique_ptr<MmdState> mmd;
 

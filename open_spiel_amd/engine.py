@@ -848,6 +848,90 @@ class TabularSolver:
                     counterfactual_reach_probs_vs_br=res["cf_reach"][rows], player_reach_probs_vs_br=res["player_reach"][rows],
                     rows=rows)
 
+    def _table_stack(self, tables, device, what):
+        """`tables` as a contiguous fp64 [K, I, Amax] stack: numpy, or with device=True a tensor on the context's device."""
+        I, A = self.num_infostates, self.amax
+        if device:
+            stack = torch.as_tensor(tables, dtype=torch.float64, device=self.ctx.device).contiguous()
+        else:
+            stack = np.ascontiguousarray(tables, np.float64)
+        if stack.ndim != 3 or tuple(stack.shape[1:]) != (I, A) or stack.shape[0] < 1:
+            raise OsgError(f"{what}: expected a stack of tables of shape [K >= 1, {I}, {A}], not {tuple(stack.shape)}")
+        return stack
+
+    def infostate_players(self):
+        """[I] int32: the player who acts at each information state, in this solver's row order."""
+        return np.array([lib().osg_cfr_infostate_player(self._h, i) for i in range(self.num_infostates)], np.int32)
+
+    def profile_returns(self, tables, profiles, device=False):
+        """The expected returns of every listed profile of a population (expected_game_score.policy_value, one tree walk
+        per profile in the reference): `tables` is a stack [K, I, Amax] of policy tables in this solver's layout,
+        "policy k of player p" table k's rows at p's infostates; `profiles` is [M, P] int, player q of profile m
+        follows table profiles[m, q].  Returns [M, P].  device=False: numpy in and out.  device=True: torch tensors
+        (tables fp64, profiles int32) on the context's device, enqueued on its stream with no host round trip; there an
+        index out of range is found on the device: the call writes nothing and the next population call raises.
+        osg_cfr_profile_returns in include/osg_abi.h has the definitions and the limits."""
+        P = _abi.describe(self.game_string).num_players
+        stack = self._table_stack(tables, device, "profile_returns")
+        if device:
+            prof = torch.as_tensor(profiles, device=self.ctx.device).to(torch.int32).contiguous()
+        else:
+            prof = np.ascontiguousarray(profiles)
+            if prof.dtype.kind not in "iu":
+                raise OsgError("profile_returns: profiles must be integers")
+            prof = np.ascontiguousarray(prof, np.int32)
+        if prof.ndim != 2 or prof.shape[1] != P:
+            raise OsgError(f"profile_returns: expected profiles of shape [M, {P}], not {tuple(prof.shape)}")
+        M = int(prof.shape[0])
+        if device:
+            out = torch.zeros((M, P), dtype=torch.float64, device=self.ctx.device)
+            addr = lambda t: t.data_ptr()
+        else:
+            out = np.zeros((M, P))
+            addr = lambda a: a.ctypes.data
+        check(lib().osg_cfr_profile_returns(self._h, addr(stack), int(stack.shape[0]), addr(prof), M, 0 if device else 1, addr(out)))
+        return out
+
+    def payoff_tensors(self, tables, populations=None, device=False):
+        """The meta-game of a population in psro_v2's `meta_games` convention: a list of P arrays of shape
+        [K_0, ..., K_{P-1}], out[q][i_0, ..., i_{P-1}] the return of player q when every player p follows its i_p-th
+        policy.  populations[p] lists the tables (indices into `tables`) that are player p's policies; default: every
+        table for every player.  One profile_returns call over the cartesian product."""
+        P = _abi.describe(self.game_string).num_players
+        stack = self._table_stack(tables, device, "payoff_tensors")
+        if populations is None:
+            populations = [range(int(stack.shape[0]))] * P
+        pops = [np.asarray(list(p), np.int32) for p in populations]
+        if len(pops) != P or any(p.ndim != 1 or len(p) < 1 for p in pops):
+            raise OsgError(f"payoff_tensors: expected {P} non-empty lists of table indices")
+        grid = np.stack(np.meshgrid(*pops, indexing="ij"), axis=-1).reshape(-1, P).astype(np.int32)
+        if device:
+            grid = torch.as_tensor(grid, device=self.ctx.device)
+        ret = self.profile_returns(stack, grid, device=device)
+        shape = [len(p) for p in pops]
+        return [ret[:, q].reshape(shape) for q in range(P)]
+
+    def aggregate_policies(self, tables, weights, epsilon=1e-40, device=False):
+        """policy_aggregator.PolicyAggregator(game, epsilon).aggregate for all players at once: the [I, Amax] behavioural
+        policy that is realization-equivalent to every player p mixing the tables of the stack [K, I, Amax] with
+        weights[p] ([P, K], >= 0 and finite).  A table of weight 0 contributes nothing; a row no table reaches is
+        uniform.  device as for profile_returns.  osg_cfr_aggregate_policies in include/osg_abi.h has the definition."""
+        P = _abi.describe(self.game_string).num_players
+        stack = self._table_stack(tables, device, "aggregate_policies")
+        K = int(stack.shape[0])
+        if device:
+            w = torch.as_tensor(weights, dtype=torch.float64, device=self.ctx.device).contiguous()
+            out = torch.zeros((self.num_infostates, self.amax), dtype=torch.float64, device=self.ctx.device)
+            addr = lambda t: t.data_ptr()
+        else:
+            w = np.ascontiguousarray(weights, np.float64)
+            out = np.zeros((self.num_infostates, self.amax))
+            addr = lambda a: a.ctypes.data
+        if tuple(w.shape) != (P, K):
+            raise OsgError(f"aggregate_policies: expected weights of shape {(P, K)}, not {tuple(w.shape)}")
+        check(lib().osg_cfr_aggregate_policies(self._h, addr(stack), K, addr(w), float(epsilon), 0 if device else 1, addr(out)))
+        return out
+
     def average_policy(self):
         t = self.tables()
         return {k: [(int(t["legal"][i, a]), float(t["avg_policy"][i, a])) for a in range(t["nact"][i])]
