@@ -802,6 +802,44 @@ int osg_cfr_infostate_key(const osg_cfr* s, int64_t i, char* buf, int cap);
 /* The player who acts at infostate i (State::CurrentPlayer() of its histories), -1 for a bad index. */
 int osg_cfr_infostate_player(const osg_cfr* s, int64_t i);
 
+/* ---- PSRO's meta-strategy solvers on a batch of normal-form meta-games --------------------------
+ * Projected replicator dynamics (open_spiel/python/algorithms/projected_replicator_dynamics.py) and regret matching
+ * (regret_matching.py) with nfg_utils.StrategyAverager's average: psro_v2's "prd" and "rm".  A problem is P payoff
+ * tensors [K_0 .. K_{P-1}], one per player, row-major; a call holds n_problems of one shape and runs every iteration of
+ * every problem in ONE launch, a workgroup per problem, with the strategies, regrets and sums in LDS and registers.
+ * csrc/osg_meta_solver.h has the arithmetic and the one order of every sum; the reference's sums go through BLAS, so it is
+ * matched within rounding, not bit for bit.  The bits of a problem's result depend on its tensors, its cfg and its initial
+ * strategies, not on its position, on n_problems, on the other problems, on `form` or on on_host.
+ *   cfgs      n_cfgs = 1: one cfg for every problem; n_cfgs = n_problems: problem b runs cfgs[b] (a sweep of dt, gamma,
+ *             iterations or method over copies of one meta-game, or many meta-games, is one launch).  ALWAYS host memory.
+ *   form      0: the tensors are staged in LDS where P * K_0 * .. * K_{P-1} doubles fit the workgroup's LDS limit (from
+ *             the device's properties) beside the strategies, and read from global memory otherwise; 1 / 2 name one
+ *             (1 where it does not fit: OSG_ERR_UNSUPPORTED).  Every cfg of a call names the same form.
+ *   window    0: the average of the whole trajectory (the initial strategies and every iteration); n > 0: of the last
+ *             min(n, iterations + 1) entries (average_over_last_n_strategies).
+ *   initial   [n_problems, sum K_p], player after player, or NULL: uniform.  iterations = 0 returns it.
+ *   average, last   [n_problems, sum K_p]: the averaged strategies and the last iterate; last may be NULL.
+ * on_host = 1: tensors, initial, average and last are host memory and the call returns when the outputs have arrived;
+ * on_host = 0: they are device memory and the launch is enqueued on the context's stream.
+ * A refused call writes nothing.  OSG_ERR_INVALID: a null ctx, shape, cfgs, tensors or average, n_problems < 0, n_cfgs
+ * neither 1 nor n_problems, a method other than 0 / 1, iterations or window < 0, a form outside 0..2 or not the same in
+ * every cfg, a dt or gamma that is not finite.  OSG_ERR_UNSUPPORTED: fewer than 2 or more than 5 players, a K_p outside
+ * 1..64, more than 2^22 cells per tensor, more than 10^8 iterations, more than 2^20 problems or 2^32 bytes of tensors per
+ * call.  The tensors are expected finite. */
+typedef struct osg_meta_cfg {
+  int32_t method;       /* 0 projected replicator dynamics, 1 regret matching */
+  int32_t iterations;
+  double dt;            /* projected replicator dynamics only (prd_dt) */
+  double gamma;         /* prd_gamma / gamma */
+  int32_t window;       /* 0: the whole trajectory */
+  int32_t use_approx;   /* projected replicator dynamics only: _approx_simplex_projection */
+  int32_t form;         /* 0 by size, 1 tensors resident in LDS, 2 tensors read from global memory */
+  int32_t reserved;     /* 0 */
+} osg_meta_cfg;
+int osg_meta_solve(osg_ctx* ctx, int n_players, const int32_t* shape /* [P] */, int64_t n_problems,
+                   const double* tensors /* [n_problems, P, K_0 .. K_{P-1}] */, const osg_meta_cfg* cfgs, int64_t n_cfgs,
+                   const double* initial, double* average, double* last, int on_host);
+
 /* ---- multi-GPU exchange step ---------------------------------------------------
  * One process per GPU.  Units shard by global index with no data-path collective; the ONE exchange
  * on the path is external-sampling MCCFR's all-reduce(sum) of the regret / average-policy delta

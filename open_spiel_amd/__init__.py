@@ -5,7 +5,8 @@ path: batched LegalActions / ApplyAction / IsTerminal / Returns /
 ObservationTensor for tic_tac_toe, connect_four, hex, kuhn_poker and
 leduc_poker, random-rollout evaluation, MCTS, information-set MCTS and alpha-beta search over batches of roots, and
 tabular CFR / Discounted CFR / external-sampling MCCFR / extensive-form fictitious play /
-magnetic mirror descent, and payoff tensors / policy aggregation / PSRO over populations of policies.
+magnetic mirror descent, payoff tensors / policy aggregation / PSRO over populations of policies, and PSRO's
+meta-strategy solvers (projected replicator dynamics, regret matching) on batches of normal-form meta-games.
 The C-ABI is include/osg_abi.h.
 """
 from ._abi import OsgError, describe, lib  # noqa: F401
@@ -35,6 +36,10 @@ def __getattr__(name):
     if name == "PSROSolver":
         from . import psro
         return psro.PSROSolver
+    if name in ("meta_solvers", "solve_meta_games"):   # (its projected_replicator_dynamics / regret_matching: by the module)
+        import importlib
+        module = importlib.import_module(".meta_solvers", __name__)
+        return module if name == "meta_solvers" else module.solve_meta_games
     if name in ("ISMCTSBot", "ISMCTSFinalPolicyType", "ChildSelectionPolicy"):
         from . import ismcts
         return getattr(ismcts, name)

@@ -93,7 +93,20 @@ class CfrCfg(C.Structure):
     ]
 
 
-class ActionValuesOut(C.Structure):   # osg_action_values_out: host or device addresses, any may be None
+class MetaCfg(C.Structure):   # osg_meta_cfg
+    _fields_ = [
+        ("method", C.c_int32),
+        ("iterations", C.c_int32),
+        ("dt", C.c_double),
+        ("gamma", C.c_double),
+        ("window", C.c_int32),
+        ("use_approx", C.c_int32),
+        ("form", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class ActionValuesOut(C.Structure):  # osg_action_values_out: host or device addresses, any may be None
     _fields_ = [(name, C.c_void_p) for name in (
         "root_values", "action_values", "cf_reach", "player_reach", "reach", "chance_reach", "cf_reach_by_value",
         "weighted_values", "best_response_value", "best_index")]
@@ -205,6 +218,7 @@ SIGNATURES = {
     "osg_cfr_action_values": (INT, [VP, INT, VP, INT, INT, C.POINTER(ActionValuesOut)]),
     "osg_cfr_profile_returns": (INT, [VP, VP, INT, VP, I64, INT, VP]),
     "osg_cfr_aggregate_policies": (INT, [VP, VP, INT, VP, C.c_double, INT, VP]),
+    "osg_meta_solve": (INT, [VP, INT, VP, I64, VP, VP, I64, VP, VP, VP, INT]),
     "osg_cfr_infostate_key": (INT, [VP, I64, C.c_char_p, INT]),
     "osg_cfr_best_response_history_values": (INT, [VP, INT, VP, INT, VP]),
     "osg_cfr_tree_edges": (INT, [VP, VP, VP]),

@@ -1,18 +1,22 @@
 """Policy-space response oracles (Lanctot et al. 2017; open_spiel/python/algorithms/psro_v2/) with exact best responses
 on the kuhn_poker / leduc_poker trees: the population, the payoff tensors' new cells, the aggregation of a meta-strategy
 into one behavioural policy and the best responses to it all run on the device (TabularSolver.profile_returns,
-aggregate_policies, osg_cfr_best_response); only the meta-solver, a function of the small payoff tensors, runs on the
-host.  Out of scope: strategy selectors other than "add every player's best response", sampled meta-game estimation
-(sims_per_entry), reinforcement-learning oracles, device ports of projected replicator dynamics or the LP Nash solver
-(pass them as `meta_solver`)."""
+aggregate_policies, osg_cfr_best_response), and so do psro_v2's "prd" and "rm" meta-solvers (projected replicator
+dynamics and regret matching, meta_solvers.py: every iteration of a solve in one launch); a meta-solver passed as a
+callable runs on the host.  Out of scope: strategy selectors other than "add every player's best response", sampled
+meta-game estimation (sims_per_entry), reinforcement-learning oracles, the LP Nash solver ("nash"; pass one as a
+callable), "uniform_biased", joint meta-strategies and alpha-rank."""
+import functools
 import itertools
 
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, meta_solvers
 from ._abi import OsgError, check, lib
 from .engine import TabularSolver
+
+DEVICE_META_SOLVERS = {"prd": meta_solvers.projected_replicator_dynamics, "rm": meta_solvers.regret_matching}
 
 
 def uniform_meta_solver(payoff_tensors):
@@ -21,25 +25,31 @@ def uniform_meta_solver(payoff_tensors):
 
 
 class PSROSolver:
-    """PSRO / double oracle on the device.  `meta_solver`: "uniform", or any callable that takes the payoff tensors (a
-    list of P arrays [K_0, ..., K_{P-1}], psro_v2's `meta_games`) and returns P weight vectors, the reference's
-    meta-solvers among them.  `initial`: "uniform", or an [I, Amax] policy table in the solver's layout: every player's
+    """PSRO / double oracle on the device.  `meta_solver`: "uniform"; "prd" or "rm", projected replicator dynamics or
+    regret matching on the device with `meta_solver_kwargs` under the reference's names (prd_iterations, prd_dt,
+    prd_gamma / iterations, gamma, average_over_last_n_strategies, ...; its defaults otherwise); or any callable that takes
+    the payoff tensors (a list of P arrays [K_0, ..., K_{P-1}], psro_v2's `meta_games`) and returns P weight vectors, the
+    reference's meta-solvers among them.  `initial`: "uniform", or an [I, Amax] policy table in the solver's layout: every player's
     first policy.  With the uniform meta-solver and the uniform initial policy this is fictitious play with kept
     oracles: the aggregate after t iterations is XFPSolver's average policy, up to argmax ties.
 
     The population is a stack of tables on the device (grown geometrically); every iteration appends ONE table whose
     rows are the one-hot best responses of all players, and player p's population is a list of indices into the stack."""
 
-    def __init__(self, ctx, game_string, meta_solver="uniform", initial="uniform"):
+    def __init__(self, ctx, game_string, meta_solver="uniform", initial="uniform", meta_solver_kwargs=None):
         self.ctx = ctx
         self.game_string = game_string
         self.solver = TabularSolver(ctx, game_string)
         self.num_players = _abi.describe(game_string).num_players
         I, A = self.solver.num_infostates, self.solver.amax
+        if meta_solver_kwargs and not (isinstance(meta_solver, str) and meta_solver in DEVICE_META_SOLVERS):
+            raise OsgError("PSROSolver: meta_solver_kwargs go with meta_solver 'prd' or 'rm'")
         if meta_solver == "uniform":
             meta_solver = uniform_meta_solver
+        elif isinstance(meta_solver, str) and meta_solver in DEVICE_META_SOLVERS:
+            meta_solver = functools.partial(DEVICE_META_SOLVERS[meta_solver], ctx, **dict(meta_solver_kwargs or {}))
         if not callable(meta_solver):
-            raise OsgError(f"PSROSolver: meta_solver must be 'uniform' or a callable, not {meta_solver!r}")
+            raise OsgError(f"PSROSolver: meta_solver must be 'uniform', 'prd', 'rm' or a callable, not {meta_solver!r}")
         self._meta_solver = meta_solver
         self._nact = np.zeros(I, np.int32)
         check(lib().osg_cfr_tables(self.solver._h, self._nact.ctypes.data, None, None, None, None, None))
