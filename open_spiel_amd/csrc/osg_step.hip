@@ -2,6 +2,7 @@
 // File map: osg_batch_internal.h.
 #include "osg_batch_internal.h"
 #include "osg_c4_step.h"
+#include "step/osg_c4_step_split.h"
 #include "osg_ttt_step.h"
 
 namespace {
@@ -233,52 +234,72 @@ k_step_c4x2(typename G::Params p, const uint64_t* src, uint64_t* dst, int64_t n,
 }
 
 // THE HEADLINE KERNEL (with k_step_c4std2 below): the fused step of the standard connect_four board (6 x 7, four in a
-// row), one state per thread, workgroups of 128.  The step itself is c4_fused_step (osg_c4_step.h: straight-line selects on the two
-// packed planes, ONE line test — the mover's —, the successor's legal mask gathered by two 24-bit multiplies; the
-// result of the game lives in plane 0's spare byte).  2^20 states are 16 384 wavefronts, TWO rounds of the chip's
-// 8 192 wave slots: the second round's loads overlap the first round's stores, which measured faster than two
-// states per thread with 16-byte accesses in one round (6.18-6.30 vs 6.48-6.67 us per launch at 2^20 states in the
-// same runs, 97.8-99.7 vs 101.8-103.6 us at 2^24; workgroups of 64 / 256 / 1024: 6.73 / 6.17-6.35 / 6.16-6.19 us at
-// 2^20 and 107.7 / 99.6-102.3 / 105.0-105.8 us at 2^24).  Any batch size, no alignment requirement on the side arrays.
+// row), one state per thread, workgroups of 128.  The step is c4_place + c4_finish (step/osg_c4_step_split.h:
+// c4_fused_step of osg_c4_step.h cut where the o plane is final and written on the planes' 32-bit halves — ONE line
+// test, the mover's, as funnel shifts of the low word; the successor's legal mask gathered by two 24-bit multiplies;
+// the result of the game lives in plane 0's spare byte).  Any batch size, no alignment requirement on the side arrays.
+// The shape of both kernels (round 10; figures for k_step_c4std2 in profiles/r10a_c4_step_parts.txt):
+//  - kExact (the grid covers the batch exactly): no test of i against n, so the wave asks for all its arguments in one
+//    scalar clause and its first load waits for one scalar round trip, not two;
+//  - the o plane (8 of a state's 18 bytes out) leaves right after placement, ahead of the line tests (the compiler
+//    keeps the store there without being told: instruction 99 of 210; a scheduling barrier behind it measured
+//    0.016 us slower, profiles/r10a_c4_step_dropped.txt);
+//  - stores are non-temporal: the successor records are not read again by this launch, and written around the L2 they
+//    neither displace the inputs still to be read nor wait for a write-back at the end of the kernel (measured in
+//    round 3: 6.1-6.3 -> 5.0-5.1 us per launch at 2^20 states, 97-99 -> 89-91 us at 2^24; non-temporal LOADS as well: 6.8 us).
+template <bool kExact>
 __global__ void __launch_bounds__(kC4StepBlock)
 k_step_c4std(const uint64_t* src, uint64_t* dst, int64_t n, const uint8_t* __restrict__ actions,  // src may BE dst
              uint8_t* __restrict__ mask_out, uint8_t* __restrict__ status) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kC4StepBlock + threadIdx.x;
-  if (i >= n) return;
-  uint64_t x = src[i], o = src[n + i];
-  const uint32_t r = c4_fused_step(x, o, actions[i]);
-  // Non-temporal stores: the successor records are not read again by this launch, and written around the L2 they
-  // neither displace the inputs still to be read nor wait for a write-back at the end of the kernel (measured:
-  // 6.1-6.3 -> 5.0-5.1 us per launch at 2^20 states, 97-99 -> 89-91 us at 2^24; non-temporal LOADS as well: 6.8 us).
-  __builtin_nontemporal_store(x, dst + i);
-  __builtin_nontemporal_store(o, dst + n + i);
+  if constexpr (!kExact) {
+    if (i >= n) return;
+  }
+  const C4Placed p = c4_place(src[i], src[n + i], actions[i]);
+  __builtin_nontemporal_store((static_cast<uint64_t>(p.no_hi) << 32) | p.no_lo, dst + n + i);
+  uint32_t nflags;
+  const uint32_t r = c4_finish(p, nflags);
+  __builtin_nontemporal_store((static_cast<uint64_t>(p.nx_hi | (nflags << 24)) << 32) | p.nx_lo, dst + i);
   __builtin_nontemporal_store(static_cast<uint8_t>(r), mask_out + i);
   __builtin_nontemporal_store(static_cast<uint8_t>(r >> 8), status + i);
 }
 
 // The same step with TWO consecutive states per thread (16-byte plane accesses, u16 side arrays) for even batches
-// with 2-byte aligned side arrays — the headline configuration.  With ordinary stores one state per thread was the
-// faster layout (two rounds of wavefronts: the second round's loads overlap the first round's stores); with
-// non-temporal stores the wider accesses win again (same runs, 2^20 states: 5.07-5.08 vs 5.14-5.21 us per launch;
-// 2^24 states: 86.7-88.6 vs 90.6-91.7 us).
-__global__ void __launch_bounds__(kC4StepBlock)
+// with 2-byte aligned side arrays — the headline configuration: 2^20 states are 8 192 wavefronts, ONE round of the
+// chip's wave slots, so nothing of a launch overlaps a later round and the path from the first scalar load to the last
+// store is what a launch costs beyond its bytes.  Both placements, the o plane's store, both finishes, the rest.
+// Workgroups of ONE wavefront (round 10): 4.38 -> 4.07 us per launch at 2^20 states against workgroups of 128, 86.9 ->
+// 86.2 us at 2^24 (profiles/r10a_c4_step_parts.txt, c3 / c4; workgroups of 256: 4.53 against 4.27 in the run of
+// profiles/r10a_c4_step_dropped.txt) — a wavefront that need not start beside a second one starts sooner.
+// Per lane of two states (hipcc -S, gfx950, exact form): 181 vector instructions, 14 of them 64-bit — 7 in the step (the
+// columns' cells 2 shifts, the dropped stones 2 shifts, their tests 2 compares, the byte offset 1 shift) and 7 address
+// adds — so 195 issue slots, 34 VGPRs; before round 10: 202, 35 (26 + 9), 237, 37.
+constexpr int kC4PairBlock = 64;
+template <bool kExact>
+__global__ void __launch_bounds__(kC4PairBlock)
 k_step_c4std2(const uint64_t* src, uint64_t* dst, int64_t n, const uint8_t* __restrict__ actions,  // src may BE dst
               uint8_t* __restrict__ mask_out, uint8_t* __restrict__ status) {
-  const int64_t i = (static_cast<int64_t>(blockIdx.x) * kC4StepBlock + threadIdx.x) * 2;
-  if (i >= n) return;
+  const int64_t i = (static_cast<int64_t>(blockIdx.x) * kC4PairBlock + threadIdx.x) * 2;
+  if constexpr (!kExact) {
+    if (i >= n) return;
+  }
   typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
   typedef uint8_t u8x2 __attribute__((ext_vector_type(2)));
   const u64x2 xs = *reinterpret_cast<const u64x2*>(src + i), os = *reinterpret_cast<const u64x2*>(src + n + i);
   const u8x2 av = *reinterpret_cast<const u8x2*>(actions + i);
-  uint64_t x0 = xs.x, x1 = xs.y, o0 = os.x, o1 = os.y;
-  const uint32_t r0 = c4_fused_step(x0, o0, av.x), r1 = c4_fused_step(x1, o1, av.y);
+  const C4Placed p0 = c4_place(xs.x, os.x, av.x), p1 = c4_place(xs.y, os.y, av.y);
   u64x2 xo, oo;
-  xo.x = x0; xo.y = x1; oo.x = o0; oo.y = o1;
+  oo.x = (static_cast<uint64_t>(p0.no_hi) << 32) | p0.no_lo;
+  oo.y = (static_cast<uint64_t>(p1.no_hi) << 32) | p1.no_lo;
+  __builtin_nontemporal_store(oo, reinterpret_cast<u64x2*>(dst + n + i));
+  uint32_t f0, f1;
+  const uint32_t r0 = c4_finish(p0, f0), r1 = c4_finish(p1, f1);
+  xo.x = (static_cast<uint64_t>(p0.nx_hi | (f0 << 24)) << 32) | p0.nx_lo;
+  xo.y = (static_cast<uint64_t>(p1.nx_hi | (f1 << 24)) << 32) | p1.nx_lo;
   u8x2 mo, so;
   mo.x = static_cast<uint8_t>(r0); mo.y = static_cast<uint8_t>(r1);
   so.x = static_cast<uint8_t>(r0 >> 8); so.y = static_cast<uint8_t>(r1 >> 8);
   __builtin_nontemporal_store(xo, reinterpret_cast<u64x2*>(dst + i));
-  __builtin_nontemporal_store(oo, reinterpret_cast<u64x2*>(dst + n + i));
   __builtin_nontemporal_store(mo, reinterpret_cast<u8x2*>(mask_out + i));
   __builtin_nontemporal_store(so, reinterpret_cast<u8x2*>(status + i));
 }
@@ -306,16 +327,22 @@ int osg_step(const osg_batch* src, osg_batch* dst, const uint8_t* d_actions, voi
   const bool planes16 = ((reinterpret_cast<uintptr_t>(src->words()) | reinterpret_cast<uintptr_t>(dst->words())) & 15u) == 0;
   if (planes16 && src->spec.desc.game_kind == kC4 && src->spec.c4_std && (n & 1) == 0 &&
       ((reinterpret_cast<uintptr_t>(d_actions) | reinterpret_cast<uintptr_t>(d_mask) | reinterpret_cast<uintptr_t>(d_status)) & 1u) == 0) {
-    k_step_c4std2<<<dim3(static_cast<unsigned>((n / 2 + kC4StepBlock - 1) / kC4StepBlock)), dim3(kC4StepBlock), 0, ctx->stream>>>(
-        static_cast<const uint64_t*>(src->words()), static_cast<uint64_t*>(dst->words()), n, d_actions,
-        static_cast<uint8_t*>(d_mask), d_status);
+    with_bool(n % (2 * kC4PairBlock) == 0, [&](auto exact) {   // (the grid covers the batch exactly: no bound test in the kernel)
+      k_step_c4std2<decltype(exact)::value><<<dim3(static_cast<unsigned>((n / 2 + kC4PairBlock - 1) / kC4PairBlock)), dim3(kC4PairBlock), 0, ctx->stream>>>(
+          static_cast<const uint64_t*>(src->words()), static_cast<uint64_t*>(dst->words()), n, d_actions,
+          static_cast<uint8_t*>(d_mask), d_status);
+      return OSG_OK;
+    });
     OSG_HIP(hipGetLastError());
     return OSG_OK;
   }
   if (src->spec.desc.game_kind == kC4 && src->spec.c4_std) {  // odd batches / unaligned side arrays: one state per thread
-    k_step_c4std<<<dim3(static_cast<unsigned>((n + kC4StepBlock - 1) / kC4StepBlock)), dim3(kC4StepBlock), 0, ctx->stream>>>(
-        static_cast<const uint64_t*>(src->words()), static_cast<uint64_t*>(dst->words()), n, d_actions,
-        static_cast<uint8_t*>(d_mask), d_status);
+    with_bool(n % kC4StepBlock == 0, [&](auto exact) {
+      k_step_c4std<decltype(exact)::value><<<dim3(static_cast<unsigned>((n + kC4StepBlock - 1) / kC4StepBlock)), dim3(kC4StepBlock), 0, ctx->stream>>>(
+          static_cast<const uint64_t*>(src->words()), static_cast<uint64_t*>(dst->words()), n, d_actions,
+          static_cast<uint8_t*>(d_mask), d_status);
+      return OSG_OK;
+    });
     OSG_HIP(hipGetLastError());
     return OSG_OK;
   }
