@@ -100,7 +100,19 @@ int osg_ctx_set_stream(osg_ctx* ctx, void* stream);
 /* ---- game description (no device needed) -------------------------------- */
 /* Replaces LoadGame(game_string) (open_spiel/spiel.cc:255) for the five hot-path
  * games; unknown parameters / wrong types are OSG_ERR_INVALID as in
- * spiel.cc:65-90, games or sizes without a device layout OSG_ERR_UNSUPPORTED. */
+ * spiel.cc:65-90, games or sizes without a device layout OSG_ERR_UNSUPPORTED.
+ * The sizes with a layout (every accepted string equals the reference at every ply; the message of a refusal names the limit):
+ *   connect_four  rows <= 127, columns <= 32, (rows + 1) * columns <= 128, and the line test's largest shift below the
+ *                 width of the board's word(s): (x_in_row - 1) * (rows + 2) — 2 * (rows + 2) for x_in_row = 4 — at
+ *                 most 63 where (rows + 1) * columns <= 64, at most 127 above (so 29 rows with four in a row in one
+ *                 word, 61 in two; 7 x 8 up to x_in_row = 8, 7 x 16 up to 15).  Every x_in_row >= 1 otherwise: a value
+ *                 above max(rows, columns), which the reference accepts and for which it never finds a line, is
+ *                 played as max(rows, columns) + 1 (no line either): no kernel's trip count grows with the value given
+ *   hex           num_cols <= 31 and num_cols * num_rows (+ 1 with swap) <= 384; swap only where num_cols <= num_rows,
+ *                 plain_obs_tensor only on square boards (the reference indexes out of bounds elsewhere); boards with
+ *                 a single row or column are served by the rules, not by the entry points that play out (osg_rollout)
+ *   kuhn_poker, leduc_poker   2 to 10 players (OSG_ERR_INVALID outside, as in the reference)
+ * Each dimension is checked before a product is formed: rows = 2^31 - 1 is refused, not wrapped. */
 int osg_game_describe(const char* game_string, osg_game_desc* out);
 
 /* ---- batches of states --------------------------------------------------- */

@@ -161,7 +161,8 @@ int parse_game(const char* game_string, GameSpec* out) {
     if (rows < 1 || cols < 1 || k < 1) return set_error(OSG_ERR_INVALID, "connect_four: bad dimensions");
     // two u64 planes while (rows + 1) * columns <= 64, four (two words per colour) up to 128 bits — 8 x 8 ... 10 x 10,
     // 7 x 15 ...; the reference has no upper bound (connect_four.cc:50-54): larger boards stay unsupported here
-    if ((rows + 1) * cols > 128 || cols > 32)
+    // (each dimension is bounded before the product is formed: rows = 2^31 - 1 must not overflow it)
+    if (rows > 127 || cols > 32 || (rows + 1) * cols > 128)
       return set_error(OSG_ERR_UNSUPPORTED, "connect_four: (rows+1)*columns must fit a 128-bit board (and columns <= 32)");
     const bool wide = (rows + 1) * cols > 64;
     d.game_kind = kC4;
@@ -170,7 +171,25 @@ int parse_game(const char* game_string, GameSpec* out) {
     d.obs_size = 3 * rows * cols; d.obs_rank = 3; d.obs_shape[0] = 3; d.obs_shape[1] = rows; d.obs_shape[2] = cols;
     d.state_words = wide ? 4 : 2; d.state_word_bytes = 8;
     C4::Params& p = out->c4;
-    p.words = wide ? 4 : 2; p.rows = rows; p.cols = cols; p.k = k; p.ego = ego;
+    // x_in_row has no upper bound in the reference (connect_four.cc:50-54), which then never finds a line: no line is
+    // longer than max(rows, columns).  Every such game is served as x_in_row = max(rows, columns) + 1, for which
+    // C4T::line finds no line either (a run is cut by a column's sentinel after `rows` cells or leaves the board after
+    // `columns`), so no kernel's trip count depends on an unbounded parameter: k <= 128 on every device batch (the
+    // description and the canonical string keep the value given).
+    const int longest = rows > cols ? rows : cols;
+    const int k_dev = k > longest ? longest + 1 : k;
+    // C4T::line relies on bits shifting OUT of the board's word: its largest shift, (k - 1) * (rows + 2) along the
+    // rising diagonal (2 * (rows + 2) in the two-step form of x_in_row = 4), has to stay below the word's width — at
+    // the width the hardware takes the amount modulo it and the term comes back as the board itself (two columns of 31
+    // rows: 66; 7 x 8 with x_in_row = 9: 72).  The tall boards and the boards that fill their word with a long
+    // x_in_row have no device layout: a guard in the line test's loop cost the other run-time boards 4 to 16 %.
+    const int width = wide ? 128 : 64, reach = (k_dev == 4 ? 2 : k_dev - 1) * (rows + 2);
+    if (reach > width - 1)
+      return set_error(OSG_ERR_UNSUPPORTED, "connect_four: the line test of this board shifts by " + std::to_string(reach) +
+                       " bits ((x_in_row - 1) * (rows + 2); 2 * (rows + 2) for x_in_row = 4), the limit is " +
+                       std::to_string(width - 1) + " for a " + std::to_string(width) + "-bit board: boards this tall, or "
+                       "with an x_in_row this long for their rows, have no device layout");
+    p.words = wide ? 4 : 2; p.rows = rows; p.cols = cols; p.k = k_dev; p.ego = ego;
     out->c4_std = (rows == 6 && cols == 7 && k == 4);
     out->c4_wide = wide;
     osg_u128 board = 0, top = 0;
@@ -189,10 +208,12 @@ int parse_game(const char* game_string, GameSpec* out) {
     if (!rd.finish()) return set_error(OSG_ERR_INVALID, rd.err);
     if (rep != "standard" && rep != "explicit") return set_error(OSG_ERR_INVALID, "Invalid string_rep " + rep);
     if (cols < 1 || rows < 1) return set_error(OSG_ERR_INVALID, "hex: bad dimensions");
-    int cells = cols * rows;
     // the planes hold up to 384 cells (19 x 19 = 361, with the swap action 362 ids); a row shift must stay below a
     // word (cols <= 31).  The reference has no upper bound (hex.cc:47-56): larger boards stay unsupported here.
-    if (cells + (swap ? 1 : 0) > 32 * 12 || cols > 31)
+    // (each dimension is bounded before the product is formed, so that it cannot overflow)
+    const bool too_big = cols > 31 || rows > 32 * 12 || cols * rows + (swap ? 1 : 0) > 32 * 12;
+    int cells = too_big ? 0 : cols * rows;
+    if (too_big)
       return set_error(OSG_ERR_UNSUPPORTED, "hex: boards above 384 cells (or wider than 31 columns) have no device layout");
     if (swap && cols > rows)
       return set_error(OSG_ERR_UNSUPPORTED, "hex: swap on a board with more columns than rows writes past the board in the "

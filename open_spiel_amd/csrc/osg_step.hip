@@ -348,7 +348,9 @@ int osg_step(const osg_batch* src, osg_batch* dst, const uint8_t* d_actions, voi
   }
   const bool aligned2 = ((reinterpret_cast<uintptr_t>(d_actions) | reinterpret_cast<uintptr_t>(d_mask) |
                           reinterpret_cast<uintptr_t>(d_status)) & 1u) == 0;
-  if (planes16 && src->spec.desc.game_kind == kC4 && !src->spec.c4_wide && (n & 1) == 0 && aligned2) {
+  // (k_step_c4x2 writes ONE mask byte per state: boards of up to 8 columns.  A 64-bit board can have up to 32 — 2 x 19,
+  // 1 x 32: a two- or four-byte mask —, which the generic kernel below writes in the format the description names)
+  if (planes16 && src->spec.desc.game_kind == kC4 && !src->spec.c4_wide && (n & 1) == 0 && aligned2 && cmb == 1) {
     const int64_t pairs = n / 2;
     k_step_c4x2<C4><<<dim3(static_cast<unsigned>((pairs + kC4StepBlock - 1) / kC4StepBlock)), dim3(kC4StepBlock), 0, ctx->stream>>>(
         src->spec.c4, static_cast<const uint64_t*>(src->words()), static_cast<uint64_t*>(dst->words()), n, d_actions,

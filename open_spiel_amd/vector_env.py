@@ -26,7 +26,7 @@ import enum
 import torch
 
 from . import _abi
-from ._abi import check, lib
+from ._abi import OsgError, check, lib
 from .engine import StateBatch
 
 
@@ -89,6 +89,7 @@ class BatchedEnvironment:
         if self._compact:
             self._flags = torch.full((n,), 2, dtype=torch.uint8, device=dev)      # LAST: every environment starts an episode
             self._rewards_x2 = torch.empty((n, P), dtype=torch.int8, device=dev)
+        self._bad_ids = None   # compact form, 255 actions: the out-of-range ids of the step in flight (see _launch)
 
     def __len__(self):
         return self.num_envs
@@ -106,7 +107,18 @@ class BatchedEnvironment:
     # -- stepping -----------------------------------------------------------------------------
     def _launch(self, actions):
         if self._compact:
-            a8 = torch.where(actions < 0, torch.full_like(actions, 255), actions).to(torch.uint8)
+            # one byte per action: -1 (leave) travels as 0xFF.  Narrowing alone would wrap 256 + a onto the legal id a
+            # and read an explicit 255 as "leave", so every id outside [-1, A) is replaced BEFORE narrowing by the byte
+            # A, which no position has as a legal action: the kernel refuses and counts it like the non-compact form
+            # does (that environment unchanged, OsgError at the synchronisation of step()).  No extra synchronisation.
+            # With A = 255 every byte but 0xFF names an action: there the bad ids travel as "leave" and step() raises
+            # for them after its synchronisation (an environment that starts a new episode ignores its action, as in
+            # the kernel).
+            A = self.batch.desc.num_distinct_actions
+            bad = (actions < -1) | (actions >= A)
+            self._bad_ids = bad & ((self._flags & 3) != 2) if A == 255 else None
+            leave = (actions == -1) | bad if A == 255 else actions == -1
+            a8 = torch.where(leave, torch.full_like(actions, 255), torch.where(bad, torch.full_like(actions, A), actions)).to(torch.uint8)
             check(lib().osg_env_step_compact(self.batch._h, a8.data_ptr(), self._flags.data_ptr(), self._seed, self._index_offset,
                                              self._t, self._rewards_x2.data_ptr(), self._mask.data_ptr()))
             # the reference's TimeStep types, formed from the compact arrays (what get_time_step hands out)
@@ -156,6 +168,8 @@ class BatchedEnvironment:
             raise ValueError(f"Invalid number of actions. Expected {self.num_envs}, got {a.numel()}")
         self._launch(a)
         self.ctx.synchronize()  # surfaces illegal actions (IllegalActionError in the reference)
+        if self._bad_ids is not None and bool(self._bad_ids.any()):
+            raise OsgError(f"osg error -4: {int(self._bad_ids.sum())} illegal action(s) in osg_env_step_compact")
         ts = self.get_time_step()
         if not reset_if_done:
             return ts

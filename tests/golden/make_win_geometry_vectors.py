@@ -8,8 +8,10 @@ build container (needs the reference sources):
 
     python tests/golden/make_win_geometry_vectors.py
 
-Output: tests/golden/win_geometry_vectors.npz (fixed seeds, fixed zip timestamps: byte for byte reproducible).
-Per set <set> (SETS below: five connect_four geometries, five hex boards):
+Output: tests/golden/win_geometry_vectors.npz (fixed seeds, fixed zip timestamps: byte for byte reproducible) and
+tests/golden/win_geometry_edge_vectors.npz (`--edge` writes only this one): the connect_four geometries at the edges of
+what the device's bitboards hold (C4_EDGE_SETS), same arrays, searched with their own seeds so that the first file
+keeps its bytes.  Per set <set> (SETS below: five connect_four geometries, five hex boards; seven edge geometries):
 
   <set>/game        the game string (bytes)
   <set>/histories   [n, L] action histories from the initial state, padded with -1 (int8 connect_four, int16 hex)
@@ -53,6 +55,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 OUT = os.path.join(ROOT, "tests", "golden", "win_geometry_vectors.npz")
+OUT_EDGE = os.path.join(ROOT, "tests", "golden", "win_geometry_edge_vectors.npz")
 
 KIND_LINE, KIND_DRAW, KIND_LAST_CELL, KIND_NEAR_MISS, KIND_CHAIN_NEAR_FIRST, KIND_CHAIN_FAR_FIRST = range(6)
 DIRS = ((1, 0), (0, 1), (1, 1), (-1, 1))   # (d_row, d_col): vertical, horizontal, rising, falling
@@ -64,6 +67,21 @@ C4_SETS = {
     "c4_8x8": dict(game="connect_four(rows=8,columns=8)", R=8, C=8, K=4, last_tries=1000),
     "c4_9x10x5": dict(game="connect_four(rows=9,columns=10,x_in_row=5)", R=9, C=10, K=5, last_tries=150),
     "c4_7x15": dict(game="connect_four(rows=7,columns=15)", R=7, C=15, K=4, last_tries=100),
+}
+# The edges of the accepted geometries (H = rows + 1 bits per column; one 64-bit word per colour up to 64 bits, two up
+# to 128): boards so tall that a shift of the line test reaches the word width, boards that fill their words exactly
+# with x_in_row = columns (only whole rows are lines) and columns + 1 (no line exists: zero cases of kinds 0 and 2),
+# and x_in_row = 1 (the first stone wins: one line case per column, nothing else).  Kinds that cannot exist on a board
+# are recorded with zero cases (tests/test_win_geometry_goldens.py asserts which).  `tries` thins the searches: the long
+# histories of these boards cost more per attempt; a line or near miss not found within them is left out.
+C4_EDGE_SETS = {
+    "c4e_31x2": dict(game="connect_four(rows=31,columns=2)", R=31, C=2, K=4, last_tries=300, tries=3000),
+    "c4e_63x2": dict(game="connect_four(rows=63,columns=2)", R=63, C=2, K=4, last_tries=300, tries=3000),
+    "c4e_7x8x8": dict(game="connect_four(rows=7,columns=8,x_in_row=8)", R=7, C=8, K=8, last_tries=300, tries=3000),
+    "c4e_7x8x9": dict(game="connect_four(rows=7,columns=8,x_in_row=9)", R=7, C=8, K=9, last_tries=10, tries=3000),
+    "c4e_7x16x16": dict(game="connect_four(rows=7,columns=16,x_in_row=16)", R=7, C=16, K=16, last_tries=300, tries=3000),
+    "c4e_7x16x17": dict(game="connect_four(rows=7,columns=16,x_in_row=17)", R=7, C=16, K=17, last_tries=10, tries=3000),
+    "c4e_4x5x1": dict(game="connect_four(rows=4,columns=5,x_in_row=1)", R=4, C=5, K=1, last_tries=10, tries=50),
 }
 HEX_SETS = {
     "hex_19": dict(game="hex(board_size=19)", R=19, C=19, deep=True),
@@ -82,7 +100,7 @@ LINE_TRIES, NEAR_TRIES, DRAW_TRIES, DRAWS_KEPT = 3000, 3000, 60000, 4
 def all_lines(R, C, K):
     """Every placement of K cells in a row: (direction, ((row, col), ...)) in a fixed order."""
     out = []
-    for d, (dr, dc) in enumerate(DIRS):
+    for d, (dr, dc) in enumerate(DIRS[:1] if K == 1 else DIRS):     # (one cell is the same placement in every direction)
         for r in range(R):
             for c in range(C):
                 r1, c1 = r + (K - 1) * dr, c + (K - 1) * dc
@@ -158,7 +176,7 @@ def guided(geom, rng, mode, targets=(), winner=-1, hold=None):
                 closes = mover == winner and missing == {cell} and (mode == "line" or (mode == "last" and left == 1))
                 if not closes:
                     continue
-                if mode == "line" and sum(max(0, n - K + 1) for n in runs) != 1:
+                if mode == "line" and K > 1 and sum(max(0, n - K + 1) for n in runs) != 1:
                     continue          # would complete a second placement as well
                 b.play(c)
                 return b.history
@@ -193,16 +211,21 @@ def search(geom, seed, tries, mode, **kw):
     return None, tries
 
 
-def c4_cases(name):
-    """[(kind, history, winner, direction, cells)] of one geometry, in a fixed order."""
-    geom = C4_SETS[name]
+def c4_cases(name, sets=None, first_base=0):
+    """[(kind, history, winner, direction, cells)] of one geometry, in a fixed order.  The edge sets (`tries` given) keep
+    what their thinned searches find; the others must find every line and DRAWS_KEPT draws."""
+    sets = C4_SETS if sets is None else sets
+    geom = sets[name]
     R, C, K = geom["R"], geom["C"], geom["K"]
-    base = sorted(C4_SETS).index(name) * 1_000_000
+    edge = "tries" in geom
+    base = (first_base + sorted(sets).index(name)) * 1_000_000
     cases, worst = [], 0
     lines = all_lines(R, C, K)
     for li, (d, cells) in enumerate(lines):
         for colour in (0, 1):
-            h, t = search(geom, base + 10 * li + colour, LINE_TRIES, "line", targets=cells, winner=colour)
+            h, t = search(geom, base + 10 * li + colour, geom.get("tries", LINE_TRIES), "line", targets=cells, winner=colour)
+            if h is None and edge:
+                continue
             assert h is not None, f"{name}: no history for line {cells} colour {colour}"
             worst = max(worst, t)
             cases.append((KIND_LINE, h, colour, d, cells))
@@ -211,6 +234,8 @@ def c4_cases(name):
     rng = random.Random(rng_seed)
     while found < DRAWS_KEPT:
         tries_used += 1
+        if edge and tries_used > geom["tries"]:
+            break
         assert tries_used <= DRAW_TRIES, f"{name}: {found} draws in {DRAW_TRIES} tries"
         h = guided(geom, rng, "draw")
         if h is not None:
@@ -229,9 +254,11 @@ def c4_cases(name):
     n_near = 0
     for c in range(C - 1):
         for j in range(1, K):
+            if j > R or K - j > R:
+                continue              # (x_in_row above the rows: the split does not fit the two columns)
             cells = tuple((R - j + i, c) for i in range(j)) + tuple((i, c + 1) for i in range(K - j))
             for colour in (0, 1):
-                h, _ = search(geom, base + 700_000 + 100 * c + 10 * j + colour, NEAR_TRIES, "near", targets=cells, winner=colour)
+                h, _ = search(geom, base + 700_000 + 100 * c + 10 * j + colour, geom.get("tries", NEAR_TRIES), "near", targets=cells, winner=colour)
                 if h is not None:
                     cases.append((KIND_NEAR_MISS, h, colour, -1, cells))
                     n_near += 1
@@ -348,10 +375,10 @@ def pack(histories, dtype):
     return out
 
 
-def build_sets(reference_py):
+def build_sets(reference_py, edge=False):
     out = {}
-    for name, spec in C4_SETS.items():
-        cases = c4_cases(name)
+    for name, spec in (C4_EDGE_SETS if edge else C4_SETS).items():
+        cases = c4_cases(name, C4_EDGE_SETS, 100) if edge else c4_cases(name)
         game = reference_py.Game(spec["game"])
         res = [reference_results(game, c[1]) for c in cases]
         for (kind, _, winner, _, _), (end, rets) in zip(cases, res):   # the search's claims, checked on the reference
@@ -366,7 +393,7 @@ def build_sets(reference_py):
                          end_ply=np.array([r[0] for r in res], np.int16), returns=np.array([r[1] for r in res], np.int8),
                          kind=np.array([c[0] for c in cases], np.int8), winner=np.array([c[2] for c in cases], np.int8),
                          direction=np.array([c[3] for c in cases], np.int8), cells=cells)
-    for name, spec in HEX_SETS.items():
+    for name, spec in ({} if edge else HEX_SETS).items():
         cases = hex_cases(name)
         game = reference_py.Game(spec["game"])
         res = [reference_results(game, c[1]) for c in cases]
@@ -397,11 +424,12 @@ def main():
     if not reference_py.sources_present():
         raise RuntimeError("needs the reference sources")
     reference_py.build()
-    t0 = time.time()
-    sets = build_sets(reference_py)
-    write_npz(OUT, {f"{name}/{k}": v for name, s in sets.items() for k, v in s.items()})
-    n = sum(len(s["kind"]) for s in sets.values())
-    print(OUT, os.path.getsize(OUT), "bytes,", n, "histories,", f"{time.time() - t0:.0f} s")
+    for path, edge in ((OUT_EDGE, True),) if "--edge" in sys.argv[1:] else ((OUT, False), (OUT_EDGE, True)):
+        t0 = time.time()
+        sets = build_sets(reference_py, edge)
+        write_npz(path, {f"{name}/{k}": v for name, s in sets.items() for k, v in s.items()})
+        n = sum(len(s["kind"]) for s in sets.values())
+        print(path, os.path.getsize(path), "bytes,", n, "histories,", f"{time.time() - t0:.0f} s")
 
 
 if __name__ == "__main__":

@@ -69,7 +69,13 @@ def test_game_descriptions_match_the_oracle(built, oracle, game, A, C_, P, obs, 
 
 def test_bad_game_strings_are_rejected(built):
     for bad in ["chess", "connect_four(rows=12,columns=12)", "hex(board_size=20)", "connect_four(foo=1)",
-                "hex(swap=3)", "kuhn_poker(players=1)", "leduc_poker(players=11)", "hex(board_size=3"]:
+                "hex(swap=3)", "kuhn_poker(players=1)", "leduc_poker(players=11)", "hex(board_size=3",
+                "connect_four(rows=2147483647,columns=1)", "connect_four(rows=65535,columns=65537)", "hex(board_size=65536)",
+                "hex(num_cols=2,num_rows=2147483647)",
+                "connect_four(rows=31,columns=2)", "connect_four(rows=30,columns=2)", "connect_four(rows=63,columns=1)",
+                "connect_four(rows=63,columns=2)", "connect_four(rows=62,columns=2)", "connect_four(rows=126,columns=1)",
+                "connect_four(rows=7,columns=8,x_in_row=9)", "connect_four(rows=7,columns=8,x_in_row=15)",
+                "connect_four(rows=7,columns=16,x_in_row=16)", "connect_four(rows=7,columns=16,x_in_row=17)"]:
         with pytest.raises(built.OsgError):
             built.describe(bad)
 

@@ -300,7 +300,15 @@ def test_illegal_and_terminal_actions_are_rejected(ctx):
 def test_bad_game_strings(ctx):
     import open_spiel_amd as osa
     for bad in ["chess", "connect_four(rows=12,columns=12)", "hex(board_size=20)", "hex(num_cols=32,num_rows=3)", "hex(num_cols=5,num_rows=4,swap=True)", "kuhn_poker(players=11)",
-                "leduc_poker(players=11)", "connect_four(foo=1)", "hex(swap=3)"]:
+                "leduc_poker(players=11)", "connect_four(foo=1)", "hex(swap=3)",
+                # dimensions whose product would overflow before it is compared with the limit
+                "connect_four(rows=2147483647,columns=1)", "connect_four(rows=65535,columns=65537)", "hex(board_size=65536)",
+                "hex(num_cols=2,num_rows=2147483647)", "connect_four(rows=128,columns=1)", "hex(num_cols=16,num_rows=24,swap=True)",
+                # the line test's largest shift would reach the width of the board's word(s)
+                "connect_four(rows=31,columns=2)", "connect_four(rows=30,columns=2)", "connect_four(rows=63,columns=1)",
+                "connect_four(rows=63,columns=2)", "connect_four(rows=62,columns=2)", "connect_four(rows=126,columns=1)",
+                "connect_four(rows=7,columns=8,x_in_row=9)", "connect_four(rows=7,columns=8,x_in_row=15)",
+                "connect_four(rows=7,columns=16,x_in_row=16)", "connect_four(rows=7,columns=16,x_in_row=17)"]:
         with pytest.raises(osa.OsgError):
             osa.StateBatch(ctx, bad, 4)
     with pytest.raises(osa.OsgError):

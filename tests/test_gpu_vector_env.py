@@ -149,6 +149,40 @@ def test_illegal_action_is_reported(ctx):
         osa.BatchedEnvironment(ctx, "tic_tac_toe", 4, discount=1.5)
 
 
+@pytest.mark.parametrize("game,legal,other", [("connect_four", 3, 2), ("leduc_poker", 1, 2), ("hex(num_cols=15,num_rows=17)", 3, 2)])
+@pytest.mark.parametrize("bad", [-2, 255, 256, 256 + 3, 65536 + 3])
+def test_compact_form_refuses_action_ids_outside_the_game_like_the_other_form(ctx, bad, game, legal, other):
+    """BatchedEnvironment(compact=True) hands its actions on as bytes: narrowing alone would wrap 256 + 3 and 65536 + 3
+    onto the legal column 3 and read an explicit 255 as "leave the environment as it is".  Every id outside
+    [-1, num_distinct_actions) raises what the non-compact form raises, and both batches stay bit for bit as they were
+    (odd and even batch: the one- and the two-environment kernels).  connect_four (7 actions) and leduc_poker (3, chance
+    sampling) hand the kernel the byte A, which no position has as a legal action; hex 15 x 17 has 255 actions, every
+    byte but 0xFF names one, and the wrapper sends "leave" and raises after the step's synchronisation."""
+    import torch
+    import open_spiel_amd as osa
+    for n in (5, 6):
+        envs = [osa.BatchedEnvironment(ctx, game, n, seed=3, compact=compact) for compact in (False, True)]
+        for env in envs:
+            env.reset()
+            ts = env.step(torch.full((n,), legal, dtype=torch.int32))       # a legal action, and played
+            assert bool((ts.step_type == MID).all())
+        before = [env.batch.raw_words().copy() for env in envs]
+        assert (before[0] == before[1]).all() and before[0].any()
+        for env, words in zip(envs, before):
+            with pytest.raises(osa.OsgError, match="illegal"):
+                env.step(torch.full((n,), bad, dtype=torch.int32))
+            np.testing.assert_array_equal(env.batch.raw_words(), words)
+        # one bad id among good ones: that environment alone stays, in both forms alike
+        mixed = torch.full((n,), other, dtype=torch.int32)
+        mixed[1] = bad
+        for env in envs:
+            with pytest.raises(osa.OsgError, match="illegal"):
+                env.step(mixed)
+        after = [env.batch.raw_words() for env in envs]
+        assert (after[0] == after[1]).all()
+        assert (after[0][:, 1] == before[0][:, 1]).all() and (after[0][:, 0] != before[0][:, 0]).any()
+
+
 @pytest.mark.parametrize("game", ["connect_four", "connect_four(rows=5,columns=6,x_in_row=3)"])
 def test_env_step_two_per_thread_equals_one_per_thread(ctx, game):
     """k_env_step_x2 (two environments per thread, 16-byte accesses; taken for even batches of two-plane two-player games

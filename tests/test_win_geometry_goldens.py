@@ -5,7 +5,12 @@ column-wrap near misses, and hex chains whose flood fill is deeper than 128 step
 What the file claims to cover is RECOMPUTED here from the histories alone, by a few lines of plain Python that share
 nothing with the generator's search (its rules model is not imported for this); then the oracle, and where it is built
 the genuine reference build, replay every history and must give the recorded results at every recorded point.  The
-device is held to the same histories by tests/test_z15_gpu_win_geometry.py."""
+device is held to the same histories by tests/test_z15_gpu_win_geometry.py.
+
+tests/golden/win_geometry_edge_vectors.npz holds the same for seven connect_four geometries at the edges of what the
+device's bitboards hold (boards two columns wide and 31 / 63 rows tall, boards of exactly 64 and 128 bits with x_in_row =
+columns and columns + 1, and x_in_row = 1).  A kind that cannot exist on a board has zero cases there, and which kinds
+those are is worked out here from the geometry, not read from the file."""
 import importlib.util
 import os
 
@@ -18,6 +23,10 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 C4_GEOMETRY = {   # set: rows, columns, x_in_row, number of line placements (connect_four.cc HasLine's four directions)
     "c4_6x7": (6, 7, 4, 69), "c4_5x6x3": (5, 6, 3, 62), "c4_8x8": (8, 8, 4, 130), "c4_9x10x5": (9, 10, 5, 164),
     "c4_7x15": (7, 15, 4, 240)}
+C4_EDGE_GEOMETRY = {   # the second file: 28 / 60 vertical placements per column; whole rows only; none; single cells
+    "c4e_31x2": (31, 2, 4, 56), "c4e_63x2": (63, 2, 4, 120), "c4e_7x8x8": (7, 8, 8, 7), "c4e_7x8x9": (7, 8, 9, 0),
+    "c4e_7x16x16": (7, 16, 16, 7), "c4e_7x16x17": (7, 16, 17, 0), "c4e_4x5x1": (4, 5, 1, 20)}
+C4_ALL = {**C4_GEOMETRY, **C4_EDGE_GEOMETRY}
 HEX_BOARD = {     # set: rows, columns, whether the chain is deeper than the 128 flood steps HexT::apply once stopped at
     "hex_19": (19, 19, True), "hex_18": (18, 18, True), "hex_17x19": (19, 17, True), "hex_16": (16, 16, False),
     "hex_11": (11, 11, False)}
@@ -27,10 +36,14 @@ STEPS = ((1, 0), (0, 1), (1, 1), (-1, 1))   # (d_row, d_col) of direction codes 
 
 @pytest.fixture(scope="module")
 def vectors():
-    path = os.path.join(GOLDEN, "win_geometry_vectors.npz")
-    assert os.path.getsize(path) < 100 * 1024
-    with np.load(path) as z:
-        return {k: z[k] for k in z.files}
+    out = {}
+    for name in ("win_geometry_vectors.npz", "win_geometry_edge_vectors.npz"):
+        path = os.path.join(GOLDEN, name)
+        assert os.path.getsize(path) < 100 * 1024
+        with np.load(path) as z:
+            assert not set(z.files) & set(out)
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 @pytest.fixture(scope="module")
@@ -52,7 +65,7 @@ def placements(R, C, K):
         for r in range(R):
             for c in range(C):
                 if 0 <= r + (K - 1) * dr < R and 0 <= c + (K - 1) * dc < C:
-                    out[frozenset((r + i * dr) * C + c + i * dc for i in range(K))] = d
+                    out.setdefault(frozenset((r + i * dr) * C + c + i * dc for i in range(K)), d)   # (K = 1: one cell, direction 0)
     return out
 
 
@@ -72,10 +85,10 @@ def owned_lines(owner, lines, colour, through=None):
 
 
 def test_the_sets_are_recorded_with_consistent_shapes(vectors):
-    assert {k.split("/")[0] for k in vectors} == set(C4_GEOMETRY) | set(HEX_BOARD)
-    for name in list(C4_GEOMETRY) + list(HEX_BOARD):
+    assert {k.split("/")[0] for k in vectors} == set(C4_ALL) | set(HEX_BOARD)
+    for name in list(C4_ALL) + list(HEX_BOARD):
         s = case_set(vectors, name)
-        is_c4 = name in C4_GEOMETRY
+        is_c4 = name in C4_ALL
         assert set(s) == {"game", "histories", "end_ply", "returns", "kind", "winner"} | ({"direction", "cells"} if is_c4 else {"depth"})
         n = len(s["kind"])
         assert s["histories"].dtype == (np.int8 if is_c4 else np.int16) and s["histories"].shape[0] == n
@@ -89,14 +102,27 @@ def test_the_sets_are_recorded_with_consistent_shapes(vectors):
         assert (s["returns"][won, 0] == 1 - 2 * s["winner"][won]).all() and (s["returns"][:, 1] == -s["returns"][:, 0]).all()
         assert (s["returns"][~won] == 0).all()
         if is_c4:
-            R, C, K, _ = C4_GEOMETRY[name]
+            R, C, K, _ = C4_ALL[name]
             assert s["cells"].shape == (n, K) and s["histories"].shape[1] <= R * C
             assert f"rows={R}" in bytes(s["game"]).decode() or (R, C) == (6, 7)
 
 
-@pytest.mark.parametrize("name", list(C4_GEOMETRY))
+def reachable_line_cases(R, C, K, lines):
+    """The (placement, colour) pairs a game can end on.  x_in_row = 1: the first stone wins, so only the first player
+    and only the bottom row.  A whole bottom row (x_in_row = columns) can only be the first player's, whose first stone
+    lies in it; a whole top row means a full board, an even number of stones, so the second player made the last move.
+    Everything else on these boards is reachable (and found)."""
+    if K == 1:
+        return {(l, 0) for l in lines if min(l) < C}
+    out = {(l, colour) for l in lines for colour in (0, 1)}
+    if K == C:
+        out -= {(frozenset(range(C)), 1), (frozenset(range((R - 1) * C, R * C)), (R * C) & 1)}
+    return out
+
+
+@pytest.mark.parametrize("name", list(C4_ALL))
 def test_connect_four_coverage_recomputed_from_the_histories(vectors, name):
-    R, C, K, n_lines = C4_GEOMETRY[name]
+    R, C, K, n_lines = C4_ALL[name]
     s = case_set(vectors, name)
     lines = placements(R, C, K)
     assert len(lines) == n_lines
@@ -134,14 +160,21 @@ def test_connect_four_coverage_recomputed_from_the_histories(vectors, name):
             near.add((cols[0], j, winner))
     print(f"{name}: {len(covered)} (line, colour) pairs of {2 * n_lines}, {draws} draws, {last_cell} wins on the last cell, "
           f"{len(near)} near misses of {(C - 1) * (K - 1) * 2}")
-    assert covered == {(l, colour) for l in lines for colour in (0, 1)}
-    assert draws >= 4
+    assert covered == reachable_line_cases(R, C, K, lines)
+    # kinds that cannot exist have zero cases: no draw where the first stone wins; no win on the last cell without a
+    # line to complete there (none exists, or the game ended long before); a near miss needs a split of x_in_row that
+    # fits two columns (j and x_in_row - j cells, neither above the rows)
+    assert draws >= 4 if K > 1 else draws == 0
     if name in ("c4_6x7", "c4_8x8"):
         assert last_cell >= 8
-    for c in range(C - 1):
-        for colour in (0, 1):
-            assert any((c, j, colour) in near for j in range(1, K)), (name, c, colour)
-    assert len(near) == (C - 1) * (K - 1) * 2      # (the file in fact has every split)
+    if name in C4_EDGE_GEOMETRY:
+        assert last_cell >= 1 if (lines and K > 1) else last_cell == 0
+    splits = [j for j in range(1, K) if j <= R and K - j <= R]
+    assert near == {(c, j, colour) for c in range(C - 1) for j in splits for colour in (0, 1)}   # every split
+    if name in C4_GEOMETRY:
+        assert len(near) == (C - 1) * (K - 1) * 2
+    if K > 2 * R or K == 1:
+        assert not near                  # (7 x 16 with 16 / 17 in a row: no split fits two columns of 7)
 
 
 def hex_adjacent(cell, R, C):
@@ -204,12 +237,12 @@ def replay_and_compare(binding, vectors, name):
         assert state.returns() == [float(x) for x in s["returns"][i]], (name, i)
 
 
-@pytest.mark.parametrize("name", list(C4_GEOMETRY) + list(HEX_BOARD))
+@pytest.mark.parametrize("name", list(C4_ALL) + list(HEX_BOARD))
 def test_the_oracle_replays_every_history_to_the_recorded_results(oracle, vectors, name):
     replay_and_compare(oracle, vectors, name)
 
 
-@pytest.mark.parametrize("name", list(C4_GEOMETRY) + list(HEX_BOARD))
+@pytest.mark.parametrize("name", list(C4_ALL) + list(HEX_BOARD))
 def test_the_reference_build_replays_every_history_to_the_recorded_results(reference, vectors, name):
     replay_and_compare(reference, vectors, name)
 
@@ -234,3 +267,17 @@ def test_the_generator_reproduces_a_sample_of_the_file(gen, vectors):
         for i, (kind, h, winner, depth) in enumerate(gen.hex_cases(name)):
             assert h == [int(a) for a in s["histories"][i] if a >= 0]
             assert (kind, winner, depth) == (int(s["kind"][i]), int(s["winner"][i]), int(s["depth"][i]))
+
+
+@pytest.mark.parametrize("name", ["c4e_7x8x8", "c4e_7x8x9", "c4e_4x5x1", "c4e_31x2"])
+def test_the_generator_reproduces_edge_sets(gen, vectors, name):
+    """Whole edge sets searched for again (their own seeds: the first file's do not move when a set is added here)."""
+    assert set(gen.C4_EDGE_SETS) == set(C4_EDGE_GEOMETRY)
+    s = case_set(vectors, name)
+    geom = gen.C4_EDGE_SETS[name]
+    assert bytes(s["game"]).decode() == geom["game"] and (geom["R"], geom["C"], geom["K"]) == C4_EDGE_GEOMETRY[name][:3]
+    cases = gen.c4_cases(name, gen.C4_EDGE_SETS, 100)
+    assert len(cases) == len(s["kind"])
+    for i, (kind, h, winner, direction, _) in enumerate(cases):
+        assert h == [int(a) for a in s["histories"][i] if a >= 0], (name, i)
+        assert (kind, winner, direction) == (int(s["kind"][i]), int(s["winner"][i]), int(s["direction"][i]))

@@ -12,7 +12,13 @@ as one batch.  HexT::apply stopped its flood after 128 steps until this file was
 large hex boards failed test_ply_by_ply (the label planes of the observation tensor differ one ply before the last
 stone, which is then not seen as a win) and 18 x 18 and 17 x 19 failed test_hex_playouts_from_the_chain_position (games
 that run two to four plies past the oracle's); the controls and every connect_four case passed
-(profiles/r10a_hex_flood_bound.txt)."""
+(profiles/r10a_hex_flood_bound.txt).
+
+C4_EDGE_SETS are the sets of tests/golden/win_geometry_edge_vectors.npz that the device serves: 7 x 8 (exactly 64
+bits) with x_in_row = columns, where only whole rows are lines and the line test's largest shift is 63, the last
+amount below the word's width, and x_in_row = 1.  The file's other sets (two columns of 31 and of 63 rows, x_in_row =
+columns + 1, 7 x 16 with 16 in a row) are boards whose shifts reach the width: the parser refuses them
+(tests/test_edge_games_cpu.py), and tests/test_win_geometry_goldens.py holds the oracle to them."""
 import os
 
 import numpy as np
@@ -22,6 +28,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C4_SETS = ["c4_6x7", "c4_5x6x3", "c4_8x8", "c4_9x10x5", "c4_7x15"]
+C4_EDGE_SETS = ["c4e_7x8x8", "c4e_4x5x1"]
 HEX_SETS = ["hex_19", "hex_18", "hex_17x19", "hex_16", "hex_11"]
 LINE, DRAW, LAST_CELL, NEAR_MISS = 0, 1, 2, 3
 
@@ -34,8 +41,11 @@ def ctx():
 
 @pytest.fixture(scope="module")
 def vectors():
-    with np.load(os.path.join(ROOT, "tests", "golden", "win_geometry_vectors.npz")) as z:
-        return {k: z[k] for k in z.files}
+    out = {}
+    for name in ("win_geometry_vectors.npz", "win_geometry_edge_vectors.npz"):
+        with np.load(os.path.join(ROOT, "tests", "golden", name)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 _RECORDS = {}
@@ -88,7 +98,7 @@ def oracle_record(oracle, vectors, name):
     return rec
 
 
-@pytest.mark.parametrize("name", C4_SETS + HEX_SETS)
+@pytest.mark.parametrize("name", C4_SETS + HEX_SETS + C4_EDGE_SETS)
 def test_ply_by_ply(oracle, ctx, vectors, name):
     """apply_actions / status() / legal_actions_mask_bits() against the oracle at EVERY ply of every history; hex also
     observation_tensor(0) from the winner's first edge stone on (its label planes show a short flood one ply before
@@ -117,7 +127,7 @@ def test_ply_by_ply(oracle, ctx, vectors, name):
 
 @pytest.mark.parametrize("in_place", [False, True])
 @pytest.mark.parametrize("extra", [0, 1, 2])
-@pytest.mark.parametrize("name", C4_SETS + ["hex_11"])
+@pytest.mark.parametrize("name", C4_SETS + ["hex_11"] + C4_EDGE_SETS)
 def test_fused_step(oracle, ctx, vectors, name, extra, in_place):
     """The same histories through step(dst=...) and step() in place.  The set is padded (by repeating histories) to a
     multiple of four plus `extra`: the four-, one- and two-state kernels of the non-standard boards and hex, and
@@ -178,7 +188,7 @@ def one_ply_alpha_beta(state, mover):
     return value, best, nodes
 
 
-@pytest.mark.parametrize("name", C4_SETS)
+@pytest.mark.parametrize("name", C4_SETS + C4_EDGE_SETS)
 def test_alpha_beta_one_ply_deep_finds_every_line(oracle, ctx, vectors, name):
     """From each line history minus its last move, alpha_beta_search(depth_limit=1, leaf_value=0.0): the value is 1.0
     for the mover, best_action the lowest legal action whose child the oracle calls a win, nodes 1 plus the children
