@@ -668,6 +668,43 @@ int osg_mmd_gap(osg_cfr* s, double* out);
  * :376-382) of the selected replica as an [I, Amax] host array, cell (I, a) the sequence value, padding 0. */
 int osg_mmd_sequences(osg_cfr* s, int which, double* h_x);
 
+/* Extensive-form regret minimization: EFRSolver (open_spiel/python/algorithms/efr.py; Morrill et al. 2021, arXiv 2102.06973)
+ * on a CFRSolverBase object (solver 0, no discounting, one replica) of kuhn_poker or leduc_poker with any served number of
+ * players.  The current policy lives in the current-policy table and the reach-weighted cumulative policy in the
+ * cumulative-policy table, so osg_cfr_tables, osg_cfr_evaluate_policy and osg_cfr_action_values read them as they read
+ * CFR's; the regret table is not touched: EFR's regrets are per (information state, deviation).  One iteration updates
+ * all players at once, with no alternation and no linear averaging (efr.py:424-433).  csrc/osg_efr.h has the arithmetic,
+ * the reference's behaviour it restates and its fixed orders of summation; no floating-point atomics, two runs and both
+ * kernel forms give the same bits.
+ *
+ * osg_efr_set_deviations: builds the deviation tables of set `type` on the host from the solver's tree and starts from the
+ * uniform policy with R = 0, counter 0.  type: 0 blind action, 1 informed action, 2 blind cf, 3 informed cf, 4 bps,
+ * 5 cfps, 6 csps, 7 tips, 8 bhv (efr.py:465-488).  form: 0 by tree size (<= 4096 histories: resident), 1 "k_efr_resident"
+ * — ONE launch of one workgroup runs all iterations of a call —, 2 "k_efr" — a launch per phase, tree level and
+ * own-decision depth.  OSG_ERR_INVALID for an MCCFR, discounting or mirror-descent solver, an unknown type or form;
+ * OSG_ERR_UNSUPPORTED for replicas > 1, a policy row wider than 4 actions, more than 8 earlier own decisions on a path,
+ * more than 2^26 deviations.  Afterwards osg_cfr_iterate answers OSG_ERR_INVALID and osg_cfr_reset returns to the start. */
+int osg_efr_set_deviations(osg_cfr* s, int type, int form);
+/* evaluate_and_update_policy() x iters (efr.py:424-433).  OSG_ERR_INVALID before osg_efr_set_deviations. */
+int osg_efr_iterate(osg_cfr* s, int iters);
+/* out[5]: deviations in total, the most of one information state, L (the most earlier own decisions on a path, at least
+ * 1), the doubles of the regret state (osg_efr_regrets), own-decision depths. */
+int osg_efr_sizes(const osg_cfr* s, int64_t* out);
+/* The tables, for tests; any pointer may be NULL.  dev_off [I + 1]: the deviations of information state i are
+ * dev_off[i] .. dev_off[i + 1], in the reference's order.  Per deviation: target and source (-1: external) as indices among
+ * the row's legal actions; weights_none (1: the reference's `None` weight vector); weights [D, L] (0 / 1, -1 padding and
+ * with weights_none) and memory [D, L] (remembered action ids, -1 padding) as the reference states them; y_slot (the index
+ * of its swap among the information state's distinct swaps, in order of first appearance); cells [D, L]: for every
+ * remembered decision the cell (earlier information state * Amax + column) of the current-policy table whose product is
+ * memreach, -2 where the reference reads a probability that is always 0, -1 where nothing is remembered. */
+int osg_efr_deviations(const osg_cfr* s, int32_t* dev_off, int8_t* target, int8_t* source, int8_t* weights_none, int8_t* weights,
+                       int8_t* memory, int32_t* y_slot, int32_t* cells);
+/* The regret state as osg_efr_sizes out[3] doubles: R per deviation, then the y values [I, 16] an information state
+ * carries into the next policy pass when the regret pass reaches none of its histories (efr.py:338,351).  A checkpoint is
+ * this, the cumulative and current policy tables (osg_cfr_upload_tables) and the counter (osg_cfr_set_iteration). */
+int osg_efr_regrets(osg_cfr* s, double* h_state);
+int osg_efr_upload_regrets(osg_cfr* s, const double* h_state);
+
 /* ExternalSamplingMCCFRSolver::RunIteration (external_sampling_mccfr.cc:71-186,
  * AverageType::kSimple) for `trajectories` traverser passes (player = global
  * trajectory index mod P), mini-batched: every trajectory of one call reads the

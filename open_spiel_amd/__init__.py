@@ -5,7 +5,7 @@ path: batched LegalActions / ApplyAction / IsTerminal / Returns /
 ObservationTensor for tic_tac_toe, connect_four, hex, kuhn_poker and
 leduc_poker, random-rollout evaluation, MCTS, information-set MCTS and alpha-beta search over batches of roots, and
 tabular CFR / Discounted CFR / external-sampling MCCFR / extensive-form fictitious play /
-magnetic mirror descent, payoff tensors / policy aggregation / PSRO over populations of policies, and PSRO's
+magnetic mirror descent / extensive-form regret minimization, payoff tensors / policy aggregation / PSRO over populations of policies, and PSRO's
 meta-strategy solvers (projected replicator dynamics, regret matching) on batches of normal-form meta-games.
 The C-ABI is include/osg_abi.h.
 """
@@ -30,7 +30,7 @@ def __getattr__(name):
         return importlib.import_module(".pyspiel_hip", __name__)
     # torch-backed classes are imported lazily so that `import open_spiel_amd`
     # (and the ABI symbol check) works without touching torch.
-    if name in ("Context", "Game", "StateBatch", "SolvedGame", "TabularSolver", "DCFRSolver", "LCFRSolver", "XFPSolver", "MMDSolver"):
+    if name in ("Context", "Game", "StateBatch", "SolvedGame", "TabularSolver", "DCFRSolver", "LCFRSolver", "XFPSolver", "MMDSolver", "EFRSolver"):
         from . import engine
         return getattr(engine, name)
     if name == "PSROSolver":

@@ -204,6 +204,12 @@ SIGNATURES = {
     "osg_mmd_iterate": (INT, [VP, INT]),
     "osg_mmd_gap": (INT, [VP, VP]),
     "osg_mmd_sequences": (INT, [VP, INT, VP]),
+    "osg_efr_set_deviations": (INT, [VP, INT, INT]),
+    "osg_efr_iterate": (INT, [VP, INT]),
+    "osg_efr_sizes": (INT, [VP, VP]),
+    "osg_efr_deviations": (INT, [VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "osg_efr_regrets": (INT, [VP, VP]),
+    "osg_efr_upload_regrets": (INT, [VP, VP]),
     "osg_mccfr_iterate": (INT, [VP, U64, I64, I64]),
     "osg_cfr_table_ptrs": (INT, [VP, C.POINTER(VP), C.POINTER(VP), C.POINTER(VP)]),
     "osg_mccfr_delta_ptrs": (INT, [VP, C.POINTER(VP), C.POINTER(VP)]),

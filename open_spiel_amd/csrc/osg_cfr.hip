@@ -482,12 +482,14 @@ int osg_cfr_sizes(const osg_cfr* s, int64_t* out) {
 
 int osg_cfr_reset(osg_cfr* s) {
   if (int rc = init_tables(s)) return rc;
+  if (efr_mode(s)) return efr_after_reset(s);
   return mmd_mode(s) ? mmd_after_reset(s) : OSG_OK;   // (mirror descent keeps its parameters and starts from avg_x = x again)
 }
 
 int osg_cfr_iterate(osg_cfr* s, int iters) {
   if (!s || iters < 0) return set_error(OSG_ERR_INVALID, "osg_cfr_iterate: bad argument");
   if (mmd_mode(s)) return set_error(OSG_ERR_INVALID, "osg_cfr_iterate: the solver is in mirror-descent mode (osg_mmd_set_params); a CFR iteration would overwrite its tables");
+  if (efr_mode(s)) return set_error(OSG_ERR_INVALID, "osg_cfr_iterate: the solver runs EFR (osg_efr_set_deviations); a CFR iteration would overwrite its tables");
   if (iters == 0) return OSG_OK;
   if (int rc = cfr_sub_error(s)) return rc;
   Tables tb{s->regrets(), s->cum(), s->cur()};

@@ -11,6 +11,7 @@
 //
 //   osg_cfr_xfp.hip     k_xfp_small, k_xfp_*          extensive-form fictitious play
 //   osg_cfr_mmd.hip     k_mmd_small, k_mmd_*          magnetic mirror descent (MmdState lives there)
+//   osg_cfr_efr.hip     k_efr_resident, k_efr_*       extensive-form regret minimization (osg_efr.h has the arithmetic)
 //
 // Every kernel is launched from the translation unit that defines it; what crosses the units are the device-side
 // argument structs below (views: raw pointers), the per-family plans that own the memory behind them (SplitPlan,
@@ -30,6 +31,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "osg_efr.h"
 #include "osg_internal.h"
 
 using namespace osg;
@@ -454,6 +456,19 @@ struct PopulationPlan {   // payoff-tensor cells and policy aggregation (osg_cfr
   PinnedArray<unsigned int> h_refused; // mapped: the same, kept until the next population call reports it
 };
 
+struct EfrPlan {   // extensive-form regret minimization (osg_cfr_efr.hip): built by osg_efr_set_deviations
+  bool active = false;
+  int form = 0;                  // 0: chosen by tree size, 1: one workgroup runs a whole call, 2: a launch per phase, level and depth
+  EfrTables tables;              // the host's copy (osg_efr_deviations, osg_efr_sizes)
+  DeviceArray<int32_t> dev_off, dev_info, dev_desc, nkeys, own_len, own_info, mown, depth_off, depth_info;
+  DeviceArray<uint32_t> dev_cols;
+  DeviceArray<int8_t> key_desc;
+  DeviceArray<double> state;     // R [Dtot] | y [I, kEfrMaxKeys]: with the policy tables and the counter, the checkpoint
+  DeviceArray<double> work;      // counterfactual reach [M] | own reach [M] | the policy pass's row per member [M, A]
+  DeviceArray<int32_t> flags;    // live [M] | visited [I]
+  size_t state_doubles(int I) const { return tables.dev_info.size() + static_cast<size_t>(I) * kEfrMaxKeys; }
+};
+
 }  // namespace osg_cfr_impl
 
 using namespace osg_cfr_impl;
@@ -527,6 +542,7 @@ struct osg_cfr {
   PopulationPlan population;
   // magnetic mirror descent (osg_cfr_mmd.hip): built at the first osg_mmd_* call
   std::unique_ptr<MmdState> mmd;
+  EfrPlan efr;
 
   Tree tree() const {
     Tree t;
@@ -630,4 +646,7 @@ int build_resident_tree(osg_cfr* s);
 // ---- osg_cfr_mmd.hip ----
 bool mmd_mode(const osg_cfr* s);       // osg_mmd_set_params was accepted: pi and avg_x live in the cur and cum tables
 int mmd_after_reset(osg_cfr* s);       // avg_x = x of the fresh uniform policy
+// ---- osg_cfr_efr.hip ----
+bool efr_mode(const osg_cfr* s);       // osg_efr_set_deviations was accepted
+int efr_after_reset(osg_cfr* s);       // R and y back to 0
 }  // namespace osg_cfr_impl

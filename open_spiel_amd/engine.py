@@ -1126,3 +1126,95 @@ class MMDSolver(TabularSolver):
 
     def exploitability(self):
         return self.evaluate_policy("current")["exploitability"]
+
+
+class EFRSolver(TabularSolver):
+    """efr.EFRSolver(game, deviations_name) on the device: extensive-form regret minimization (Morrill et al. 2021).  The
+    deviation set decides which hindsight-rationality class the empirical play approaches; `blind cf` is CFR with
+    simultaneous updates.  The current policy lives in the current-policy table and the reach-weighted cumulative policy
+    in the cumulative-policy table, so tables(), evaluate_policy(), nash_conv() and action_values() are the inherited
+    ones; the regrets are per (information state, deviation) (osg_efr_set_deviations in include/osg_abi.h; csrc/osg_efr.h
+    has the arithmetic).  kuhn_poker and leduc_poker with any served number of players, one replica.
+    form: None (by tree size), "resident" (one launch of one workgroup per call) or "levels" (a launch per phase)."""
+
+    DEVIATION_SETS = {
+        "blind action": 0, "informed action": 1, "blind cf": 2, "blind counterfactual": 2, "informed cf": 3,
+        "informed counterfactual": 3, "bps": 4, "blind partial sequence": 4, "cfps": 5, "cf partial sequence": 5,
+        "counterfactual partial sequence": 5, "csps": 6, "casual partial sequence": 6, "tips": 7,
+        "twice informed partial sequence": 7, "bhv": 8, "single target behavioural": 8, "behavioural": 8}
+
+    def __init__(self, ctx, game_string, deviations_name, form=None, replicas=1):
+        self._h = None
+        self._check_arguments(deviations_name, form)
+        super().__init__(ctx, game_string, alternating_updates=False, linear_averaging=False, regret_matching_plus=False,
+                         replicas=replicas)
+        self.set_deviations(deviations_name, form)
+
+    @classmethod
+    def _check_arguments(cls, deviations_name, form):
+        if deviations_name not in cls.DEVIATION_SETS:   # efr.py:490-494, the message as the reference words it
+            raise ValueError("Unsupported Deviation Set Passed              As Constructor Argument")
+        if form not in (None, "resident", "levels"):
+            raise OsgError(f"EFRSolver: form must be None, 'resident' or 'levels', not {form!r}")
+
+    def set_deviations(self, deviations_name, form=None):
+        """Builds the tables of another deviation set (or kernel form) on the same tree and starts over: uniform policy,
+        R = 0, counter 0 (osg_efr_set_deviations)."""
+        self._check_arguments(deviations_name, form)
+        check(lib().osg_efr_set_deviations(self._h, self.DEVIATION_SETS[deviations_name], {None: 0, "resident": 1, "levels": 2}[form]))
+        self.deviations_name = deviations_name
+        self.external_only = self.DEVIATION_SETS[deviations_name] in (0, 2, 4)
+        sizes = (C.c_int64 * 5)()
+        check(lib().osg_efr_sizes(self._h, sizes))
+        self.num_deviations, self.max_deviations, self.memory, self._state_doubles, self.depths = [int(v) for v in sizes]
+
+    def evaluate_and_update_policy(self, iters=1):
+        """_EFRSolver.evaluate_and_update_policy() (efr.py:424-433), `iters` times."""
+        check(lib().osg_efr_iterate(self._h, int(iters)))
+
+    def evaluate_and_update_policy_cfr_br(self, iters=1):
+        raise OsgError("EFRSolver: evaluate_and_update_policy() advances EFR; a CFR-BR iteration would overwrite its tables")
+
+    def deviation_counts(self):
+        """dict(total=, max_per_infostate=, memory=): deviations of the set on this game, and L."""
+        return dict(total=self.num_deviations, max_per_infostate=self.max_deviations, memory=self.memory)
+
+    def deviations(self):
+        """The deviation tables (osg_efr_deviations): dict of offsets [I + 1], target, source, weights_none, y_slot [D],
+        weights, memory, cells [D, L]."""
+        D, L = self.num_deviations, self.memory
+        out = dict(offsets=np.zeros(self.num_infostates + 1, np.int32), target=np.zeros(D, np.int8), source=np.zeros(D, np.int8),
+                   weights_none=np.zeros(D, np.int8), weights=np.zeros((D, L), np.int8), memory=np.zeros((D, L), np.int8),
+                   y_slot=np.zeros(D, np.int32), cells=np.zeros((D, L), np.int32))
+        check(lib().osg_efr_deviations(self._h, *[out[k].ctypes.data for k in
+                                                  ("offsets", "target", "source", "weights_none", "weights", "memory", "y_slot", "cells")]))
+        return out
+
+    def regret_state(self):
+        """The checkpointable regret state (osg_efr_regrets): R per deviation, then the carried y values."""
+        state = np.zeros(self._state_doubles, np.float64)
+        check(lib().osg_efr_regrets(self._h, state.ctypes.data))
+        return state
+
+    def load_regret_state(self, state):
+        state = np.ascontiguousarray(state, np.float64)
+        if state.shape != (self._state_doubles,):
+            raise OsgError(f"load_regret_state: expected {self._state_doubles} doubles")
+        check(lib().osg_efr_upload_regrets(self._h, state.ctypes.data))
+
+    def set_iteration(self, iteration):
+        check(lib().osg_cfr_set_iteration(self._h, int(iteration)))
+
+    def return_cumulative_regret(self):
+        """{infostate string: [cumulative regret by deviation index]} (efr.py:121-132)."""
+        R = self.regret_state()[:self.num_deviations]
+        off = self.deviations()["offsets"]
+        return {k: R[off[i]:off[i + 1]].tolist() for i, k in enumerate(self.tables()["keys"])}
+
+    def current_policy(self):
+        """[I, Amax]: the current policy table, columns the row's legal actions ascending."""
+        return self.tables()["cur_policy"]
+
+    def average_policy(self):
+        """[I, Amax]: the average policy table (efr.py:144-163), a row the regret pass never reached uniform."""
+        return self.tables()["avg_policy"]
