@@ -504,6 +504,79 @@ int osg_mcts_tree_leaf_path(osg_mcts_tree* t, int64_t root, int32_t* h_actions, 
 int64_t osg_mcts_tree_nodes(osg_mcts_tree* t, int64_t root);
 int osg_mcts_tree_download(osg_mcts_tree* t, int64_t root, int64_t cap, uint32_t* h_meta, uint32_t* h_first,
                            uint32_t* h_count, double* h_total, double* h_prior);
+/* The root node's total_reward / explore_count (alpha_zero.cc:141) into d_value [n] f64 (device); NaN where the root
+ * was never visited. */
+int osg_mcts_tree_root_values(osg_mcts_tree* t, double* d_value);
+/* Dirichlet noise for the roots' priors in one launch (mcts.cc:188-203, 284-292; the arithmetic is dirichlet_row of
+ * open_spiel_amd/csrc/osg_selfplay.h).  d_prior [n, A] f64 is mixed IN PLACE at the legal actions of d_mask
+ * [n, mask_words] u32 (bit a of word a / 32, as osg_legal_mask writes it): prior = (1 - epsilon) * prior + epsilon *
+ * noise, noise = one Gamma(alpha, 1) draw per legal action in ascending order on the stream
+ * Rng(seed, index_offset + row, sub), normalised.  Only rows whose d_request byte is 5 are touched (d_request NULL:
+ * every row); illegal columns and all other rows are left bit-unchanged.  alpha > 0, 0 <= epsilon <= 1,
+ * A <= 32 * mask_words. */
+int osg_mcts_root_noise(osg_ctx* ctx, double* d_prior, const uint32_t* d_mask, int mask_words, const uint8_t* d_request,
+                        int64_t n, int A, double alpha, double epsilon, uint64_t seed, int64_t index_offset, uint64_t sub);
+
+/* ---- AlphaZero self-play (alpha_zero_torch/alpha_zero.cc PlayGame, python/algorithms/alpha_zero/alpha_zero.py
+ * _play_game, replay_buffer.py) -----------------------------------------------------------------------------------
+ * The deterministic two-player games: tic_tac_toe, connect_four, hex.  kuhn_poker and leduc_poker answer
+ * OSG_ERR_UNSUPPORTED.  The arithmetic is open_spiel_amd/csrc/osg_selfplay.h.
+ *
+ * osg_replay: a ring of `capacity` training rows that keeps the newest ones.  A row is the game's state record (in
+ * an osg_batch of `capacity` states: osg_replay_states lends it, every batch entry point reads it; do not destroy
+ * it), policy [A] f32, value f32 (player 0's outcome of the row's game), root_value f32, player i8, action i32.
+ * Rows hold states, not observation tensors: pack those for the rows you sample (osg_observation, osg_legal_mask).
+ * osg_replay_sizes: rows held, rows ever appended, capacity (synchronises).
+ * osg_replay_sample: index[j] = Rng(seed, index_offset + j, 0).below(size) for j < m; state, policy [m, A] and value
+ *   [m] of those rows into dst_states (a batch of the game and of m states), d_policy, d_value; d_index [m] i64 (may
+ *   be NULL).  An empty ring or m < 1 is OSG_ERR_INVALID.
+ * osg_replay_rows: the stored rows d_index [m] i64 names (device; each in [0, capacity)), any output may be NULL. */
+typedef struct osg_replay osg_replay;
+int osg_replay_create(osg_ctx* ctx, const char* game_string, int64_t capacity, osg_replay** out);
+int osg_replay_destroy(osg_replay* buf);
+int osg_replay_sizes(osg_replay* buf, int64_t* size, int64_t* total_seen, int64_t* capacity);
+osg_batch* osg_replay_states(osg_replay* buf);
+int osg_replay_sample(osg_replay* buf, uint64_t seed, int64_t index_offset, int64_t m, osg_batch* dst_states,
+                      float* d_policy, float* d_value, int64_t* d_index);
+int osg_replay_rows(osg_replay* buf, const int64_t* d_index, int64_t m, float* d_policy, float* d_value,
+                    float* d_root_value, int8_t* d_player, int32_t* d_action);
+
+/* osg_selfplay: the environments `envs` play games against themselves, one ply per select + commit, and finished
+ * games go to `buf` (both are borrowed and must outlive the object; same game, same context).  Per-environment
+ * trajectories of up to max_game_length plies are staged time-major.
+ * osg_selfplay_select (one launch): from a search's d_child_visits [n, A] i32, d_best_action [n] i32 and d_root_value
+ *   [n] f64 (all device) the policy target p[a] = visits[a] ^ (1 / temperature) / sum and the move: drawn from p on
+ *   the stream Rng(seed, index_offset + env, ply_counter[env]) while the environment has played fewer than
+ *   temperature_drop moves of its game, d_best_action[env] from then on (no draw).  ply_counter[env] counts the plies the
+ *   environment has played since osg_selfplay_create and never resets.  The ply (state record before the move, policy as
+ *   f32, action, root value, player) is staged; d_policy_out [n, A] f32 (may be NULL) and d_action_out [n] i32 receive
+ *   policy and move.  A row whose visits sum to 0 (or whose state is terminal) is left unrecorded, gets action
+ *   OSG_INVALID_ACTION and is counted like an illegal action (osg_ctx_synchronize: OSG_ERR_ILLEGAL).
+ * osg_selfplay_commit (four kernels plus a memset and up to two device-to-device copies; no host read-back unless
+ *   h_counts is given): applies the chosen moves; a game
+ *   ends when its state is terminal, or when |root_value| > cutoff_value, then with returns +-root_value for the mover
+ *   (alpha_zero.cc:154-158); the finished trajectories are appended to the ring in ascending environment order, each in
+ *   ply order, every row with value = returns[0]; finished environments restart from the initial state.
+ *   d_finished [n] u8 and d_returns [n] f64 (player 0's return of a finished game, else 0; either may be NULL);
+ *   h_counts [2] (may be NULL): games finished and rows appended by this call.
+ * osg_selfplay_staged: ply t of every environment's running trajectory (any output may be NULL; dst_states: a batch
+ *   of the game and of n states), d_length [n] i32 the plies staged per environment, d_ply_counter [n] i64. */
+typedef struct {
+  double temperature;        /* finite and > 0 */
+  double cutoff_value;       /* > max_utility: never */
+  int32_t temperature_drop;
+  int32_t reserved;
+  uint64_t seed;
+  int64_t index_offset;
+} osg_selfplay_cfg;
+typedef struct osg_selfplay osg_selfplay;
+int osg_selfplay_create(osg_batch* envs, osg_replay* buf, const osg_selfplay_cfg* cfg, osg_selfplay** out);
+int osg_selfplay_destroy(osg_selfplay* sp);
+int osg_selfplay_select(osg_selfplay* sp, const int32_t* d_child_visits, const int32_t* d_best_action,
+                        const double* d_root_value, float* d_policy_out, int32_t* d_action_out);
+int osg_selfplay_commit(osg_selfplay* sp, uint8_t* d_finished, double* d_returns, int64_t* h_counts);
+int osg_selfplay_staged(osg_selfplay* sp, int t, osg_batch* dst_states, float* d_policy, int32_t* d_action,
+                        float* d_root_value, int8_t* d_player, int32_t* d_length, int64_t* d_ply_counter);
 
 /* ---- tabular CFR family -------------------------------------------------- */
 typedef struct {

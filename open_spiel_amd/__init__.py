@@ -6,7 +6,8 @@ ObservationTensor for tic_tac_toe, connect_four, hex, kuhn_poker and
 leduc_poker, random-rollout evaluation, MCTS, information-set MCTS and alpha-beta search over batches of roots, and
 tabular CFR / Discounted CFR / external-sampling MCCFR / extensive-form fictitious play /
 magnetic mirror descent / extensive-form regret minimization, payoff tensors / policy aggregation / PSRO over populations of policies, and PSRO's
-meta-strategy solvers (projected replicator dynamics, regret matching) on batches of normal-form meta-games.
+meta-strategy solvers (projected replicator dynamics, regret matching) on batches of normal-form meta-games, and
+AlphaZero self-play (policy targets, moves, trajectories and a replay buffer on the device).
 The C-ABI is include/osg_abi.h.
 """
 from ._abi import OsgError, describe, lib  # noqa: F401
@@ -43,6 +44,9 @@ def __getattr__(name):
     if name in ("ISMCTSBot", "ISMCTSFinalPolicyType", "ChildSelectionPolicy"):
         from . import ismcts
         return getattr(ismcts, name)
+    if name in ("SelfPlay", "ReplayBuffer", "TrainInput"):
+        from . import alpha_zero
+        return getattr(alpha_zero, name)
     if name in ("BatchedEnvironment", "TimeStep", "StepType", "ObservationType"):
         from . import vector_env
         return getattr(vector_env, name)

@@ -106,6 +106,17 @@ class MetaCfg(C.Structure):   # osg_meta_cfg
     ]
 
 
+class SelfPlayCfg(C.Structure):   # osg_selfplay_cfg
+    _fields_ = [
+        ("temperature", C.c_double),
+        ("cutoff_value", C.c_double),
+        ("temperature_drop", C.c_int32),
+        ("reserved", C.c_int32),
+        ("seed", C.c_uint64),
+        ("index_offset", C.c_int64),
+    ]
+
+
 class ActionValuesOut(C.Structure):  # osg_action_values_out: host or device addresses, any may be None
     _fields_ = [(name, C.c_void_p) for name in (
         "root_values", "action_values", "cf_reach", "player_reach", "reach", "chance_reach", "cf_reach_by_value",
@@ -177,6 +188,19 @@ SIGNATURES = {
     "osg_mcts_tree_leaf_path": (INT, [VP, I64, VP, INT]),
     "osg_mcts_tree_nodes": (I64, [VP, I64]),
     "osg_mcts_tree_download": (INT, [VP, I64, I64, VP, VP, VP, VP, VP]),
+    "osg_mcts_tree_root_values": (INT, [VP, VP]),
+    "osg_mcts_root_noise": (INT, [VP, VP, VP, INT, VP, I64, INT, C.c_double, C.c_double, U64, I64, U64]),
+    "osg_replay_create": (INT, [VP, C.c_char_p, I64, C.POINTER(VP)]),
+    "osg_replay_destroy": (INT, [VP]),
+    "osg_replay_sizes": (INT, [VP, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
+    "osg_replay_states": (VP, [VP]),
+    "osg_replay_sample": (INT, [VP, U64, I64, I64, VP, VP, VP, VP]),
+    "osg_replay_rows": (INT, [VP, VP, I64, VP, VP, VP, VP, VP]),
+    "osg_selfplay_create": (INT, [VP, VP, C.POINTER(SelfPlayCfg), C.POINTER(VP)]),
+    "osg_selfplay_destroy": (INT, [VP]),
+    "osg_selfplay_select": (INT, [VP, VP, VP, VP, VP, VP]),
+    "osg_selfplay_commit": (INT, [VP, VP, VP, C.POINTER(I64)]),
+    "osg_selfplay_staged": (INT, [VP, INT, VP, VP, VP, VP, VP, VP, VP]),
     "osg_cfr_create": (INT, [VP, C.c_char_p, C.POINTER(CfrCfg), C.POINTER(VP)]),
     "osg_cfr_destroy": (INT, [VP]),
     "osg_cfr_sizes": (INT, [VP, C.POINTER(I64)]),

@@ -663,6 +663,15 @@ k_mcts_tree_results(StepPool pool, int64_t n, int num_actions, int32_t* best_act
                                              MctsOut{best_action, child_visits, child_reward, child_outcome, root_stats}, child_prior);
 }
 
+// The root node's mean reward (alpha_zero.cc:141: root->total_reward / root->explore_count); NaN for an unvisited root.
+__global__ void __launch_bounds__(256) k_mcts_tree_root_values(StepPool pool, int64_t n, double* value) {
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (r >= n) return;
+  const int64_t at0 = pool.at(0, r);
+  const uint32_t count = pool.count[at0];
+  value[r] = count != 0 ? pool.total[at0] / static_cast<double>(count) : __builtin_nan("");
+}
+
 __global__ void __launch_bounds__(256) k_mcts_tree_init(StepPool pool, const int8_t* root_player, int64_t n) {
   const int64_t r = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (r >= n) return;
@@ -979,6 +988,13 @@ int osg_mcts_tree_results(osg_mcts_tree* t, int32_t* best_action, int32_t* child
   else
     k_mcts_tree_results<false><<<dim3(grid), dim3(kBlockM), 0, t->ctx->stream>>>(pool, t->n, t->A, best_action, child_visits,
                                                                                  child_reward, child_outcome, child_prior, root_stats);
+  OSG_HIP(hipGetLastError());
+  return OSG_OK;
+}
+
+int osg_mcts_tree_root_values(osg_mcts_tree* t, double* d_value) {
+  if (!t || !d_value) return set_error(OSG_ERR_INVALID, "osg_mcts_tree_root_values: null argument");
+  k_mcts_tree_root_values<<<dim3(static_cast<unsigned>((t->n + 255) / 256)), dim3(256), 0, t->ctx->stream>>>(make_pool(t), t->n, d_value);
   OSG_HIP(hipGetLastError());
   return OSG_OK;
 }

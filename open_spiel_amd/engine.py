@@ -154,11 +154,22 @@ class StateBatch:
     """N states of one game in HBM (all start at Game::NewInitialState())."""
 
     def __init__(self, ctx, game_string, n):
+        h = C.c_void_p()
+        check(lib().osg_batch_create(ctx._h, game_string.encode(), int(n), C.byref(h)))
+        self._adopt(ctx, game_string, h, owner=None)
+
+    @classmethod
+    def borrowed(cls, ctx, game_string, handle, owner):
+        """A StateBatch over an osg_batch that `owner` owns (kept alive as long as the view is): close() only lets go."""
+        self = cls.__new__(cls)
+        self._adopt(ctx, game_string, C.c_void_p(handle), owner)
+        return self
+
+    def _adopt(self, ctx, game_string, h, owner):
         self.ctx = ctx
         self.game_string = game_string
-        self.n = int(n)
-        h = C.c_void_p()
-        check(lib().osg_batch_create(ctx._h, game_string.encode(), self.n, C.byref(h)))
+        self._owner = owner   # None: the batch is this object's to destroy
+        self.n = int(lib().osg_batch_size(h))
         self._h = h
         self._hraw = h.value  # the osg_batch* as an int for the native step (0 once closed)
         self.desc = _abi.GameDesc()
@@ -177,7 +188,9 @@ class StateBatch:
     def close(self):
         """Free the states now; step() on a closed batch (as source or destination) raises."""
         if self._h:
-            lib().osg_batch_destroy(self._h)
+            if self._owner is None:
+                lib().osg_batch_destroy(self._h)
+            self._owner = None
             self._h = None
             self._hraw = 0
 

@@ -98,7 +98,8 @@ def dirichlet_noise(count, alpha, generator):
 
 def search(roots, evaluator, max_simulations=1024, uct_c=2.0, n_rollouts=1, solve=False, max_nodes=0, seed=0,
            index_offset=0, puct=False, dirichlet_alpha=0.0, dirichlet_epsilon=0.0, dont_return_chance_node=False,
-           max_wall_clock_time=0.0, noise_generator=None, want_tree_of=None, graph=None):
+           max_wall_clock_time=0.0, noise_generator=None, want_tree_of=None, graph=None, noise_seed=None, noise_sub=0,
+           want_root_value=False):
     """MCTSBot::MCTSearch (mcts.cc:353-467) for every root of `roots` with `evaluator` outside the kernel.
     Arguments as MCTSBot's constructor (mcts.h:161-169).  max_wall_clock_time > 0 stops the searches when that
     many seconds have passed (checked between evaluator rounds) instead of after max_simulations.
@@ -106,13 +107,18 @@ def search(roots, evaluator, max_simulations=1024, uct_c=2.0, n_rollouts=1, solv
     i's whole tree as arrays (meta, first_child, explore_count, total_reward, prior; include/osg_abi.h).
     graph: None = evaluators that declare joint = True run one evaluator round per simulation (nothing read back between
     rounds); False = always the request / answer loop below; True = additionally capture the round once and replay it as
-    a graph (measured slower than plain launches on ROCm 7: 1.8 vs 0.73 ms per round at 2^16 roots — kept as an option)."""
+    a graph (measured slower than plain launches on ROCm 7: 1.8 vs 0.73 ms per round at 2^16 roots — kept as an option).
+    noise_seed: None = the root noise is drawn on the host, root by root, from noise_generator; an integer = all roots'
+    noise in one launch on the device (osg_mcts_root_noise: root i draws on Rng(noise_seed, index_offset + i, noise_sub);
+    self-play passes its ply index as noise_sub).  want_root_value adds "root_value" [n]: the root's total_reward /
+    explore_count (alpha_zero.cc:141)."""
     ctx, n = roots.ctx, roots.n
     A, P = roots.num_distinct_actions, roots.num_players
     if (getattr(evaluator, "joint", False) and graph is not False and dirichlet_alpha == 0 and max_wall_clock_time <= 0
             and not isinstance(evaluator, RolloutEvaluator)):
         return _search_joint(roots, evaluator, max_simulations, uct_c, n_rollouts, solve, max_nodes, seed, index_offset,
-                             puct, dont_return_chance_node, want_tree_of, use_graph=graph is True)
+                             puct, dont_return_chance_node, want_tree_of, use_graph=graph is True,
+                             want_root_value=want_root_value)
     needs_prior = bool(getattr(evaluator, "needs_prior", True)) or dirichlet_alpha > 0
     flags = (1 if needs_prior else 0) | (2 if dont_return_chance_node else 0)
     # (with max_wall_clock_time the searches still stop at max_simulations: the tree slots are sized for it)
@@ -125,6 +131,7 @@ def search(roots, evaluator, max_simulations=1024, uct_c=2.0, n_rollouts=1, solv
         request = torch.zeros(n, dtype=torch.uint8, device=ctx.device)
         counts = (C.c_int64 * 4)()
         prior = value = None
+        roots_to_mix = True   # (noise_seed) no round has mixed the root noise yet
         start = time.perf_counter()
         while True:
             # (one new simulation per search and launch: see _search_joint)
@@ -150,11 +157,27 @@ def search(roots, evaluator, max_simulations=1024, uct_c=2.0, n_rollouts=1, solv
             if counts[1]:
                 if prior is None:
                     raise OsgError("the evaluator returned no prior although searches asked for one")
+                given = prior
                 prior = prior.to(torch.float64).contiguous()
                 if prior.shape != (n, A):
                     raise OsgError(f"evaluator prior has shape {tuple(prior.shape)}, expected {(n, A)}")
                 at_root = request == 5
-                if dirichlet_alpha > 0 and bool(at_root.any()):
+                if dirichlet_alpha > 0 and noise_seed is not None:
+                    # The same mix for every root that asked at its root, in one launch (rows without request 5 untouched).
+                    # The searches run in step, so their roots all ask in the first round that asks for priors; a root asks
+                    # again only after a garbage collection cleared its children, i.e. with fewer visits than the collection's limit,
+                    # which takes a caller's small max_nodes (a pool capped by free memory collects far later) —
+                    # without one the later rounds skip the mask, the copy and a launch that would touch no row.
+                    if roots_to_mix or max_nodes > 0:
+                        roots_to_mix = False
+                        bits = leaf.legal_actions_mask_bits()
+                        if prior.data_ptr() == given.data_ptr():
+                            prior = prior.clone()   # mixed in place: never the evaluator's own tensor
+                        check(lib().osg_mcts_root_noise(ctx._h, prior.data_ptr(), bits.data_ptr(), bits.shape[1],
+                                                        request.data_ptr(), n, A, float(dirichlet_alpha),
+                                                        float(dirichlet_epsilon), int(noise_seed) & (2 ** 64 - 1),
+                                                        int(index_offset), int(noise_sub)))
+                elif dirichlet_alpha > 0 and bool(at_root.any()):
                     # the root's prior (mcts.cc:284-292): (1 - epsilon) * prior + epsilon * Dirichlet(alpha) noise
                     legal = leaf.legal_actions_mask()[:, :A].bool().cpu()
                     pr = prior.cpu()
@@ -173,7 +196,7 @@ def search(roots, evaluator, max_simulations=1024, uct_c=2.0, n_rollouts=1, solv
                     raise OsgError(f"evaluator value has shape {tuple(value.shape)}, expected {(n, P)}")
             else:
                 value = None
-        return _results(tree, ctx, n, A, want_tree_of)
+        return _results(tree, ctx, n, A, want_tree_of, want_root_value)
     finally:
         lib().osg_mcts_tree_destroy(tree)
 
@@ -185,7 +208,7 @@ def _answer(t, rows, cols):
     return t.to(torch.float64).contiguous()
 
 
-def _results(tree, ctx, n, A, want_tree_of):
+def _results(tree, ctx, n, A, want_tree_of, want_root_value=False):
     out = {
         "best_action": torch.empty(n, dtype=torch.int32, device=ctx.device),
         "child_visits": torch.empty((n, A), dtype=torch.int32, device=ctx.device),
@@ -197,6 +220,9 @@ def _results(tree, ctx, n, A, want_tree_of):
     check(lib().osg_mcts_tree_results(tree, *[out[k].data_ptr() for k in
                                               ("best_action", "child_visits", "child_reward", "child_outcome",
                                                "child_prior", "root_stats")]))
+    if want_root_value:
+        out["root_value"] = torch.empty(n, dtype=torch.float64, device=ctx.device)
+        check(lib().osg_mcts_tree_root_values(tree, out["root_value"].data_ptr()))
     if want_tree_of is not None:
         import numpy as np
         used = lib().osg_mcts_tree_nodes(tree, int(want_tree_of))
@@ -212,7 +238,7 @@ def _results(tree, ctx, n, A, want_tree_of):
 
 
 def _search_joint(roots, evaluator, max_simulations, uct_c, n_rollouts, solve, max_nodes, seed, index_offset, puct,
-                  dont_return_chance_node, want_tree_of, use_graph):
+                  dont_return_chance_node, want_tree_of, use_graph, want_root_value=False):
     """search() for an evaluator that answers prior and value together (BatchedEvaluator.joint): the prior that comes
     with a leaf's value is kept on the device until the leaf is expanded (osg_mcts_tree_create flag 8), so every
     simulation is ONE round — advance the searches, pack the leaves' observations and legal masks, one forward — and
@@ -289,10 +315,10 @@ def _search_joint(roots, evaluator, max_simulations, uct_c, n_rollouts, solve, m
                 answers[0], answers[1] = _answer(pr, n, A), _answer(va, n, P)
         if use_graph:
             with torch.cuda.stream(side):
-                out = _results(tree, ctx, n, A, want_tree_of)
+                out = _results(tree, ctx, n, A, want_tree_of, want_root_value)
             side.synchronize()
             return out
-        return _results(tree, ctx, n, A, want_tree_of)
+        return _results(tree, ctx, n, A, want_tree_of, want_root_value)
     finally:
         if bound_before is not None:
             ctx.synchronize()
