@@ -962,6 +962,56 @@ int osg_meta_solve(osg_ctx* ctx, int n_players, const int32_t* shape /* [P] */, 
                    const double* tensors /* [n_problems, P, K_0 .. K_{P-1}] */, const osg_meta_cfg* cfgs, int64_t n_cfgs,
                    const double* initial, double* average, double* last, int on_host);
 
+/* ---- alpha-rank on a batch of normal-form meta-games ------------------------------------------------
+ * open_spiel/python/egt/alpharank.py: compute() at a finite alpha (use_fast_compute) or at infinite alpha with one noise
+ * level eps, and sweep_pi_vs_epsilon(); psro_v2's default meta-solver.  A problem is P payoff tensors [K_0 .. K_{P-1}], one
+ * per player, row-major; the chain's states are the n = K_0 * .. * K_{P-1} pure profiles, a profile's id its row-major
+ * index.  n_players = 1 is the single-population chain with the local selection model: `shape` is then the [K, K] of one
+ * square table and n = K.  The stationary distribution comes from a Grassmann-Taksar-Heyman elimination, which never
+ * subtracts: no negative mass, small masses keep their relative accuracy, and nothing fails where the reference's
+ * eigen-solve does.  csrc/osg_alpharank.h has every formula and the one order of every sum (the multiply-add is not
+ * fused); a workgroup solves one (problem, eps), the matrix in LDS or in the context's scratch.  The bits of a problem's
+ * result depend on its tensors and its cfg, not on its position, on n_problems, on the other problems, on `form`, on
+ * `chunk` or on on_host.
+ *   cfgs      n_cfgs = 1: one cfg for every problem; n_cfgs = n_problems: problem b runs cfgs[b] (a sweep of alpha or m
+ *             over copies of one meta-game, or problems of different modes, is one call).  ALWAYS host memory.
+ *   mode      0: finite alpha with population size m; 1: infinite alpha at eps; 2: eps_0 = eps (0: 0.5), eps_{t+1} = 0.5
+ *             eps_t, solved until the first t > min_iters with |pi_t - pi_{t-1}| <= 1e-8 + 1e-5 |pi_{t-1}| everywhere.
+ *   form      0: the matrix stays in LDS where n * n doubles fit the workgroup's LDS limit (from the device's properties)
+ *             beside a vector, and in scratch memory otherwise; 1 / 2 name one (1 where it does not fit:
+ *             OSG_ERR_UNSUPPORTED).  Every cfg of a call names the same form and the same chunk.
+ *   chunk     mode 2: consecutive epsilons solved per launch, speculatively (0: 8, fewer where the scratch for them would
+ *             pass 2^30 bytes); the host waits once per chunk for the count of finished problems, also with on_host = 0.
+ *   pi        [n_problems, n]
+ *   marginals [n_problems, sum K_p] (n_players = 1: [n_problems, K], pi itself), or NULL: per player and strategy the sum
+ *             of pi over the profiles that play it (psro_v2/utils.py get_alpharank_marginals)
+ *   eps_used, iterations   [n_problems] or NULL: mode 2: the epsilon of the returned pi and its step t; mode 1: eps, 0;
+ *             mode 0: 0, 0
+ *   status    [n_problems]: 0; 1: the chain is not irreducible in floating point (a pivot row's sum is 0 or not finite: a
+ *             finite-alpha fixation probability underflowed, or a payoff is not finite), which also ends a sweep; 2: the
+ *             sweep did not stop before max_iters.  With 1 or 2 the problem's pi and marginals are NaN; the other
+ *             problems of the call are unaffected.
+ * on_host = 1: tensors and every output are host memory and the call returns when the outputs have arrived; on_host = 0:
+ * they are device memory and the launches are enqueued on the context's stream.
+ * A refused call writes nothing.  OSG_ERR_INVALID: a null ctx, shape, cfgs, tensors, pi or status, n_problems < 0, n_cfgs
+ * neither 1 nor n_problems, a mode outside 0..2, mode 0 with m < 1 or an alpha that is not finite, an eps that is negative
+ * or not finite (mode 1: or 0), min_iters < 0 or max_iters < 1, a form outside 0..2 or a negative chunk, or either not the
+ * same in every cfg, a size below 1, a table that is not square with n_players = 1.  OSG_ERR_UNSUPPORTED: fewer than 1 or
+ * more than 5 players, more than 4096 profiles, more than 2^16 problems, a chunk above 64, max_iters above 4096, form 1 where the matrix does
+ * not fit, or problems whose scratch for ONE epsilon each would pass 2^30 bytes (global form: n_problems * n * n * 8). */
+typedef struct osg_alpharank_cfg {
+  int32_t mode;        /* 0 finite alpha (compute), 1 infinite alpha at one eps, 2 sweep over eps */
+  int32_t m;           /* mode 0 */
+  double alpha;        /* mode 0 */
+  double eps;          /* mode 1: inf_alpha_eps; mode 2: the warm start, 0 = 0.5 */
+  int32_t min_iters, max_iters;   /* mode 2; the reference's 10 and 100 */
+  int32_t form;        /* 0 by size, 1 LDS, 2 global */
+  int32_t chunk;       /* mode 2: epsilons per launch, 0 = the implementation's choice */
+} osg_alpharank_cfg;
+int osg_alpharank(osg_ctx* ctx, int n_players, const int32_t* shape, int64_t n_problems,
+                  const double* tensors /* [n_problems, P, K_0 .. K_{P-1}] */, const osg_alpharank_cfg* cfgs, int64_t n_cfgs,
+                  double* pi, double* marginals, double* eps_used, int32_t* iterations, int32_t* status, int on_host);
+
 /* ---- multi-GPU exchange step ---------------------------------------------------
  * One process per GPU.  Units shard by global index with no data-path collective; the ONE exchange
  * on the path is external-sampling MCCFR's all-reduce(sum) of the regret / average-policy delta

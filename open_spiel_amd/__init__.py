@@ -37,10 +37,10 @@ def __getattr__(name):
     if name == "PSROSolver":
         from . import psro
         return psro.PSROSolver
-    if name in ("meta_solvers", "solve_meta_games"):   # (its projected_replicator_dynamics / regret_matching: by the module)
+    if name in ("meta_solvers", "solve_meta_games", "solve_alpharank"):   # (the reference-named solvers: by the module)
         import importlib
         module = importlib.import_module(".meta_solvers", __name__)
-        return module if name == "meta_solvers" else module.solve_meta_games
+        return module if name == "meta_solvers" else getattr(module, name)
     if name in ("ISMCTSBot", "ISMCTSFinalPolicyType", "ChildSelectionPolicy"):
         from . import ismcts
         return getattr(ismcts, name)

@@ -106,6 +106,19 @@ class MetaCfg(C.Structure):   # osg_meta_cfg
     ]
 
 
+class AlphaRankCfg(C.Structure):   # osg_alpharank_cfg
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("m", C.c_int32),
+        ("alpha", C.c_double),
+        ("eps", C.c_double),
+        ("min_iters", C.c_int32),
+        ("max_iters", C.c_int32),
+        ("form", C.c_int32),
+        ("chunk", C.c_int32),
+    ]
+
+
 class SelfPlayCfg(C.Structure):   # osg_selfplay_cfg
     _fields_ = [
         ("temperature", C.c_double),
@@ -249,6 +262,7 @@ SIGNATURES = {
     "osg_cfr_profile_returns": (INT, [VP, VP, INT, VP, I64, INT, VP]),
     "osg_cfr_aggregate_policies": (INT, [VP, VP, INT, VP, C.c_double, INT, VP]),
     "osg_meta_solve": (INT, [VP, INT, VP, I64, VP, VP, I64, VP, VP, VP, INT]),
+    "osg_alpharank": (INT, [VP, INT, VP, I64, VP, VP, I64, VP, VP, VP, VP, VP, INT]),
     "osg_cfr_infostate_key": (INT, [VP, I64, C.c_char_p, INT]),
     "osg_cfr_best_response_history_values": (INT, [VP, INT, VP, INT, VP]),
     "osg_cfr_tree_edges": (INT, [VP, VP, VP]),

@@ -211,6 +211,20 @@ int osg_ctx_scratch(osg_ctx* ctx, size_t bytes, void** out);
 namespace osg {
 // Offsets of the pieces a caller carves out of it: multiples of 256 bytes, like the allocation itself.
 inline size_t align_up(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
+// The LDS one workgroup may have on `device`, from its properties (asked once per device).
+inline int workgroup_lds_limit(int device, size_t* out) {
+  static std::mutex mu;
+  static std::map<int, size_t> known;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = known.find(device);
+  if (it == known.end()) {
+    hipDeviceProp_t prop;
+    OSG_HIP(hipGetDeviceProperties(&prop, device));
+    it = known.emplace(device, prop.sharedMemPerBlockOptin ? prop.sharedMemPerBlockOptin : prop.sharedMemPerBlock).first;
+  }
+  *out = it->second;
+  return OSG_OK;
+}
 }  // namespace osg
 
 #endif  // OSG_INTERNAL_H_

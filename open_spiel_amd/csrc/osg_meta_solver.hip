@@ -147,21 +147,6 @@ __global__ void __launch_bounds__(64 * kMetaMaxPlayers) k_meta_solve(MetaCall c)
   }
 }
 
-// The LDS one workgroup may have on `device`, from its properties (asked once per device).
-int workgroup_lds_limit(int device, size_t* out) {
-  static std::mutex mu;
-  static std::map<int, size_t> known;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = known.find(device);
-  if (it == known.end()) {
-    hipDeviceProp_t prop;
-    OSG_HIP(hipGetDeviceProperties(&prop, device));
-    it = known.emplace(device, prop.sharedMemPerBlockOptin ? prop.sharedMemPerBlockOptin : prop.sharedMemPerBlock).first;
-  }
-  *out = it->second;
-  return OSG_OK;
-}
-
 }  // namespace
 
 extern "C" {

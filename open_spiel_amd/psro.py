@@ -2,10 +2,12 @@
 on the kuhn_poker / leduc_poker trees: the population, the payoff tensors' new cells, the aggregation of a meta-strategy
 into one behavioural policy and the best responses to it all run on the device (TabularSolver.profile_returns,
 aggregate_policies, osg_cfr_best_response), and so do psro_v2's "prd" and "rm" meta-solvers (projected replicator
-dynamics and regret matching, meta_solvers.py: every iteration of a solve in one launch); a meta-solver passed as a
-callable runs on the host.  Out of scope: strategy selectors other than "add every player's best response", sampled
+dynamics and regret matching, meta_solvers.py: every iteration of a solve in one launch) and its default, "alpharank" (the
+sweep over the infinite-alpha noise, of which the MARGINALS are played); a meta-solver passed as a callable runs on the
+host.  Out of scope: strategy selectors other than "add every player's best response", sampled
 meta-game estimation (sims_per_entry), reinforcement-learning oracles, the LP Nash solver ("nash"; pass one as a
-callable), "uniform_biased", joint meta-strategies and alpha-rank."""
+callable), "uniform_biased" and joint meta-strategies (psro_v2 hands alpha-rank's joint distribution to its rectified /
+joint training; here its marginals are played)."""
 import functools
 import itertools
 
@@ -16,7 +18,8 @@ from . import _abi, meta_solvers
 from ._abi import OsgError, check, lib
 from .engine import TabularSolver
 
-DEVICE_META_SOLVERS = {"prd": meta_solvers.projected_replicator_dynamics, "rm": meta_solvers.regret_matching}
+DEVICE_META_SOLVERS = {"prd": meta_solvers.projected_replicator_dynamics, "rm": meta_solvers.regret_matching,
+                       "alpharank": meta_solvers.alpharank_strategy}
 
 
 def uniform_meta_solver(payoff_tensors):
@@ -27,7 +30,8 @@ def uniform_meta_solver(payoff_tensors):
 class PSROSolver:
     """PSRO / double oracle on the device.  `meta_solver`: "uniform"; "prd" or "rm", projected replicator dynamics or
     regret matching on the device with `meta_solver_kwargs` under the reference's names (prd_iterations, prd_dt,
-    prd_gamma / iterations, gamma, average_over_last_n_strategies, ...; its defaults otherwise); or any callable that takes
+    prd_gamma / iterations, gamma, average_over_last_n_strategies, ...; its defaults otherwise); "alpharank", the marginals
+    of alpha-rank's swept distribution on the device; or any callable that takes
     the payoff tensors (a list of P arrays [K_0, ..., K_{P-1}], psro_v2's `meta_games`) and returns P weight vectors, the
     reference's meta-solvers among them.  `initial`: "uniform", or an [I, Amax] policy table in the solver's layout: every player's
     first policy.  With the uniform meta-solver and the uniform initial policy this is fictitious play with kept
@@ -43,13 +47,13 @@ class PSROSolver:
         self.num_players = _abi.describe(game_string).num_players
         I, A = self.solver.num_infostates, self.solver.amax
         if meta_solver_kwargs and not (isinstance(meta_solver, str) and meta_solver in DEVICE_META_SOLVERS):
-            raise OsgError("PSROSolver: meta_solver_kwargs go with meta_solver 'prd' or 'rm'")
+            raise OsgError("PSROSolver: meta_solver_kwargs go with meta_solver 'prd', 'rm' or 'alpharank'")
         if meta_solver == "uniform":
             meta_solver = uniform_meta_solver
         elif isinstance(meta_solver, str) and meta_solver in DEVICE_META_SOLVERS:
             meta_solver = functools.partial(DEVICE_META_SOLVERS[meta_solver], ctx, **dict(meta_solver_kwargs or {}))
         if not callable(meta_solver):
-            raise OsgError(f"PSROSolver: meta_solver must be 'uniform', 'prd', 'rm' or a callable, not {meta_solver!r}")
+            raise OsgError(f"PSROSolver: meta_solver must be 'uniform', 'prd', 'rm', 'alpharank' or a callable, not {meta_solver!r}")
         self._meta_solver = meta_solver
         self._nact = np.zeros(I, np.int32)
         check(lib().osg_cfr_tables(self.solver._h, self._nact.ctypes.data, None, None, None, None, None))
