@@ -115,7 +115,9 @@ OSG_HD void qv_infostate(int i, int p, int n, int A, int P, int m0, int m1, cons
   o.reach[i] = reach;
   o.cf_reach[i] = cf;
   o.chance_reach[i] = chance;
-  o.player_reach[i] = m1 > m0 ? rm[static_cast<size_t>(m0) * (P + 1) + p] : 0.0;
+  // the reference assigns ("=", action_value.py:132) at every member: the LAST member's own reach stays.  The members agree
+  // under perfect recall; leduc_poker(action_mapping=True) reaches an infostate by fold and by call, and they do not.
+  o.player_reach[i] = m1 > m0 ? rm[static_cast<size_t>(m1 - 1) * (P + 1) + p] : 0.0;
   for (int a = 0; a < A; ++a) {
     double cfq = 0.0, own = 0.0;
     for (int q = 0; q < P; ++q) {

@@ -104,6 +104,12 @@ int efr_refusal(const osg_cfr* s, const char* who) {
   if (mmd_mode(s)) return set_error(OSG_ERR_INVALID, w + ": the solver is in mirror-descent mode (osg_mmd_set_params)");
   if (s->B > 1) return set_error(OSG_ERR_UNSUPPORTED, w + ": one solver per object (replicas > 1 are not served)");
   if (!s->path_kernel || s->P > kEfrMaxPlayers) return set_error(OSG_ERR_UNSUPPORTED, w + ": the tree's root paths are not indexable");
+  // leduc_poker(action_mapping=True): "fold" where there is nothing to call is "call" and leads to the same information
+  // state, so an information state has no single own history for a deviation to remember, and the reference's run cannot
+  // be pinned (the regrets between the two tied moves are rounding noise that its max(0, R) then decides on)
+  if (s->spec.desc.game_kind == kLeduc && s->spec.leduc.mapping)
+    return set_error(OSG_ERR_UNSUPPORTED, w + ": leduc_poker with action_mapping=True gives an information state several own histories (fold "
+                                              "and call lead to the same one); EFR serves action_mapping=False");
   if (s->A > kEfrMaxA) return set_error(OSG_ERR_UNSUPPORTED, w + ": a policy row wider than " + std::to_string(kEfrMaxA) + " actions");
   return cfr_sub_error(s);
 }

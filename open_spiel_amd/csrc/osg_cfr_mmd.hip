@@ -277,6 +277,12 @@ int mmd_refusal(const osg_cfr* s, const char* who) {
   if (s->cfg.solver != 0) return set_error(OSG_ERR_INVALID, w + ": needs a CFRSolverBase table (solver 0), not an MCCFR solver");
   if (s->dcfr) return set_error(OSG_ERR_INVALID, w + ": mirror descent has no discounting, this solver discounts (osg_cfr_set_discounting)");
   if (s->P != 2) return set_error(OSG_ERR_UNSUPPORTED, w + ": two-player zero-sum games only, this game has " + std::to_string(s->P) + " players");
+  // leduc_poker(action_mapping=True): "fold" where there is nothing to call is "call", both lead to the same information
+  // state of the player who chose, so an information state has several parent sequences and the game has no sequence
+  // form (the reference's mmd_dilated.py ends in log(0) = NaN there)
+  if (s->spec.desc.game_kind == kLeduc && s->spec.leduc.mapping)
+    return set_error(OSG_ERR_UNSUPPORTED, w + ": leduc_poker with action_mapping=True has no sequence form (fold and call lead to the same "
+                                              "information state); mirror descent serves action_mapping=False");
   if (!s->eval_ok) return set_error(OSG_ERR_UNSUPPORTED, w + ": an information state spans several tree levels");
   if (s->A > kMmdMaxRow) return set_error(OSG_ERR_UNSUPPORTED, w + ": a policy row wider than " + std::to_string(kMmdMaxRow) + " actions");
   if (s->B > 1 && !mmd_takes_the_resident_form(s))

@@ -171,6 +171,13 @@ int population_call(osg_cfr* s, const char* who, const void* a, const void* b, c
   if (n_tables < 1) return set_error(OSG_ERR_INVALID, name + ": n_tables must be at least 1");
   if (!s->path_kernel || s->P > kMaxPlayers)
     return set_error(OSG_ERR_UNSUPPORTED, name + ": the tree's root paths do not fit their codes");
+  // the leduc_poker parameters change what the realization plans lean on (unequal chance weights with suit_isomorphism,
+  // several own sequences per information state with action_mapping, the owner of the first level with
+  // starting_player) and no run of the reference on them is recorded: refused until one is
+  if (s->spec.desc.game_kind == kLeduc && (s->spec.leduc.iso || s->spec.leduc.mapping || s->spec.leduc.starter != 0))
+    return set_error(OSG_ERR_UNSUPPORTED, name + ": leduc_poker populations are served with its default rules; " +
+                                              (s->spec.leduc.iso ? "suit_isomorphism=True" : s->spec.leduc.mapping ? "action_mapping=True" : "starting_player != 0") +
+                                              " is not served (no recorded run of the reference pins it)");
   const size_t IA = static_cast<size_t>(s->I) * s->A;
   if (static_cast<size_t>(n_tables) > kPopMaxStackBytes / (sizeof(double) * std::max<size_t>(IA, 1)))
     return set_error(OSG_ERR_UNSUPPORTED, name + ": " + std::to_string(n_tables) + " tables of " + std::to_string(IA) +

@@ -96,7 +96,7 @@ __global__ void __launch_bounds__(kQvThreads) k_qv_infostates(Tree t, QvCall c) 
     o.reach[i] = reach;
     o.cf_reach[i] = cf;
     o.chance_reach[i] = chance;
-    o.player_reach[i] = cnt > 0 ? c.rm[static_cast<size_t>(m0) * (P + 1) + p] : 0.0;
+    o.player_reach[i] = cnt > 0 ? c.rm[static_cast<size_t>(m0 + cnt - 1) * (P + 1) + p] : 0.0;   // the last member's (qv_infostate)
   }
   for (int a = 0; a < A; ++a) {
     double cfq = 0.0, own = 0.0;

@@ -132,6 +132,13 @@ extern "C" int osg_ismcts_search(const osg_batch* roots, const osg_ismcts_cfg* c
                                           "(the perfect-information games have osg_mcts_search)");
   if (d.num_players > kIsPlayers)
     return set_error(OSG_ERR_UNSUPPORTED, "osg_ismcts_search: kuhn_poker and leduc_poker are searched with 2 or 3 players");
+  // the leduc_poker parameters change what the search leans on (rank-keyed nodes and the resampler's "never my rank"
+  // with suit_isomorphism, three legal actions and tied children with action_mapping, who owns the first level with
+  // starting_player) and no run of the reference on them is recorded: refused until one is
+  if (d.game_kind == kLeduc && (roots->spec.leduc.iso || roots->spec.leduc.mapping || roots->spec.leduc.starter != 0))
+    return set_error(OSG_ERR_UNSUPPORTED, std::string("osg_ismcts_search: leduc_poker is searched with its default rules; ") +
+                                              (roots->spec.leduc.iso ? "suit_isomorphism=True" : roots->spec.leduc.mapping ? "action_mapping=True" : "starting_player != 0") +
+                                              " is not served (no recorded run of the reference pins it)");
   if (cfg_in->max_simulations < 1 || cfg_in->n_rollouts < 1)
     return set_error(OSG_ERR_INVALID, "osg_ismcts_cfg: max_simulations and n_rollouts must be >= 1");
   if (cfg_in->final_policy_type < 1 || cfg_in->final_policy_type > 3)

@@ -346,13 +346,17 @@ def unit_cases(efr, log):
                 rank=np.array([r[7] for r in rows], np.int32), sv=np.array([r[8] for r in rows])), deficient
 
 
-def main():
+def main(runs=None, path=None):
+    """runs, path: another list in the form of RUNS and its file (tests/golden/make_solver_variant_vectors.py), without
+    the regret-matching unit cases, which do not depend on the game."""
+    variant = runs is not None
+    runs, path = (RUNS if runs is None else runs), (path or GOLDEN)
     pyspiel, efr, cfr = reference_modules()
     log = SolveLog(efr.linalg)
     efr.linalg = log
-    out = {"runs": np.array([f"{g}|{d}" for g, d, _ in RUNS])}
+    out = {"runs": np.array([f"{g}|{d}" for g, d, _ in runs])}
     t_all = time.time()
-    for r, (game_string, name, checkpoints) in enumerate(RUNS):
+    for r, (game_string, name, checkpoints) in enumerate(runs):
         t0 = time.time()
         log.min_ratio = np.inf
         game = pyspiel.load_game(game_string)
@@ -369,12 +373,13 @@ def main():
             for k, v in eq.items():
                 out[f"cfr/{game_string}/{k}"] = v
             print(f"   against cfr.py: average policy differs by at most {np.max(np.abs(eq['avg'] - rec['avg'][-1])):.3g}", flush=True)
-    rm, deficient = unit_cases(efr, log)
-    for k, v in rm.items():
-        out[f"rm/{k}"] = v
-    print(f"{len(rm['A'])} regret-matching cases, {deficient} rank-deficient")
-    np.savez_compressed(GOLDEN, **out)
-    print(GOLDEN, os.path.getsize(GOLDEN), "bytes,", f"{time.time() - t_all:.0f} s of reference time")
+    if not variant:
+        rm, deficient = unit_cases(efr, log)
+        for k, v in rm.items():
+            out[f"rm/{k}"] = v
+        print(f"{len(rm['A'])} regret-matching cases, {deficient} rank-deficient")
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), "bytes,", f"{time.time() - t_all:.0f} s of reference time")
 
 
 if __name__ == "__main__":

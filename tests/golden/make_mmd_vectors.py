@@ -205,11 +205,14 @@ def qre_vectors(mods):
     return out
 
 
-def main(only=None, path=None):
+def main(only=None, path=None, runs=None):
+    """runs: another list in the form of RUNS (tests/golden/make_solver_variant_vectors.py); then `only` is taken as given."""
     mods = reference_modules()
     pyspiel, mmd_dilated, _ = mods
     out = {}
-    runs = [r for r in RUNS if only is None or r[0] in only]
+    if runs is not None:
+        only = {r[0] for r in runs}
+    runs = [r for r in (RUNS if runs is None else runs) if only is None or r[0] in only]
     for game_string in sorted({r[1] for r in runs}):
         game, (keys, row, legal, amax, player, pred_info, pred_action, term_seq, term_cu, bfs_rank), maps = \
             game_layout(pyspiel, mmd_dilated, game_string)

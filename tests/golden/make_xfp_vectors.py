@@ -123,7 +123,9 @@ def reaches(fictitious_play, solver, game, row):
     return avg_out, br_out
 
 
-def reference_run(game_string, iterations, nash_conv_at):
+def reference_run(game_string, iterations, nash_conv_at, action_values=False):
+    """action_values=True adds <game>/q [T, I, Amax]: the counterfactual-weighted action values the best response
+    maximised over (NaN at an infostate without counterfactual reach); tests/golden/make_solver_variant_vectors.py."""
     pyspiel, fictitious_play, exploitability, best_response = reference_modules()
     game = pyspiel.load_game(game_string)
     keys, row, legal, player, pred_info, pred_action = layout(game)
@@ -154,6 +156,8 @@ def reference_run(game_string, iterations, nash_conv_at):
                    avg_reach=np.zeros((iterations, I)), br_reach=np.zeros((iterations, I)),
                    policy=np.zeros((iterations, I, amax)), min_gap=np.full(iterations, np.inf),
                    ties=np.zeros(iterations, np.int32))
+        if action_values:
+            out["q"] = np.full((iterations, I, amax), np.nan)
         nash = {}
         for t in range(1, iterations + 1):
             del made[:]
@@ -166,7 +170,10 @@ def reference_run(game_string, iterations, nash_conv_at):
                     if not any(cf_p != 0 for _, cf_p in infoset):
                         continue
                     out["cf_nonzero"][t - 1, i] = True
-                    values = sorted((sum(cf_p * br.q_value(s, a) for s, cf_p in infoset) for a in legal[i]), reverse=True)
+                    values = [sum(cf_p * br.q_value(s, a) for s, cf_p in infoset) for a in legal[i]]
+                    if action_values:
+                        out["q"][t - 1, i, :len(values)] = values
+                    values = sorted(values, reverse=True)
                     if len(values) < 2:
                         continue
                     gap = values[0] - values[1]

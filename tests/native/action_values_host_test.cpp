@@ -70,7 +70,7 @@ void infostate_by_chunks(int i, int p, int n, int A, int P, int m0, int m1, cons
       }
   }
   o.reach[i] = reach; o.cf_reach[i] = cf; o.chance_reach[i] = chance;
-  o.player_reach[i] = cnt > 0 ? rm[static_cast<size_t>(m0) * (P + 1) + p] : 0.0;
+  o.player_reach[i] = cnt > 0 ? rm[static_cast<size_t>(m0 + cnt - 1) * (P + 1) + p] : 0.0;   // the last member's, as k_qv_infostates
   for (int a = 0; a < A; ++a) {
     for (int q = 0; q < P; ++q) o.weighted[(static_cast<size_t>(i) * A + a) * P + q] = w[static_cast<size_t>(a) * P + q];
     o.q[static_cast<size_t>(i) * A + a] = a < n ? qv_action_value(w[static_cast<size_t>(a) * P + p], reach) : 0.0;
