@@ -1012,6 +1012,57 @@ int osg_alpharank(osg_ctx* ctx, int n_players, const int32_t* shape, int64_t n_p
                   const double* tensors /* [n_problems, P, K_0 .. K_{P-1}] */, const osg_alpharank_cfg* cfgs, int64_t n_cfgs,
                   double* pi, double* marginals, double* eps_used, int32_t* iterations, int32_t* status, int on_host);
 
+/* ---- Deep CFR (open_spiel/python/pytorch/deep_cfr.py) --------------------------------------------
+ * The networks are the caller's (torch); the device does what the reference does one tree node per interpreter step:
+ * the traversals, the sampled advantages and the reservoir appends.  The arithmetic is
+ * open_spiel_amd/csrc/osg_deep_cfr.h.
+ *
+ * osg_cfr_infostate_tensors: State::InformationStateTensor(player of the infostate) of every infostate, in the
+ *   solver's infostate order, out [I, info_size] f32 (deep_cfr.py:453,472,495), from one member history each.
+ *
+ * osg_reservoir: ReservoirBuffer (deep_cfr.py:121-213) on the device.  A row is (infostate index i32, iteration i32,
+ *   values f32 [num_actions]): osg_cfr_infostate_tensors rebuilds the tensor the reference stores with each row.
+ *   The row with add index n (0-based over the buffer's life, osg_reservoir_clear restarts it) goes to slot n while
+ *   n < capacity, else to idx = mulhi64(Rng(seed, n, stream).next(), n + 1) if idx < capacity, else nowhere
+ *   (append, :150-182; the reference draws idx with np.random.randint(0, n + 1)).
+ * osg_reservoir_append: m rows (device arrays d_info [m], d_values [m, num_actions]; one iteration for all) as m
+ *   sequential append calls in row order, bit for bit: of the rows of a call that meet in a slot the last one stays.
+ *   Two launches, an integer atomicMax per slot and a copy by the winners; no floating-point atomics.
+ * osg_reservoir_sizes: rows held, add calls, capacity.
+ * osg_reservoir_sample: d_slots [m] i64 = m distinct filled slots (sample, :184-203, choice(replace=False)): the m
+ *   smallest keys Rng(seed, slot, stream).next() over the filled slots, ascending by (key, slot).  m above the rows
+ *   held is OSG_ERR_INVALID.
+ * osg_reservoir_rows: the rows d_slots [m] i64 names (device), any output may be NULL. */
+typedef struct osg_reservoir osg_reservoir;
+int osg_cfr_infostate_tensors(osg_cfr* s, float* out /* [I, info_size] */, int on_host);
+int osg_reservoir_create(osg_ctx* ctx, int num_actions, int64_t capacity, uint64_t seed, uint64_t stream, osg_reservoir** out);
+int osg_reservoir_destroy(osg_reservoir* buf);
+int osg_reservoir_sizes(osg_reservoir* buf, int64_t* size, int64_t* add_calls, int64_t* capacity);
+int osg_reservoir_clear(osg_reservoir* buf);
+int osg_reservoir_append(osg_reservoir* buf, int64_t m, const int32_t* d_info, int32_t iteration, const float* d_values);
+int osg_reservoir_sample(osg_reservoir* buf, uint64_t seed, uint64_t stream, int64_t m, int64_t* d_slots);
+int osg_reservoir_rows(osg_reservoir* buf, const int64_t* d_slots, int64_t m, int32_t* d_info, int32_t* d_iteration,
+                       float* d_values);
+/* osg_deep_cfr_traverse: _traverse_game_tree(root, player) (deep_cfr.py:413-481) x trajectories on any osg_cfr object
+ *   (its tables are not touched).  d_advantages [I, Amax] f32 (device) holds every infostate's advantage-network
+ *   output by action id; the strategy of an infostate (_sample_action_from_advantage, :484-512) is formed once per call.
+ *   Trajectory g = first_trajectory + j draws Rng(seed, g, 0).unit() in visiting order, one per chance node and one per
+ *   opponent node, by NumPy's choice(p=) rule (:432-433, :466-468).  Advantage rows (:445-460) are appended to adv_buf
+ *   and strategy rows (:470-479) to strat_buf (either may be NULL) in the reference's order: trajectories in index
+ *   order, a trajectory's advantage rows after the node's children returned, its strategy rows at the visit.
+ *   h_counts (may be NULL) [2]: advantage rows, strategy rows of the call.  Synchronises once (the row totals).
+ *   Decision nodes wider than 4 actions, action ids beyond Amax and more than 24 traverser nodes on a path are
+ *   OSG_ERR_UNSUPPORTED.
+ * osg_deep_cfr_staged: the rows of the last osg_deep_cfr_traverse in append order, with the per-trajectory offsets
+ *   [trajectories + 1] i64 into them and the draws each trajectory consumed [trajectories] i32 (device outputs, any
+ *   may be NULL); sizes (host, may be NULL) [5]: trajectories, advantage rows, strategy rows, and the exact upper
+ *   bounds of advantage / strategy rows per trajectory that sized the staging. */
+int osg_deep_cfr_traverse(osg_cfr* s, const float* d_advantages, int player, int iteration, uint64_t seed,
+                          int64_t first_trajectory, int64_t trajectories, osg_reservoir* adv_buf, osg_reservoir* strat_buf,
+                          int64_t* h_counts);
+int osg_deep_cfr_staged(osg_cfr* s, int64_t* sizes, int64_t* d_adv_offsets, int32_t* d_adv_info, float* d_adv_values,
+                        int64_t* d_strat_offsets, int32_t* d_strat_info, float* d_strat_values, int32_t* d_draws);
+
 /* ---- multi-GPU exchange step ---------------------------------------------------
  * One process per GPU.  Units shard by global index with no data-path collective; the ONE exchange
  * on the path is external-sampling MCCFR's all-reduce(sum) of the regret / average-policy delta

@@ -7,7 +7,8 @@ leduc_poker, random-rollout evaluation, MCTS, information-set MCTS and alpha-bet
 tabular CFR / Discounted CFR / external-sampling MCCFR / extensive-form fictitious play /
 magnetic mirror descent / extensive-form regret minimization, payoff tensors / policy aggregation / PSRO over populations of policies, and PSRO's
 meta-strategy solvers (projected replicator dynamics, regret matching) on batches of normal-form meta-games, and
-AlphaZero self-play (policy targets, moves, trajectories and a replay buffer on the device).
+AlphaZero self-play (policy targets, moves, trajectories and a replay buffer on the device), and Deep CFR (traversals,
+sampled advantages and reservoir buffers on the device; the networks are torch's).
 The C-ABI is include/osg_abi.h.
 """
 from ._abi import OsgError, describe, lib  # noqa: F401
@@ -47,6 +48,10 @@ def __getattr__(name):
     if name in ("SelfPlay", "ReplayBuffer", "TrainInput"):
         from . import alpha_zero
         return getattr(alpha_zero, name)
+    if name in ("DeepCFRSolver", "ReservoirBuffer", "deep_cfr"):   # (ReservoirBuffer: Deep CFR's; AlphaZero's ring is ReplayBuffer)
+        import importlib
+        module = importlib.import_module(".deep_cfr", __name__)
+        return module if name == "deep_cfr" else getattr(module, name)
     if name in ("BatchedEnvironment", "TimeStep", "StepType", "ObservationType"):
         from . import vector_env
         return getattr(vector_env, name)

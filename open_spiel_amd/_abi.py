@@ -263,6 +263,16 @@ SIGNATURES = {
     "osg_cfr_aggregate_policies": (INT, [VP, VP, INT, VP, C.c_double, INT, VP]),
     "osg_meta_solve": (INT, [VP, INT, VP, I64, VP, VP, I64, VP, VP, VP, INT]),
     "osg_alpharank": (INT, [VP, INT, VP, I64, VP, VP, I64, VP, VP, VP, VP, VP, INT]),
+    "osg_cfr_infostate_tensors": (INT, [VP, VP, INT]),
+    "osg_reservoir_create": (INT, [VP, INT, I64, U64, U64, C.POINTER(VP)]),
+    "osg_reservoir_destroy": (INT, [VP]),
+    "osg_reservoir_sizes": (INT, [VP, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
+    "osg_reservoir_clear": (INT, [VP]),
+    "osg_reservoir_append": (INT, [VP, I64, VP, C.c_int32, VP]),
+    "osg_reservoir_sample": (INT, [VP, U64, U64, I64, VP]),
+    "osg_reservoir_rows": (INT, [VP, VP, I64, VP, VP, VP]),
+    "osg_deep_cfr_traverse": (INT, [VP, VP, INT, INT, U64, I64, I64, VP, VP, VP]),
+    "osg_deep_cfr_staged": (INT, [VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "osg_cfr_infostate_key": (INT, [VP, I64, C.c_char_p, INT]),
     "osg_cfr_best_response_history_values": (INT, [VP, INT, VP, INT, VP]),
     "osg_cfr_tree_edges": (INT, [VP, VP, VP]),

@@ -12,6 +12,7 @@
 //   osg_cfr_xfp.hip     k_xfp_small, k_xfp_*          extensive-form fictitious play
 //   osg_cfr_mmd.hip     k_mmd_small, k_mmd_*          magnetic mirror descent (MmdState lives there)
 //   osg_cfr_efr.hip     k_efr_resident, k_efr_*       extensive-form regret minimization (osg_efr.h has the arithmetic)
+//   osg_deep_cfr.hip    k_dcfr_*, k_res_*             Deep CFR traversals and reservoir buffers (osg_deep_cfr.h has the arithmetic)
 //
 // Every kernel is launched from the translation unit that defines it; what crosses the units are the device-side
 // argument structs below (views: raw pointers), the per-family plans that own the memory behind them (SplitPlan,
@@ -543,6 +544,9 @@ struct osg_cfr {
   // magnetic mirror descent (osg_cfr_mmd.hip): built at the first osg_mmd_* call
   std::unique_ptr<MmdState> mmd;
   EfrPlan efr;
+  // Deep CFR (osg_deep_cfr.hip): the legal ids, the launch's strategy table and the staged rows of the last
+  // osg_deep_cfr_traverse, built at the first call (a DeepState; its deleter comes with the pointer)
+  std::shared_ptr<void> deep;
 
   Tree tree() const {
     Tree t;

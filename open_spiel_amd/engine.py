@@ -762,6 +762,54 @@ class TabularSolver:
         out.update(keys=keys, nact=nact, legal=legal)
         return out
 
+    def infostate_tensors(self, device=True):
+        """[I, info_size] float32: information_state_tensor(player of the infostate) of every infostate, in this
+        solver's infostate order (a torch tensor on the device, or a NumPy array)."""
+        E = _abi.describe(self.game_string).info_size
+        if device:
+            out = torch.empty((self.num_infostates, E), dtype=torch.float32, device=self.ctx.device)
+            check(lib().osg_cfr_infostate_tensors(self._h, out.data_ptr(), 0))
+            return out
+        out = np.zeros((self.num_infostates, E), np.float32)
+        check(lib().osg_cfr_infostate_tensors(self._h, out.ctypes.data, 1))
+        return out
+
+    def deep_cfr_traverse(self, advantages, player, iteration, seed, trajectories, first_trajectory=0,
+                          advantage_buffer=None, strategy_buffer=None):
+        """`trajectories` Deep CFR traversals for `player` (deep_cfr.py _traverse_game_tree) against `advantages`, an
+        [I, Amax] float32 device tensor of advantage-network outputs by action id.  The sampled advantages go to
+        advantage_buffer and the opponents' strategies to strategy_buffer (deep_cfr.ReservoirBuffer, or None) in the
+        reference's append order; the solver's own tables are not touched.  Returns (advantage rows, strategy rows)."""
+        want = (self.num_infostates, self.amax)
+        if (not isinstance(advantages, torch.Tensor) or advantages.dtype != torch.float32 or tuple(advantages.shape) != want
+                or not advantages.is_contiguous() or advantages.device != self.ctx.device):
+            raise OsgError(f"deep_cfr_traverse: expected a contiguous float32 tensor of shape {want} on {self.ctx.device}")
+        counts = (C.c_int64 * 2)()
+        check(lib().osg_deep_cfr_traverse(self._h, advantages.data_ptr(), int(player), int(iteration), int(seed),
+                                          int(first_trajectory), int(trajectories),
+                                          None if advantage_buffer is None else advantage_buffer._h,
+                                          None if strategy_buffer is None else strategy_buffer._h, counts))
+        return int(counts[0]), int(counts[1])
+
+    def deep_cfr_staged(self):
+        """The rows of the last deep_cfr_traverse in append order: a dict of device tensors adv_offsets / strat_offsets
+        [T + 1] int64, adv_info / strat_info [R] int32, adv_values / strat_values [R, Amax] float32, draws [T] int32, and
+        `bounds`, the most advantage / strategy rows one trajectory can append."""
+        sizes = (C.c_int64 * 5)()
+        check(lib().osg_deep_cfr_staged(self._h, sizes, None, None, None, None, None, None, None))
+        T, na, ns = int(sizes[0]), int(sizes[1]), int(sizes[2])
+        dev = self.ctx.device
+        out = dict(adv_offsets=torch.zeros(T + 1, dtype=torch.int64, device=dev), adv_info=torch.empty(na, dtype=torch.int32, device=dev),
+                   adv_values=torch.empty((na, self.amax), dtype=torch.float32, device=dev),
+                   strat_offsets=torch.zeros(T + 1, dtype=torch.int64, device=dev), strat_info=torch.empty(ns, dtype=torch.int32, device=dev),
+                   strat_values=torch.empty((ns, self.amax), dtype=torch.float32, device=dev),
+                   draws=torch.empty(T, dtype=torch.int32, device=dev))
+        check(lib().osg_deep_cfr_staged(self._h, None, *[out[k].data_ptr() for k in (
+            "adv_offsets", "adv_info", "adv_values", "strat_offsets", "strat_info", "strat_values", "draws")]))
+        self.ctx.synchronize()
+        out["bounds"] = (int(sizes[3]), int(sizes[4]))
+        return out
+
     def evaluate_policy(self, which="average", table=None):
         """NashConv / exploitability / expected returns / best-response values of a policy on the
         device (algorithms::NashConv, Exploitability, ExpectedReturns, TabularBestResponse).
