@@ -579,6 +579,13 @@ int osg_selfplay_staged(osg_selfplay* sp, int t, osg_batch* dst_states, float* d
                         float* d_root_value, int8_t* d_player, int32_t* d_length, int64_t* d_ply_counter);
 
 /* ---- tabular CFR family -------------------------------------------------- */
+/* osg_cfr_cfg.kernel (the field's comment below says what each one forces) */
+#define OSG_CFR_KERNEL_AUTO 0
+#define OSG_CFR_KERNEL_GENERAL 1
+#define OSG_CFR_KERNEL_GRID 2
+#define OSG_CFR_KERNEL_PATH 3
+#define OSG_CFR_KERNEL_SPLIT 4
+#define OSG_CFR_KERNEL_SUB 5
 typedef struct {
   int32_t alternating_updates;   /* CFRSolverBase ctor (cfr.h:190-196)            */
   int32_t linear_averaging;
@@ -592,17 +599,17 @@ typedef struct {
                                        protocol through osg_mccfr_sample / osg_mccfr_iterate        */
   double epsilon;                /* solver 2 only: OutcomeSamplingMCCFRSolver's exploration
                                     (outcome_sampling_mccfr.h:43 kDefaultEpsilon = 0.6)          */
-  int32_t kernel;                /* 0 auto; 1 force the general level-synchronous kernel (k_cfr)
-                                    even where the all-in-LDS small-tree kernel applies; 2 force the
-                                    full-grid phase kernels (auto for trees > 65536 histories); 3 force
-                                    the single-workgroup path kernel; 4 = auto's choice for trees that
-                                    start with their chance deals and split into <= #CUs subtrees of
-                                    <= 1024 histories (leduc_poker): one workgroup per deal subtree,
-                                    one grid barrier per player pass; 5 = auto's choice for the big
-                                    trees of that shape (3-player leduc_poker: 1.8 M histories): ONE
-                                    cooperative launch, a workgroup per deal subtree of up to 8192
-                                    histories, two grid barriers per player pass (alternating
-                                    updates only)                                                 */
+  int32_t kernel;                /* OSG_CFR_KERNEL_*: AUTO; GENERAL forces the general level-synchronous
+                                    kernel (k_cfr) even where the all-in-LDS small-tree kernel applies;
+                                    GRID forces the full-grid phase kernels (auto for trees > 65536
+                                    histories); PATH forces the single-workgroup path kernel; SPLIT =
+                                    auto's choice for trees that start with their chance deals and
+                                    split into <= #CUs subtrees of <= 1024 histories (leduc_poker): one
+                                    workgroup per deal subtree, one grid barrier per player pass; SUB =
+                                    auto's choice for the big trees of that shape (3-player
+                                    leduc_poker: 1.8 M histories): ONE cooperative launch, a workgroup
+                                    per deal subtree of up to 8192 histories, two grid barriers per
+                                    player pass (alternating updates only)                        */
   int32_t replicas;              /* 0 or 1: one solver.  B > 1: B independent solvers of the same
                                     game advanced together, one workgroup each (CFR family, trees
                                     that fit LDS); select one with osg_cfr_select_replica         */

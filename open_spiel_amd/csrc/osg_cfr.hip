@@ -497,33 +497,30 @@ int osg_cfr_iterate(osg_cfr* s, int iters) {
     double* base0 = s->replica_base(0);
     tb = Tables{base0, base0 + static_cast<size_t>(s->I) * s->A, base0 + 2 * static_cast<size_t>(s->I) * s->A};
   }
-  const unsigned grid_b = static_cast<unsigned>(s->B);
-  // Trees far beyond one workgroup: full-grid launches per phase (osg_cfr_cfg.kernel == 2 forces it).
-  const bool grid_path = s->path_kernel && s->B == 1 && (s->cfg.kernel == 2 || (s->cfg.kernel == 0 && s->H > 65536));
-  // Trees too big for one workgroup: the persistent cooperative launch with a workgroup per deal subtree where the
-  // tree has that shape (kernel == 5 forces it, 2 forces the per-phase launches), else a launch per phase.
-  const bool sub_path = s->sub.ok && (!s->dcfr || s->sub.dcfr_ok) && s->B == 1 && (s->cfg.kernel == 5 || (s->cfg.kernel == 0 && grid_path));
-  if (sub_path) return cfr_sub_iterate(s, tb, iters);     // osg_cfr_sub.hip
-  if (grid_path) return cfr_grid_iterate(s, tb, iters);   // osg_cfr_sub.hip
-  if (s->split.ok && (s->cfg.kernel == 0 || s->cfg.kernel == 4)) {
-    // one workgroup per deal subtree, one grid barrier per player pass (k_cfr_split)
-    const SmallTree stree = small_tree_of(s);
-    const SplitTree sp = split_tree_of(s);
-    const int passes = s->cfg.alternating_updates ? s->P : 1;
-    const int per_launch = std::max(1, (1 << 30) / std::max(1, passes * s->split.G));  // the arrival counter is 32 bits
-    const double* disc = nullptr;
-    if (int rc = cfr_discount_table(s, s->iteration, iters, &disc)) return rc;
-    for (int done = 0; done < iters; done += per_launch) {
-      const int rc = launch_split(s, stree, sp, tb, std::min(per_launch, iters - done), s->iteration + done, s->cfg, false,
-                                  disc ? disc + 3 * static_cast<size_t>(done) : nullptr);
-      if (rc) return rc;
+  switch (cfr_iterate_form(s)) {
+    case CfrForm::kSub: return cfr_sub_iterate(s, tb, iters);     // osg_cfr_sub.hip
+    case CfrForm::kGrid: return cfr_grid_iterate(s, tb, iters);   // osg_cfr_sub.hip
+    case CfrForm::kSplit: {
+      // one workgroup per deal subtree, one grid barrier per player pass (k_cfr_split)
+      const SmallTree stree = small_tree_of(s);
+      const SplitTree sp = split_tree_of(s);
+      const int passes = s->cfg.alternating_updates ? s->P : 1;
+      const int per_launch = std::max(1, (1 << 30) / std::max(1, passes * s->split.G));  // the arrival counter is 32 bits
+      const double* disc = nullptr;
+      if (int rc = cfr_discount_table(s, s->iteration, iters, &disc)) return rc;
+      for (int done = 0; done < iters; done += per_launch) {
+        const int rc = launch_split(s, stree, sp, tb, std::min(per_launch, iters - done), s->iteration + done, s->cfg, false,
+                                    disc ? disc + 3 * static_cast<size_t>(done) : nullptr);
+        if (rc) return rc;
+      }
+      OSG_HIP(hipGetLastError());
+      s->last_kernel = s->dcfr ? "k_cfr_split<dcfr>" : "k_cfr_split";
+      break;
     }
-    OSG_HIP(hipGetLastError());
-    s->iteration += iters;
-    s->last_kernel = s->dcfr ? "k_cfr_split<dcfr>" : "k_cfr_split";
-    return OSG_OK;
+    case CfrForm::kSmall:
+      if (int rc = cfr_small_iterate(s, tb, iters, static_cast<unsigned>(s->B))) return rc;   // osg_cfr_small.hip
+      break;
   }
-  if (int rc = cfr_small_iterate(s, tb, iters, grid_b)) return rc;   // osg_cfr_small.hip
   s->iteration += iters;
   return OSG_OK;
 }
@@ -544,18 +541,18 @@ int osg_cfr_br_iterate(osg_cfr* s, int iters) {
   Tables tb{s->regrets(), s->cum(), s->cur()};
   // every player's best response to the current policy (cfr_br.cc:55-68), then one regret / average-policy
   // pass per player against the others' best responses (cfr_br.cc:70-81) and ApplyRegretMatching
-  const bool jobs = s->jobs.ok && OSG_EVAL_JOBS_ENABLED();
-  const bool split = s->split.ok && s->split.br_ok && (s->cfg.kernel == 0 || s->cfg.kernel == 4);
-  if (!split && !jobs && eval_takes_the_grid(s) && s->path_kernel) {   // large trees (osg_cfr_sub.hip)
-    // the P passes in ONE persistent launch per iteration (kernel == 2 keeps a launch per phase: the cross-check)
-    if (s->sub.ok && s->sub.br_ok && s->cfg.kernel != 2) return cfr_sub_br_iterate(s, tb, ea, cfg, iters);
-    return cfr_grid_br_iterate(s, tb, ea, cfg, iters);
+  const EvalForm ef = eval_form(s);
+  const CfrForm form = cfr_br_iterate_form(s);
+  switch (form) {
+    case CfrForm::kSub: return cfr_sub_br_iterate(s, tb, ef, ea, cfg, iters);     // large trees (osg_cfr_sub.hip)
+    case CfrForm::kGrid: return cfr_grid_br_iterate(s, tb, ef, ea, cfg, iters);
+    default: break;   // kSplit, kSmall: the passes differ, the loop is one
   }
   const SmallTree stree = small_tree_of(s);
   const SplitTree sp = split_tree_of(s);
   for (int it = 0; it < iters; ++it) {
-    if (int rc = cfr_best_responses_to_current(s, ea, jobs)) return rc;   // osg_cfr_eval.hip
-    if (split) {
+    if (int rc = launch_policy_eval(s, ef, ea, s->cur(), false, nullptr, true)) return rc;   // osg_cfr_eval.hip
+    if (form == CfrForm::kSplit) {
       const int rc = launch_split(s, stree, sp, tb, 1, s->iteration, cfg, true);
       if (rc) return rc;
     } else {

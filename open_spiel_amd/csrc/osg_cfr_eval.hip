@@ -518,14 +518,12 @@ EvalJobs eval_jobs_of(const osg_cfr* s) {
   return ej;
 }
 
-// Trees beyond one workgroup's reach (and too large for the jobs) are evaluated with a launch per level and phase
-// (k_geval_*); OSG_EVAL_GRID=1 forces that form, 0 forbids it (the tests compare the three).
-bool eval_takes_the_grid(const osg_cfr* s) {
-  const char* e = getenv("OSG_EVAL_GRID");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  return s->H > 65536;
+static void record_eval_form(osg_cfr* s, EvalForm form) {
+  static const char* const kNames[] = {"k_policy_eval", "k_eval_jobs", "k_geval", "k_geval_persist"};   // in EvalForm's order
+  s->last_eval_form = form;
+  s->last_eval_kernel = kNames[static_cast<int>(form)];
 }
+
 // The plan of the large-tree evaluation, made at its first use: the infostates of every level, and — only where
 // OSG_EVAL_PERSIST=1 asks for the one persistent launch — the offsets on the device, the grid barrier and the grid.
 static int build_grid_eval_plan(osg_cfr* s, bool persist) {
@@ -561,7 +559,7 @@ static int build_grid_eval_plan(osg_cfr* s, bool persist) {
   return OSG_OK;
 }
 
-int launch_grid_eval(osg_cfr* s, const EvalArrays& ea, const double* src, bool from_cum, double* d_pol, bool only_br) {
+static int launch_grid_eval(osg_cfr* s, const EvalArrays& ea, const double* src, bool from_cum, double* d_pol, bool only_br) {
   hipStream_t st = s->ctx->stream;
   const Tree t = s->tree();
   const double* pol = src;
@@ -596,10 +594,10 @@ int launch_grid_eval(osg_cfr* s, const EvalArrays& ea, const double* src, bool f
     const void* kern = reinterpret_cast<const void*>(&k_geval_persist);
     if (plain) OSG_HIP(hipLaunchKernel(kern, dim3(static_cast<unsigned>(s->eval.grid)), dim3(kGEvalThreads), args, 0, st));
     else OSG_HIP(hipLaunchCooperativeKernel(kern, dim3(static_cast<unsigned>(s->eval.grid)), dim3(kGEvalThreads), args, 0, st));
-    s->last_eval_kernel = "k_geval_persist";
+    record_eval_form(s, EvalForm::kGridPersist);
     return OSG_OK;
   }
-  s->last_eval_kernel = "k_geval";
+  record_eval_form(s, EvalForm::kGrid);
   k_geval_cf<<<dim3(std::max(1u, mblocks)), dim3(256), 0, st>>>(t, ea, pol);
   for (int l = s->D - 1; l >= 0; --l) {
     const int n_infos = s->eval.level_off[l + 1] - s->eval.level_off[l];
@@ -610,11 +608,24 @@ int launch_grid_eval(osg_cfr* s, const EvalArrays& ea, const double* src, bool f
   OSG_HIP(hipGetLastError());
   return OSG_OK;
 }
-// OSG_EVAL_JOBS=0 keeps the one-workgroup evaluation (k_policy_eval) for trees that could take the jobs: the tests
-// compare the two.
-bool OSG_EVAL_JOBS_ENABLED() {
-  const char* e = getenv("OSG_EVAL_JOBS");
-  return !(e && e[0] == '0');
+
+int launch_policy_eval(osg_cfr* s, EvalForm form, const EvalArrays& ea, const double* src, bool from_cum, double* d_pol, bool only_br) {
+  hipStream_t st = s->ctx->stream;
+  switch (form) {
+    case EvalForm::kGrid:
+    case EvalForm::kGridPersist:   // (which of the two: OSG_EVAL_PERSIST's say, recorded there)
+      return launch_grid_eval(s, ea, src, from_cum, d_pol, only_br);
+    case EvalForm::kJobs:
+      // the tables never leave the device: the average policy is formed from the cumulative table inside the jobs
+      k_eval_jobs<<<dim3(s->jobs.J), dim3(s->jobs.threads), s->jobs.lds_bytes, st>>>(s->tree(), ea, eval_jobs_of(s), src, from_cum ? 0 : 1,
+                                                                                     only_br ? 1 : 0);
+      break;
+    case EvalForm::kOneWorkgroup:   // (one launch whatever is asked for)
+      k_policy_eval<<<dim3(1), dim3(level_threads(s)), 0, st>>>(s->tree(), ea, src, from_cum ? 1 : 0, d_pol);
+      break;
+  }
+  record_eval_form(s, form);
+  return OSG_OK;
 }
 
 // The jobs of k_eval_jobs: the cut of build_split (the first level with a node that is not a chance node); one
@@ -736,15 +747,6 @@ int build_eval_jobs(osg_cfr* s) {
   return OSG_OK;
 }
 
-// Every player's best response to the current policy (cfr_br.cc:55-68): the first half of a CFR-BR iteration.
-int cfr_best_responses_to_current(osg_cfr* s, const EvalArrays& ea, bool jobs) {
-  hipStream_t st = s->ctx->stream;
-  if (jobs) { k_eval_jobs<<<dim3(s->jobs.J), dim3(s->jobs.threads), s->jobs.lds_bytes, st>>>(s->tree(), ea, eval_jobs_of(s), s->cur(), 1, 1); s->last_eval_kernel = "k_eval_jobs"; }
-  else if (eval_takes_the_grid(s)) { if (int rc = launch_grid_eval(s, ea, s->cur(), false, nullptr, true)) return rc; }
-  else { k_policy_eval<<<dim3(1), dim3(level_threads(s)), 0, st>>>(s->tree(), ea, s->cur()); s->last_eval_kernel = "k_policy_eval"; }
-  return OSG_OK;
-}
-
 }  // namespace osg_cfr_impl
 
 extern "C" {
@@ -787,25 +789,10 @@ static int evaluate_policy_impl(osg_cfr* s, int which_policy, const double* h_po
     ea.keep = history_values_in_reach(s);
     ea.keep_r = keep_responder;
   }
-  if (s->jobs.ok && OSG_EVAL_JOBS_ENABLED()) {
-    // the tables never leave the device: the average policy is formed from the cumulative table inside the jobs
-    const double* src = which_policy == 0 ? s->cum() : which_policy == 1 ? s->cur() : d_pol;
-    if (which_policy == 2) OSG_HIP(hipMemcpyAsync(d_pol, h_policy, sizeof(double) * IA, hipMemcpyHostToDevice, st));
-    k_eval_jobs<<<dim3(s->jobs.J), dim3(s->jobs.threads), s->jobs.lds_bytes, st>>>(s->tree(), ea, eval_jobs_of(s), src,
-                                                                                   which_policy == 0 ? 0 : 1, 0);
-    s->last_eval_kernel = "k_eval_jobs";
-    OSG_HIP(hipGetLastError());
-  } else if (eval_takes_the_grid(s)) {
-    const double* src = which_policy == 0 ? s->cum() : which_policy == 1 ? s->cur() : d_pol;
-    if (which_policy == 2) OSG_HIP(hipMemcpyAsync(d_pol, h_policy, sizeof(double) * IA, hipMemcpyHostToDevice, st));
-    if (int rc = launch_grid_eval(s, ea, src, which_policy == 0, d_pol, false)) return rc;
-  } else {
-    const double* src = which_policy == 0 ? s->cum() : which_policy == 1 ? s->cur() : d_pol;
-    if (which_policy == 2) OSG_HIP(hipMemcpyAsync(d_pol, h_policy, sizeof(double) * IA, hipMemcpyHostToDevice, st));
-    k_policy_eval<<<dim3(1), dim3(level_threads(s)), 0, st>>>(s->tree(), ea, src, which_policy == 0 ? 1 : 0, d_pol);
-    s->last_eval_kernel = "k_policy_eval";
-    OSG_HIP(hipGetLastError());
-  }
+  const double* src = which_policy == 0 ? s->cum() : which_policy == 1 ? s->cur() : d_pol;
+  if (which_policy == 2) OSG_HIP(hipMemcpyAsync(d_pol, h_policy, sizeof(double) * IA, hipMemcpyHostToDevice, st));
+  if (int rc = launch_policy_eval(s, eval_form(s), ea, src, which_policy == 0, d_pol, false)) return rc;
+  OSG_HIP(hipGetLastError());
   if (h_history_values)
     OSG_HIP(hipMemcpyAsync(h_history_values, ea.keep, sizeof(double) * s->H, hipMemcpyDeviceToHost, st));
   OSG_HIP(hipStreamSynchronize(st));

@@ -46,6 +46,11 @@ constexpr double kMccfrInit = 0.000001;  // external_sampling_mccfr.h:59 kInitia
 
 enum NodeKind : uint8_t { kChanceNode = 0, kDecisionNode = 1, kTerminalNode = 2 };
 
+// The launch forms the choosers below struct osg_cfr pick.  Policy evaluation: k_policy_eval, k_eval_jobs, k_geval_*;
+// kGridPersist is never chosen: recorded where kGrid took its opt-in persistent launch (OSG_EVAL_PERSIST=1).
+enum class EvalForm { kOneWorkgroup, kJobs, kGrid, kGridPersist };
+enum class CfrForm { kSub, kGrid, kSplit, kSmall };   // k_cfr_sub, k_gcfr_*, k_cfr_split, one workgroup (k_cfr_small / k_cfr)
+
 struct Tree {  // device pointers
   int H, I, A, P, D;
   const int32_t* level_off;    // [D+1]
@@ -533,6 +538,7 @@ struct osg_cfr {
   std::vector<int32_t> info_level, mem_index;
   bool eval_ok = true;  // every infostate's members sit on one tree level
   EvalPlan eval;
+  EvalForm last_eval_form = EvalForm::kOneWorkgroup;   // launch_policy_eval's record; it names last_eval_kernel from it
   const char* last_eval_kernel = "";
   JobsPlan jobs;
   ResidentPlan resident;
@@ -618,6 +624,57 @@ inline int xfp_reach_in_reach(const osg_cfr* s, const std::string& who, double**
 inline double* member_reach_in_reach(const osg_cfr* s) { return s->d_reach; }
 inline double* history_values_in_reach(const osg_cfr* s) { return s->d_reach; }
 
+inline GridCfr grid_cfr_of(const osg_cfr* s, Tables tb) {   // (pol: the current policy; CFR-BR points it at its effective one)
+  const size_t M = s->mem.size();
+  GridCfr g;
+  g.t = s->tree(); g.path_off = s->d_path_off; g.path = s->d_path; g.meta = s->d_meta32;
+  g.info_player = s->d_info_player32; g.value = s->d_value; g.dreg = s->d_node_delta;
+  g.dpol = s->d_node_delta + M * s->A; g.skip = s->d_skip; g.tb = tb; g.M = static_cast<int>(M);
+  g.pol = tb.cur;
+  return g;
+}
+
+// ---- Which form serves a call (DESIGN.md section 6 has the table).  Both switches are read at every call. ----
+// Trees beyond one workgroup's reach (and too large for the jobs) are evaluated with a launch per level and phase
+// (k_geval_*); OSG_EVAL_GRID=1 forces that form, 0 forbids it (the tests compare the three).
+inline bool eval_grid_on(const osg_cfr* s) {
+  const char* e = getenv("OSG_EVAL_GRID");
+  if (e && e[0] == '0') return false;
+  if (e && e[0] == '1') return true;
+  return s->H > 65536;
+}
+// The evaluation, best responses and history values, the action values' responder pre-pass, CFR-BR: osg_cfr_cfg.kernel has
+// no say.  OSG_EVAL_JOBS=0 keeps the one-workgroup evaluation for trees that could take the jobs.
+inline EvalForm eval_form(const osg_cfr* s, bool jobs_allowed = true) {
+  const char* e = getenv("OSG_EVAL_JOBS");
+  if (jobs_allowed && s->jobs.ok && !(e && e[0] == '0')) return EvalForm::kJobs;
+  return eval_grid_on(s) ? EvalForm::kGrid : EvalForm::kOneWorkgroup;
+}
+// Fictitious play's best responses: GRID forces the launches per level and phase, GENERAL and PATH forbid the jobs.
+inline EvalForm eval_form_for_kernel_option(const osg_cfr* s) {
+  const int k = s->cfg.kernel;
+  return k == OSG_CFR_KERNEL_GRID ? EvalForm::kGrid : eval_form(s, k != OSG_CFR_KERNEL_GENERAL && k != OSG_CFR_KERNEL_PATH);
+}
+// The action values' own pass (k_qv_* per level, or k_qvalues_small): the jobs have no say.
+inline bool action_values_take_the_grid(const osg_cfr* s) { return s->cfg.kernel == OSG_CFR_KERNEL_GRID || eval_grid_on(s); }
+// osg_cfr_iterate.  Trees far beyond one workgroup: full-grid launches per phase (GRID forces them), or where the tree has
+// the shape the persistent cooperative launch with a workgroup per deal subtree (SUB forces it).
+inline CfrForm cfr_iterate_form(const osg_cfr* s) {
+  const int k = s->cfg.kernel;
+  const bool grid = s->path_kernel && s->B == 1 && (k == OSG_CFR_KERNEL_GRID || (k == OSG_CFR_KERNEL_AUTO && s->H > 65536));
+  const bool sub = s->sub.ok && (!s->dcfr || s->sub.dcfr_ok) && s->B == 1 && (k == OSG_CFR_KERNEL_SUB || (k == OSG_CFR_KERNEL_AUTO && grid));
+  if (sub || grid) return sub ? CfrForm::kSub : CfrForm::kGrid;
+  return s->split.ok && (k == OSG_CFR_KERNEL_AUTO || k == OSG_CFR_KERNEL_SPLIT) ? CfrForm::kSplit : CfrForm::kSmall;
+}
+// osg_cfr_br_iterate's passes.  Large trees (their best responses take the grid): the P passes in ONE persistent launch per
+// iteration (GRID keeps a launch per phase: the cross-check).
+inline CfrForm cfr_br_iterate_form(const osg_cfr* s) {
+  const int k = s->cfg.kernel;
+  if (s->split.ok && s->split.br_ok && (k == OSG_CFR_KERNEL_AUTO || k == OSG_CFR_KERNEL_SPLIT)) return CfrForm::kSplit;
+  if (eval_form(s) != EvalForm::kGrid || !s->path_kernel) return CfrForm::kSmall;
+  return s->sub.ok && s->sub.br_ok && k != OSG_CFR_KERNEL_GRID ? CfrForm::kSub : CfrForm::kGrid;
+}
+
 // ---- osg_cfr.hip ----
 int cfr_sub_error(const osg_cfr* s);   // a grid barrier timed out in an earlier launch: the solver refuses further work
 void discount_factors(double alpha, double beta, double gamma, int iteration, double out[3]);
@@ -636,15 +693,15 @@ int build_sub(osg_cfr* s);
 SubTree sub_tree_of(const osg_cfr* s);   // reads the OSG_CFR_SUB_* switches, at every call
 int cfr_sub_iterate(osg_cfr* s, Tables tb, int iters);      // k_cfr_sub
 int cfr_grid_iterate(osg_cfr* s, Tables tb, int iters);     // k_gcfr_*
-int cfr_grid_br_iterate(osg_cfr* s, Tables tb, const EvalArrays& ea, osg_cfr_cfg cfg, int iters);   // CFR-BR on large trees, a launch per phase
-int cfr_sub_br_iterate(osg_cfr* s, Tables tb, const EvalArrays& ea, osg_cfr_cfg cfg, int iters);    // CFR-BR on large trees, k_cfr_sub<., kBr>
+// CFR-BR on large trees: a launch per phase / k_cfr_sub<., kBr>; `ef`: the form of their best responses
+int cfr_grid_br_iterate(osg_cfr* s, Tables tb, EvalForm ef, const EvalArrays& ea, osg_cfr_cfg cfg, int iters);
+int cfr_sub_br_iterate(osg_cfr* s, Tables tb, EvalForm ef, const EvalArrays& ea, osg_cfr_cfg cfg, int iters);
 // ---- osg_cfr_eval.hip ----
 int build_eval_jobs(osg_cfr* s);
 EvalJobs eval_jobs_of(const osg_cfr* s);
-bool eval_takes_the_grid(const osg_cfr* s);
-bool OSG_EVAL_JOBS_ENABLED();
-int launch_grid_eval(osg_cfr* s, const EvalArrays& ea, const double* src, bool from_cum, double* d_pol, bool only_br);
-int cfr_best_responses_to_current(osg_cfr* s, const EvalArrays& ea, bool jobs);   // every player's best response (CFR-BR)
+// One evaluation's launches in the form given, no wait and no copy: of the policy `src`, or (from_cum) of the cumulative
+// table's normalisation; only_br: the best responses alone, for CFR-BR and fictitious play.  Sets last_eval_form.
+int launch_policy_eval(osg_cfr* s, EvalForm form, const EvalArrays& ea, const double* src, bool from_cum, double* d_pol, bool only_br);
 // ---- osg_cfr_mccfr.hip ----
 int build_resident_tree(osg_cfr* s);
 // ---- osg_cfr_mmd.hip ----

@@ -1094,7 +1094,7 @@ static int mccfr_sample_impl(osg_cfr* s, uint64_t seed, int64_t first_trajectory
   // Persistent workgroups: each flushes its LDS delta tables once, so fewer, longer-lived
   // groups mean fewer global atomics (256 CUs x 4 groups).
   if (blocks > 1024) blocks = 1024;
-  if (s->resident.ok && s->cfg.kernel != 1) {
+  if (s->resident.ok && s->cfg.kernel != OSG_CFR_KERNEL_GENERAL) {
     // As many workgroups per CU as the LDS footprint allows.  A footprint that only fits once (leduc:
     // 143 KB) gets one group per CU, sized to the batch — every CU busy, up to 1024 lanes each; small
     // footprints (kuhn) get several 256- or 1024-lane groups per CU.

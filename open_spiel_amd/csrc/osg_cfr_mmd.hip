@@ -269,7 +269,7 @@ MmdTree mmd_tree(const osg_cfr* s) {
 }
 
 size_t mmd_small_lds_bytes(const osg_cfr* s) { return sizeof(double) * (3 * static_cast<size_t>(s->I) * s->A + 2 * static_cast<size_t>(s->I)); }
-bool mmd_takes_the_resident_form(const osg_cfr* s) { return s->cfg.kernel == 0 && mmd_small_lds_bytes(s) <= kMmdLdsLimit; }
+bool mmd_takes_the_resident_form(const osg_cfr* s) { return s->cfg.kernel == OSG_CFR_KERNEL_AUTO && mmd_small_lds_bytes(s) <= kMmdLdsLimit; }
 
 // What every MMD entry point needs of the solver, whatever its mode.
 int mmd_refusal(const osg_cfr* s, const char* who) {

@@ -218,7 +218,7 @@ int osg_cfr_action_values(osg_cfr* s, int which_policy, const double* policy, in
   c.out.weighted = c.out.cf_q + IA;
   const Tree t = s->tree();
   auto blocks = [](size_t n) { return dim3(static_cast<unsigned>(std::max<size_t>((n + kQvThreads - 1) / kQvThreads, 1))); };
-  if (s->cfg.kernel == 2 || eval_takes_the_grid(s)) {
+  if (action_values_take_the_grid(s)) {
     k_qv_sigma<<<blocks(I), dim3(kQvThreads), 0, st>>>(t, c);
     k_qv_reach<<<blocks(M), dim3(kQvThreads), 0, st>>>(t, c);
     for (int l = s->D - 1; l >= 0; --l)

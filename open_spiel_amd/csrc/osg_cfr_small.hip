@@ -561,7 +561,7 @@ int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, unsigned grid_b) {
   const int threads = level_threads(s);
   const double* disc = nullptr;
   if (int rc = cfr_discount_table(s, s->iteration, iters, &disc)) return rc;
-  if (s->path_kernel && s->cfg.kernel != 1) {
+  if (s->path_kernel && s->cfg.kernel != OSG_CFR_KERNEL_GENERAL) {
     // Path-based kernel: no top-down reach pass; all-in-LDS when the tree is small enough.
     SmallTree st = small_tree_of(s);
     st.L0 = s->first_decision_level;

@@ -1239,9 +1239,9 @@ int cfr_sub_iterate(osg_cfr* s, Tables tb, int iters) { return cfr_sub_run(s, tb
 // evaluation's one sweep (k_geval_*: every player's best response to the current policy, cfr_br.cc:55-68) and ONE launch of
 // k_cfr_sub<., kBr> for the P passes (cfr_br.cc:70-81) — where cfr_grid_br_iterate below spends ~58 launches on them.
 // The same additions in the same order: tables bit-identical with the launch-per-phase form.
-int cfr_sub_br_iterate(osg_cfr* s, Tables tb, const EvalArrays& ea, osg_cfr_cfg cfg, int iters) {
+int cfr_sub_br_iterate(osg_cfr* s, Tables tb, EvalForm ef, const EvalArrays& ea, osg_cfr_cfg cfg, int iters) {
   for (int it = 0; it < iters; ++it) {
-    if (int rc = launch_grid_eval(s, ea, s->cur(), false, nullptr, true)) return rc;
+    if (int rc = launch_policy_eval(s, ef, ea, s->cur(), false, nullptr, true)) return rc;
     if (int rc = cfr_sub_run(s, tb, 1, s->eval.best, cfg)) return rc;
   }
   return OSG_OK;
@@ -1253,11 +1253,7 @@ int cfr_grid_iterate(osg_cfr* s, Tables tb, int iters) {
   const double* disc = nullptr;
   if (int rc = cfr_discount_table(s, s->iteration, iters, &disc)) return rc;
   const int M = static_cast<int>(s->mem.size());
-  GridCfr g;
-  g.t = s->tree(); g.path_off = s->d_path_off; g.path = s->d_path; g.meta = s->d_meta32;
-  g.info_player = s->d_info_player32; g.value = s->d_value; g.dreg = s->d_node_delta;
-  g.dpol = s->d_node_delta + static_cast<size_t>(M) * s->A; g.skip = s->d_skip; g.tb = tb; g.M = M;
-  g.pol = tb.cur;
+  const GridCfr g = grid_cfr_of(s, tb);
   hipStream_t st = s->ctx->stream;
   auto blocks = [](int n) { return dim3(static_cast<unsigned>((n + 255) / 256)); };
   k_gcfr_init_values<<<blocks(s->H), dim3(256), 0, st>>>(g);
@@ -1286,19 +1282,16 @@ int cfr_grid_iterate(osg_cfr* s, Tables tb, int iters) {
 // CFRBRSolver::EvaluateAndUpdatePolicy on large trees (3-player leduc: one workgroup walked a pass set in tens of
 // milliseconds): the evaluation's sweep leaves every infostate's best-response action, then each player's pass runs as the
 // launch-per-phase CFR pass (k_gcfr_*) on the effective policy — the same additions in the same order as k_cfr<., kBr>.
-int cfr_grid_br_iterate(osg_cfr* s, Tables tb, const EvalArrays& ea, osg_cfr_cfg cfg, int iters) {
+int cfr_grid_br_iterate(osg_cfr* s, Tables tb, EvalForm ef, const EvalArrays& ea, osg_cfr_cfg cfg, int iters) {
   const size_t M = s->mem.size();
   hipStream_t st = s->ctx->stream;
-  GridCfr g;
-  g.t = s->tree(); g.path_off = s->d_path_off; g.path = s->d_path; g.meta = s->d_meta32;
-  g.info_player = s->d_info_player32; g.value = s->d_value; g.dreg = s->d_node_delta;
-  g.dpol = s->d_node_delta + M * s->A; g.skip = s->d_skip; g.tb = tb; g.M = static_cast<int>(M);
+  GridCfr g = grid_cfr_of(s, tb);
   double* d_eff = eval_policy_slot(s);   // (the evaluation's policy scratch: [I, A], free here)
   g.pol = d_eff;
   auto blocks = [](int n) { return dim3(static_cast<unsigned>((n + 255) / 256)); };
   k_gcfr_init_values<<<blocks(s->H), dim3(256), 0, st>>>(g);
   for (int it = 0; it < iters; ++it) {
-    if (int rc = launch_grid_eval(s, ea, s->cur(), false, nullptr, true)) return rc;
+    if (int rc = launch_policy_eval(s, ef, ea, s->cur(), false, nullptr, true)) return rc;
     for (int upd = 0; upd < s->P; ++upd) {
       k_gcfr_effpol<<<blocks(s->I), dim3(256), 0, st>>>(g, upd, s->eval.best, d_eff);
       for (int l = s->D - 2; l >= 0; --l) {

@@ -142,24 +142,21 @@ size_t xfp_small_lds_bytes(const osg_cfr* s) {
 
 // The fused form takes what k_policy_eval would evaluate (no jobs, not the grid) when the resident arrays fit.
 bool xfp_takes_the_fused_form(const osg_cfr* s) {
-  return s->cfg.kernel == 0 && !(s->jobs.ok && OSG_EVAL_JOBS_ENABLED()) && !eval_takes_the_grid(s) &&
-         xfp_small_lds_bytes(s) <= kXfpLdsLimit;
+  return s->cfg.kernel == OSG_CFR_KERNEL_AUTO && eval_form(s) == EvalForm::kOneWorkgroup && xfp_small_lds_bytes(s) <= kXfpLdsLimit;
 }
 
-// Every player's best response to `cur`, left in d_best, by the form osg_cfr_cfg.kernel asks for: 2 the launches per
-// level and phase, 1 and 3 one workgroup, otherwise what osg_cfr_br_iterate picks.
-int xfp_best_responses(osg_cfr* s, const EvalArrays& ea) {
-  if (s->cfg.kernel == 2) return launch_grid_eval(s, ea, s->cur(), false, nullptr, true);
-  const bool jobs = s->jobs.ok && OSG_EVAL_JOBS_ENABLED() && s->cfg.kernel != 1 && s->cfg.kernel != 3;
-  return cfr_best_responses_to_current(s, ea, jobs);
+// Every player's best response to `cur`, left in d_best, by the form osg_cfr_cfg.kernel asks for.
+int xfp_respond_to_current(osg_cfr* s, const EvalArrays& ea) {
+  return launch_policy_eval(s, eval_form_for_kernel_option(s), ea, s->cur(), false, nullptr, true);
 }
 
-const char* xfp_general_name(const osg_cfr* s) {
-  const std::string eval = s->last_eval_kernel;
-  if (eval == "k_eval_jobs") return "k_xfp<k_eval_jobs>";
-  if (eval == "k_geval") return "k_xfp<k_geval>";
-  if (eval == "k_geval_persist") return "k_xfp<k_geval_persist>";
-  return "k_xfp<k_policy_eval>";
+const char* xfp_general_name(const osg_cfr* s) {   // (of the form xfp_respond_to_current just took)
+  switch (s->last_eval_form) {
+    case EvalForm::kJobs: return "k_xfp<k_eval_jobs>";
+    case EvalForm::kGrid: return "k_xfp<k_geval>";
+    case EvalForm::kGridPersist: return "k_xfp<k_geval_persist>";
+    default: return "k_xfp<k_policy_eval>";
+  }
 }
 
 void launch_reach(const osg_cfr* s, double* reach) {
@@ -230,7 +227,7 @@ int osg_xfp_iterate(osg_cfr* s, int iters) {
     return OSG_OK;
   }
   for (int it = 0; it < iters; ++it) {
-    if (int rc = xfp_best_responses(s, ea)) return rc;
+    if (int rc = xfp_respond_to_current(s, ea)) return rc;
     launch_reach(s, reach);
     ++s->iteration;
     launch_update(s, reach, xfp_alpha(s->iteration));
@@ -261,7 +258,7 @@ int osg_xfp_reaches(osg_cfr* s, const int32_t* h_best_index, double* h_avg_reach
   if (h_best_index) {
     if (int rc = xfp_upload_best(s, h_best_index, "osg_xfp_reaches")) return rc;
   } else {
-    if (int rc = xfp_best_responses(s, eval_arrays_of(s))) return rc;
+    if (int rc = xfp_respond_to_current(s, eval_arrays_of(s))) return rc;
   }
   launch_reach(s, reach);
   OSG_HIP(hipGetLastError());
