@@ -438,6 +438,17 @@ int osg_cfr_create(osg_ctx* ctx, const char* game_string, const osg_cfr_cfg* cfg
     if (e != hipSuccess) { osg_cfr_destroy(s); return set_error(OSG_ERR_NOMEM, hipGetErrorString(e)); }
     if (!index_fits) s->eval_ok = false;
   }
+  {  // the device, asked once: the planners and launches below and in the other units take it from the solver
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess) {
+      (void)hipGetLastError();
+      osg_cfr_destroy(s);
+      return set_error(OSG_ERR_HIP, "osg_cfr_create: device properties");
+    }
+    s->num_cus = prop.multiProcessorCount;
+    s->lds_optin_bytes = prop.sharedMemPerBlockOptin ? prop.sharedMemPerBlockOptin : prop.sharedMemPerBlock;
+    s->cooperative_launch = prop.cooperativeLaunch != 0;
+  }
   cfr_small_prepare(s);   // (the LDS caps of the one-workgroup kernels: osg_cfr_small.hip)
   if (s->B > 1 && !s->small_tree) {
     osg_cfr_destroy(s);

@@ -628,122 +628,30 @@ int launch_policy_eval(osg_cfr* s, EvalForm form, const EvalArrays& ea, const do
   return OSG_OK;
 }
 
-// The jobs of k_eval_jobs: the cut of build_split (the first level with a node that is not a chance node); one
-// expected-returns job per subtree; for every responder r the subtrees grouped into the connected components of "holds a
-// member history of the same infostate of r", one best-response job per component.  Trees of another shape, or with a
-// component that does not fit a workgroup's LDS, keep the one-workgroup kernel.
+// The jobs of k_eval_jobs (plan_eval_jobs, osg_cfr_plan.h) on the device.  Trees of another shape, or with a component
+// that does not fit a workgroup's LDS, keep the one-workgroup kernel.
 int build_eval_jobs(osg_cfr* s) {
   s->jobs.ok = false;
-  if (!s->eval_ok || s->H < 2000 || s->D >= 64 || s->P > 15) return OSG_OK;
-  const int P = s->P, A = s->A, D = s->D;
-  int L = 0;
-  for (; L < D; ++L) {
-    bool all_chance = true;
-    for (int h = s->level_off[L]; h < s->level_off[L + 1]; ++h) all_chance &= s->kind[h] == kChanceNode;
-    if (!all_chance) break;
-  }
-  if (L < 1 || L >= D - 1) return OSG_OK;
-  const int G = s->level_off[L + 1] - s->level_off[L], NT = s->level_off[L + 1];
-  if (G < 4 || G > 65536) return OSG_OK;
-  std::vector<int32_t> sub_of(s->H, -1), level_of(s->H, 0);
-  for (int l = 0; l < D; ++l)
-    for (int h = s->level_off[l]; h < s->level_off[l + 1]; ++h) level_of[h] = l;
-  for (int h = s->level_off[L]; h < s->H; ++h)
-    sub_of[h] = h < s->level_off[L + 1] ? h - s->level_off[L] : sub_of[s->parent[h]];
-  std::vector<std::vector<int32_t>> hist(G);
-  for (int h = s->level_off[L]; h < s->H; ++h) hist[sub_of[h]].push_back(h);  // ascending h = level-major
-  const int M = static_cast<int>(s->mem.size());
-  for (int m = 0; m < M; ++m)
-    if (sub_of[s->mem[m]] < 0) return OSG_OK;  // a decision node above the cut
-  // the groups of subtrees, kind by kind
-  std::vector<std::vector<int32_t>> groups;  // subtree lists
-  std::vector<int32_t> group_kind;
-  for (int g = 0; g < G; ++g) { groups.push_back({g}); group_kind.push_back(0); }
-  for (int r = 0; r < P; ++r) {
-    std::vector<int32_t> uf(G);
-    for (int g = 0; g < G; ++g) uf[g] = g;
-    auto find = [&](int x) { while (uf[x] != x) { uf[x] = uf[uf[x]]; x = uf[x]; } return x; };
-    for (int i = 0; i < s->I; ++i) {
-      if (s->info_player[i] != r) continue;
-      for (int m = s->mem_off[i] + 1; m < s->mem_off[i + 1]; ++m) {
-        const int a = find(sub_of[s->mem[s->mem_off[i]]]), b = find(sub_of[s->mem[m]]);
-        if (a != b) uf[std::max(a, b)] = std::min(a, b);
-      }
-    }
-    std::vector<int32_t> slot(G, -1);
-    for (int g = 0; g < G; ++g) {
-      const int root = find(g);
-      if (slot[root] < 0) { slot[root] = static_cast<int32_t>(groups.size()); groups.push_back({}); group_kind.push_back(1 + r); }
-      groups[slot[root]].push_back(g);
-    }
-  }
-  const int J = static_cast<int>(groups.size());
-  std::vector<int32_t> job(static_cast<size_t>(J) * 8, 0), jlevel(static_cast<size_t>(J) * (D + 1), 0), desc, fc, row, glob, ient, ment;
-  std::vector<int32_t> loc(s->H, -1), job_of_sub(G, -1);
-  size_t lds = sizeof(double) * 2 * P * NT;
-  int max_nodes = 0;
-  const size_t IA = static_cast<size_t>(s->I) * A;
-  for (int j = 0; j < J; ++j) {
-    const int kind = group_kind[j], r = kind - 1;
-    std::vector<int32_t> nodes;
-    for (int g : groups[j]) nodes.insert(nodes.end(), hist[g].begin(), hist[g].end());
-    std::sort(nodes.begin(), nodes.end());
-    const int nn = static_cast<int>(nodes.size());
-    for (int x = 0; x < nn; ++x) loc[nodes[x]] = x;
-    const int n0 = static_cast<int>(desc.size());
-    int at = 0;
-    for (int l = 0; l <= D; ++l) {
-      while (l < D && at < nn && level_of[nodes[at]] < l) ++at;
-      jlevel[static_cast<size_t>(j) * (D + 1) + l] = l == D ? nn : at;
-    }
-    for (int x = 0; x < nn; ++x) {
-      const int h = nodes[x];
-      desc.push_back(s->kind[h] | (s->nchild[h] << 2) | ((s->actor[h] + 1) << 10));
-      fc.push_back(s->kind[h] == kTerminalNode ? 0 : loc[s->first_child[h]]);
-      row.push_back(s->kind[h] == kDecisionNode ? s->info[h] * A : 0);
-      glob.push_back(h);
-    }
-    const int i0 = static_cast<int>(ient.size() / 4), m0 = static_cast<int>(ment.size() / 2);
-    int ni = 0, nm = 0;
-    if (kind != 0) {
-      for (int g : groups[j]) job_of_sub[g] = j;
-      for (int i = 0; i < s->I; ++i) {
-        if (s->info_player[i] != r || s->mem_off[i + 1] == s->mem_off[i]) continue;
-        if (job_of_sub[sub_of[s->mem[s->mem_off[i]]]] != j) continue;
-        ient.insert(ient.end(), {i, s->info_level[i], nm, s->mem_off[i + 1] - s->mem_off[i]});
-        ++ni;
-        for (int m = s->mem_off[i]; m < s->mem_off[i + 1]; ++m) {
-          ment.insert(ment.end(), {m, loc[s->mem[m]]});
-          ++nm;
-        }
-      }
-      for (int g : groups[j]) job_of_sub[g] = -1;
-    }
-    int32_t* jd = &job[static_cast<size_t>(j) * 8];
-    jd[0] = kind; jd[1] = n0; jd[2] = nn; jd[3] = i0; jd[4] = ni; jd[5] = m0; jd[6] = nm;
-    const size_t bytes = sizeof(double) * (IA + static_cast<size_t>(nn) * (kind == 0 ? P : 1) + nn + nm) +
-                         sizeof(int32_t) * (3 * static_cast<size_t>(nn) + nm + s->I);
-    lds = std::max(lds, bytes);
-    max_nodes = std::max(max_nodes, nn);
-  }
-  if (lds > 150 * 1024) return OSG_OK;
+  if (!s->eval_ok) return OSG_OK;
+  const JobsHostPlan hp = plan_eval_jobs(s->host_tree());
+  if (!hp.ok) return OSG_OK;
+  JobsPlan& jp = s->jobs;
   hipStream_t st = s->ctx->stream;
   int rc;
-  if ((rc = upload(job, s->jobs.job, st)) || (rc = upload(jlevel, s->jobs.level, st)) ||
-      (rc = upload(desc, s->jobs.desc, st)) || (rc = upload(fc, s->jobs.fc, st)) || (rc = upload(row, s->jobs.row, st)) ||
-      (rc = upload(glob, s->jobs.glob, st)) || (rc = upload(ient, s->jobs.info, st)) || (rc = upload(ment, s->jobs.mem, st)))
+  if ((rc = upload(hp.job, jp.job, st)) || (rc = upload(hp.level_off, jp.level, st)) ||
+      (rc = upload(hp.node_desc, jp.desc, st)) || (rc = upload(hp.node_fc, jp.fc, st)) || (rc = upload(hp.node_row, jp.row, st)) ||
+      (rc = upload(hp.node_glob, jp.glob, st)) || (rc = upload(hp.info_ent, jp.info, st)) || (rc = upload(hp.mem_ent, jp.mem, st)))
     return rc;
-  OSG_HIP(s->jobs.deal.alloc(static_cast<size_t>(2) * P * G));
-  OSG_HIP(s->jobs.ticket.alloc(4));
-  OSG_HIP(hipMemsetAsync(s->jobs.deal, 0, sizeof(double) * 2 * P * G, st));
-  OSG_HIP(hipMemsetAsync(s->jobs.ticket, 0, sizeof(unsigned int) * 4, st));
-  if (raise_lds_cap(reinterpret_cast<const void*>(&k_eval_jobs), static_cast<int>(lds)) != hipSuccess) {
+  OSG_HIP(jp.deal.alloc(static_cast<size_t>(2) * s->P * hp.G));
+  OSG_HIP(jp.ticket.alloc(4));
+  OSG_HIP(hipMemsetAsync(jp.deal, 0, sizeof(double) * 2 * s->P * hp.G, st));
+  OSG_HIP(hipMemsetAsync(jp.ticket, 0, sizeof(unsigned int) * 4, st));
+  if (raise_lds_cap(reinterpret_cast<const void*>(&k_eval_jobs), static_cast<int>(hp.lds_bytes)) != hipSuccess) {
     (void)hipGetLastError();
     return OSG_OK;
   }
-  s->jobs.J = J; s->jobs.L = L; s->jobs.G = G; s->jobs.NT = NT; s->jobs.lds_bytes = lds;
-  s->jobs.threads = std::max(64, std::min(1024, (max_nodes + 63) / 64 * 64));
-  s->jobs.ok = true;
+  jp.J = hp.J; jp.L = hp.L; jp.G = hp.G; jp.NT = hp.NT; jp.lds_bytes = hp.lds_bytes; jp.threads = hp.threads;
+  jp.ok = true;
   return OSG_OK;
 }
 

@@ -17,7 +17,14 @@
 // Every kernel is launched from the translation unit that defines it; what crosses the units are the device-side
 // argument structs below (views: raw pointers), the per-family plans that own the memory behind them (SplitPlan,
 // SubPlan, EvalPlan, JobsPlan, ResidentPlan: DeviceArray / PinnedArray of osg_device_buffer.h), struct osg_cfr, the one
-// function per family that forms a view from its plan, and the host functions declared at the end.  Reference files: cfr.{h,cc},
+// function per family that forms a view from its plan, and the host functions declared at the end.
+//
+// What a plan holds is worked out by the host-only planners of osg_cfr_plan.h (no HIP, no environment: they compile and
+// are tested without a device) from osg_cfr::host_tree(): plan_split feeds k_cfr_split, plan_sub and plan_sub_fold
+// k_cfr_sub, plan_eval_jobs k_eval_jobs, plan_resident the k_mccfr_resident* / k_os_mccfr_resident kernels, and
+// mccfr_launch_plan picks the MCCFR kernel and geometry of a mini-batch.  The build_* functions add what needs the device
+// (LDS caps, occupancy, uploads); the node kinds and the kernels' size limits the planners share live in that header too.
+// Reference files: cfr.{h,cc},
 // external_sampling_mccfr.{h,cc}, outcome_sampling_mccfr.cc, cfr_br.cc, expected_returns.cc, best_response.cc.
 #pragma once
 #include <algorithm>
@@ -32,6 +39,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "osg_cfr_plan.h"
 #include "osg_efr.h"
 #include "osg_internal.h"
 
@@ -39,12 +47,8 @@ using namespace osg;
 
 namespace osg_cfr_impl {
 
-constexpr int kMaxA = 4;        // widest decision node the MCCFR frame holds (kuhn 2, leduc 3)
 constexpr int kMaxPolicyRow = 8;  // widest policy row a thread regret-matches in registers (kuhn 2, leduc 3)
-constexpr int kMaxFrames = 24;  // traverser decision nodes on one path
 constexpr double kMccfrInit = 0.000001;  // external_sampling_mccfr.h:59 kInitialTableValues
-
-enum NodeKind : uint8_t { kChanceNode = 0, kDecisionNode = 1, kTerminalNode = 2 };
 
 // The launch forms the choosers below struct osg_cfr pick.  Policy evaluation: k_policy_eval, k_eval_jobs, k_geval_*;
 // kGridPersist is never chosen: recorded where kGrid took its opt-in persistent launch (OSG_EVAL_PERSIST=1).
@@ -149,8 +153,6 @@ OSG_D double load_through(const double* p) {      // agent scope: never served f
       reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
 }
 
-constexpr int kSplitMaxA = 4;       // widest policy row the split kernel folds
-constexpr int kSplitOwnerPath = 10;  // decision entries of a root path kept in registers
 constexpr int kSplitRec = 1 + kSplitMaxA;  // doubles per member and buffer: own reach, regret terms
 constexpr int kSplitChunk = 6;       // members whose records are requested together
 
@@ -248,20 +250,6 @@ OSG_D void store_through16(__amdgpu_buffer_rsrc_t r, unsigned int byte_off, osg_
 OSG_D osg_u4 load_through16(__amdgpu_buffer_rsrc_t r, unsigned int byte_off) {
   return __builtin_amdgcn_raw_buffer_load_b128(r, static_cast<int>(byte_off), 0, kCachePolicySc1);
 }
-// The member records of k_cfr_sub (round 5): 64 bytes per member — regret terms [4], average-policy terms [4] — written
-// by the member's thread as whole 16-byte pieces and fetched by the fold the same way (7 eight-byte stores and loads per
-// member before).  A record that carries no terms says so in its first word: a quiet NaN whose low word is 1 (the member
-// was pruned) or 2 + u (upper member u of the forest form: written once by the host, its terms are formed in the fold).
-constexpr unsigned int kSubFlagHi = 0x7FF80000u;
-constexpr int kSubRecDoubles = 8;
-constexpr int kSubBarWords = 16 + 16 * 64;   // grid barrier words: a cooperative grid of up to 1 024 workgroups
-
-constexpr int kSubThreads = 1024;
-constexpr int kSubKD = 4;            // decision histories per thread: ND <= 4096
-constexpr int kSubFoldInfos = 64;    // infostates a workgroup folds per round (one wavefront adds them up)
-constexpr int kSubFoldX = 2;         // member records a thread fetches per round: <= 2048 per round
-constexpr int kSubCodeChunks = 8;    // int4 chunks of path codes a member record holds at most (requested together)
-
 struct EvalArrays {
   const int32_t* path_off;   // [M+1]
   const int32_t* path;
@@ -364,9 +352,6 @@ OSG_HD uint64_t es_stream(int level, int b1, int b2) {
   return level == 0 ? 0u : (level == 1 ? 1u + static_cast<uint64_t>(b1) : 16u + 8u * static_cast<uint64_t>(b1) + static_cast<uint64_t>(b2));
 }
 
-// Where OSG_MCCFR_TREE is unset, the flat kernel's tree goes to global memory when that helps (round 6: 3.04e9 -> 4.23e9 trajectories/s at 16 x 2^20,
-// profiles/r06c_mccfr_tree_in_l2_ab.txt).
-constexpr bool kMccfrTreeGlobalDefault = true;
 struct ResidentTree {
   const uint2* rec;      // [H]
   const double* uret;    // [K, P] distinct Returns() vectors
@@ -542,7 +527,10 @@ struct osg_cfr {
   const char* last_eval_kernel = "";
   JobsPlan jobs;
   ResidentPlan resident;
+  // the context's device, asked once by osg_cfr_create: what every planner and launch sizes itself by
   int num_cus = 0;
+  size_t lds_optin_bytes = 0;   // dynamic LDS a workgroup may opt in to
+  bool cooperative_launch = false;
   // per-infostate action values (osg_cfr_qvalues.hip): the results of a call, allocated at the first one
   DeviceArray<double> d_qv_out;
   DeviceArray<int32_t> d_qv_best;
@@ -560,6 +548,15 @@ struct osg_cfr {
     t.level_off = d_level_off; t.parent = d_parent; t.first_child = d_first_child; t.kind = d_kind;
     t.nchild = d_nchild; t.aidx = d_aidx; t.actor = d_actor; t.info = d_info; t.edge_prob = d_edge_prob;
     t.term_ret = d_term_ret; t.mem_off = d_mem_off; t.mem = d_mem; t.nact = d_nact; t.info_player = d_info_player;
+    return t;
+  }
+  HostTree host_tree() const {   // what the planners of osg_cfr_plan.h read
+    HostTree t;
+    t.H = H; t.I = I; t.A = A; t.P = P; t.D = D; t.M = static_cast<int>(mem.size());
+    t.level_off = level_off.data(); t.parent = parent.data(); t.first_child = first_child.data(); t.kind = kind.data();
+    t.nchild = nchild.data(); t.aidx = aidx.data(); t.actor = actor.data(); t.info = info.data(); t.mem_off = mem_off.data();
+    t.mem = mem.data(); t.nact = nact.data(); t.info_player = info_player.data(); t.edge_prob = edge_prob.data();
+    t.term_ret = term_ret.data(); t.path_off = path_off.data(); t.path = path.data(); t.info_level = info_level.data();
     return t;
   }
   // Replicas: B independent solvers of the same tree (tables [B][5][I, A]); `selected` is the one the

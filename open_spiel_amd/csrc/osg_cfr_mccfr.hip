@@ -959,81 +959,20 @@ namespace osg_cfr_impl {
 // probabilities) and decides whether it fits one workgroup's LDS next to three [I, A] tables.
 int build_resident_tree(osg_cfr* s) {
   s->resident.ok = false;
-  if ((s->cfg.solver != 1 && s->cfg.solver != 2) || s->A < 1 || s->A > kMaxA) return OSG_OK;
-  if (s->H >= (1 << 24) || s->I >= (1 << 20)) return OSG_OK;
-  std::vector<uint64_t> rec(s->H);
-  std::vector<double> uret, uprob;
-  std::unordered_map<std::string, uint32_t> ret_id;
-  std::unordered_map<uint64_t, uint32_t> prob_id;
-  const int P = s->P;
-  // traverser frames one path can hold: decision nodes of one player from the root down
-  std::vector<uint8_t> own(static_cast<size_t>(s->H) * P, 0);
-  int max_frames = 0;
-  for (int h = 0; h < s->H; ++h) {
-    uint32_t x = s->kind[h] | (static_cast<uint32_t>(s->nchild[h]) << 2) |
-                 (static_cast<uint32_t>(s->actor[h] + 1) << 8);
-    uint32_t y = 0;
-    if (s->nchild[h] > 63 || s->actor[h] + 1 > 15) return OSG_OK;
-    if (s->kind[h] == kDecisionNode) x |= static_cast<uint32_t>(s->info[h]) << 12;
-    if (s->kind[h] == kTerminalNode) {
-      std::string key(reinterpret_cast<const char*>(&s->term_ret[static_cast<size_t>(h) * P]), sizeof(double) * P);
-      auto it = ret_id.find(key);
-      if (it == ret_id.end()) {
-        it = ret_id.emplace(key, static_cast<uint32_t>(ret_id.size())).first;
-        for (int p = 0; p < P; ++p) uret.push_back(s->term_ret[static_cast<size_t>(h) * P + p]);
-      }
-      y = it->second;
-    } else {
-      y = static_cast<uint32_t>(s->first_child[h]);
-    }
-    if (h > 0 && s->kind[s->parent[h]] == kChanceNode) {
-      uint64_t bits;
-      memcpy(&bits, &s->edge_prob[h], sizeof bits);
-      auto it = prob_id.find(bits);
-      if (it == prob_id.end()) {
-        if (prob_id.size() >= 256) return OSG_OK;
-        it = prob_id.emplace(bits, static_cast<uint32_t>(prob_id.size())).first;
-        uprob.push_back(s->edge_prob[h]);
-      }
-      y |= it->second << 24;
-    }
-    rec[h] = static_cast<uint64_t>(x) | (static_cast<uint64_t>(y) << 32);
-    if (h > 0) {
-      const int par = s->parent[h];
-      for (int p = 0; p < P; ++p) {
-        int d = own[static_cast<size_t>(par) * P + p] + (s->kind[par] == kDecisionNode && s->actor[par] == p ? 1 : 0);
-        if (d > 255) return OSG_OK;
-        own[static_cast<size_t>(h) * P + p] = static_cast<uint8_t>(d);
-        max_frames = std::max(max_frames, d);
-      }
-    }
-  }
-  if (max_frames > kMaxFrames) return OSG_OK;
-  // Chance nodes whose outcomes all have the same probability (every chance node of kuhn and leduc: 1 / cards left)
-  // say so in the field decision nodes use for their infostate id: index of that probability + 1, else 0.  The
-  // traversal then samples without reading the children's records.
-  for (int h = 0; h < s->H; ++h) {
-    if (s->kind[h] != kChanceNode || s->nchild[h] == 0) continue;
-    const uint32_t id0 = static_cast<uint32_t>(rec[s->first_child[h]] >> 56);
-    bool same = true;
-    for (int c = 1; c < s->nchild[h]; ++c) same &= static_cast<uint32_t>(rec[s->first_child[h] + c] >> 56) == id0;
-    if (same) rec[h] |= static_cast<uint64_t>(id0 + 1) << 12;
-  }
-  if (uprob.empty()) uprob.push_back(1.0);
-  s->resident.n_uret = static_cast<int>(uret.size() / std::max(P, 1));
-  s->resident.n_uprob = static_cast<int>(uprob.size());
-  const size_t IA = static_cast<size_t>(s->I) * s->A;
-  s->resident.lds_bytes = sizeof(double) * (3 * IA + uret.size() + uprob.size()) + sizeof(uint64_t) * s->H;
-  hipDeviceProp_t prop;
-  OSG_HIP(hipGetDeviceProperties(&prop, s->ctx->device));
-  s->num_cus = prop.multiProcessorCount;
-  if (s->resident.lds_bytes > static_cast<size_t>(prop.sharedMemPerBlockOptin ? prop.sharedMemPerBlockOptin
-                                                                              : prop.sharedMemPerBlock))
-    return OSG_OK;
+  // the general kernels' LDS delta tables (16 I A bytes, where that is at most 64 KB): the kernel osg_mccfr_sample
+  // launches for this solver when the resident form is refused or switched off
+  (void)raise_lds_cap(s->cfg.solver == 2 ? reinterpret_cast<const void*>(&k_os_mccfr<true>) : reinterpret_cast<const void*>(&k_mccfr<true>), 64 * 1024);
+  (void)hipGetLastError();
+  const ResidentHostPlan hp = plan_resident(s->host_tree(), s->cfg.solver);
+  if (!hp.ok) return OSG_OK;
+  ResidentPlan& rp = s->resident;
+  rp.n_uret = hp.n_uret; rp.n_uprob = hp.n_uprob; rp.lds_bytes = hp.lds_bytes;
+  if (hp.lds_bytes > s->lds_optin_bytes) return OSG_OK;
   hipStream_t st = s->ctx->stream;
   int rc;
-  if ((rc = upload(rec, s->resident.rec, st)) || (rc = upload(uret, s->resident.uret, st)) || (rc = upload(uprob, s->resident.uprob, st)))
+  if ((rc = upload(hp.rec, rp.rec, st)) || (rc = upload(hp.uret, rp.uret, st)) || (rc = upload(hp.uprob, rp.uprob, st)))
     return rc;
+  const int lds = static_cast<int>(hp.lds_bytes);
   const void* variants[] = {reinterpret_cast<const void*>(&k_mccfr_resident_flat<1>),
                             reinterpret_cast<const void*>(&k_mccfr_resident_flat<2>),
                             reinterpret_cast<const void*>(&k_mccfr_resident_flat<3>),
@@ -1042,7 +981,7 @@ int build_resident_tree(osg_cfr* s) {
                             reinterpret_cast<const void*>(&k_os_mccfr_resident<2>),
                             reinterpret_cast<const void*>(&k_os_mccfr_resident<3>),
                             reinterpret_cast<const void*>(&k_os_mccfr_resident<4>)};
-  if (raise_lds_cap(variants[(s->cfg.solver == 2 ? 4 : 0) + s->A - 1], static_cast<int>(s->resident.lds_bytes)) != hipSuccess) {
+  if (raise_lds_cap(variants[(s->cfg.solver == 2 ? 4 : 0) + s->A - 1], lds) != hipSuccess) {
     (void)hipGetLastError();
     return OSG_OK;
   }
@@ -1053,12 +992,11 @@ int build_resident_tree(osg_cfr* s) {
                                   reinterpret_cast<const void*>(&k_mccfr_resident<4, 1>),
                                   reinterpret_cast<const void*>(&k_mccfr_resident<4, 2>)};
   for (int level = 0; level < 2; ++level)
-    if (s->cfg.solver != 2 && s->A >= 2 &&
-        raise_lds_cap(split_variants[2 * (s->A - 1) + level], static_cast<int>(s->resident.lds_bytes)) != hipSuccess) {
+    if (s->cfg.solver != 2 && s->A >= 2 && raise_lds_cap(split_variants[2 * (s->A - 1) + level], lds) != hipSuccess) {
       (void)hipGetLastError();
       return OSG_OK;
     }
-  s->resident.ok = true;
+  rp.ok = true;
   return OSG_OK;
 }
 
@@ -1088,129 +1026,68 @@ static int mccfr_sample_impl(osg_cfr* s, uint64_t seed, int64_t first_trajectory
     if (slot >= 0) s->delta_clean[slot] = false;
   }
   if (trajectories == 0) return OSG_OK;
-  const size_t lds = sizeof(double) * 2 * IA;
-  const bool use_lds = lds <= 64 * 1024;
-  int64_t blocks = (trajectories + 255) / 256;
-  // Persistent workgroups: each flushes its LDS delta tables once, so fewer, longer-lived
-  // groups mean fewer global atomics (256 CUs x 4 groups).
-  if (blocks > 1024) blocks = 1024;
-  if (s->resident.ok && s->cfg.kernel != OSG_CFR_KERNEL_GENERAL) {
-    // As many workgroups per CU as the LDS footprint allows.  A footprint that only fits once (leduc:
-    // 143 KB) gets one group per CU, sized to the batch — every CU busy, up to 1024 lanes each; small
-    // footprints (kuhn) get several 256- or 1024-lane groups per CU.
-    int fit = static_cast<int>((160 * 1024) / std::max<size_t>(s->resident.lds_bytes, 1));
-    // Mini-batches that leave lanes idle (fewer lanes than one round of the chip even with the split) run the
-    // split form of the external-sampling kernel: 2 or 4 lanes per trajectory (OSG_MCCFR_SPLIT=0: never).
-    // OSG_MCCFR_SPLIT=0 / 1 / 2: at most that many traverser levels are spread over lanes (default 2)
-    static const int split_max = std::getenv("OSG_MCCFR_SPLIT") ? std::atoi(std::getenv("OSG_MCCFR_SPLIT")) : 2;
-    const int q = s->A <= 2 ? 2 : 4;
-    int split = 0;   // two levels while the lanes fit one round of the chip (2^14 trajectories: 31.4 us per step against 38.7
-                     // with one level; 2^13: 26.7 against 37.2), else one level under the same condition, else the flat kernel
-    if (s->cfg.solver != 2 && s->A >= 2) {
-      const int64_t round = static_cast<int64_t>(s->num_cus) * 1024;
-      if (split_max >= 2 && trajectories * q * q <= round) split = 2;
-      else if (split_max >= 1 && trajectories * q <= round) split = 1;
-    }
-    const int64_t sampled = trajectories;
-    if (split) trajectories *= split == 2 ? q * q : q;   // (the geometry below counts lanes)
-    // Where the flat kernel reads the tree from: when the staged problem allows one workgroup per CU only (leduc: 143 KB,
-    // 4 wavefronts per SIMD) but the tables alone would allow two (67 KB), the records can stay in global memory
-    // (9 457 x 8 B, read-only: L2-resident) and two 1024-lane workgroups share a CU.  OSG_MCCFR_TREE=global | lds.
-    size_t shmem_bytes = s->resident.lds_bytes;
-    int tree_global = 0;
-    {
-      static const char* where = std::getenv("OSG_MCCFR_TREE");
-      const size_t tables_only = s->resident.lds_bytes - sizeof(uint64_t) * s->H;
-      const bool helps = fit <= 1 && (160 * 1024) / std::max<size_t>(tables_only, 1) >= 2 &&
-                         trajectories >= static_cast<int64_t>(s->num_cus) * 2048;
-      const bool want = where ? std::strcmp(where, "global") == 0 : kMccfrTreeGlobalDefault;
-      if (want && helps && split == 0 && s->cfg.solver != 2) {
-        tree_global = 1;
-        shmem_bytes = tables_only;
-        fit = static_cast<int>((160 * 1024) / std::max<size_t>(tables_only, 1));
-      }
-    }
-    int threads, per_cu;
-    if (fit <= 1) {
-      const int64_t share = (trajectories + s->num_cus - 1) / std::max(s->num_cus, 1);
-      threads = static_cast<int>(std::min<int64_t>(1024, std::max<int64_t>(256, (share + 63) / 64 * 64)));
-      per_cu = 1;
-    } else {
-      threads = trajectories >= static_cast<int64_t>(s->num_cus) * 1024 ? 1024 : 256;
-      per_cu = std::max(1, std::min(fit, 2048 / threads));
-    }
-    int64_t groups = std::min<int64_t>((trajectories + threads - 1) / threads, static_cast<int64_t>(s->num_cus) * per_cu);
-    ResidentTree rt{reinterpret_cast<const uint2*>(s->resident.rec.get()), s->resident.uret, s->resident.uprob, s->resident.n_uret, s->resident.n_uprob, tree_global};
-    // OSG_MCCFR_STAMPS=1: phase stamps of workgroup 0 (tools/probe_mccfr_shard.py); the solver's own buffer
-    if (std::getenv("OSG_MCCFR_STAMPS") && !s->d_mccfr_stamps) OSG_HIP(s->d_mccfr_stamps.alloc(4));
-    unsigned long long* const d_stamps = s->d_mccfr_stamps;
-    const dim3 grid(static_cast<unsigned>(groups)), block(threads);
-    const size_t shmem = shmem_bytes;
-    with_int<1, 2, 3, 4>(s->A, [&](auto ka) {
-      constexpr int KA = decltype(ka)::value;
-      const auto resident = [&](auto sp) {   // (the split forms exist from two actions on)
-        if constexpr (KA >= 2)
-          k_mccfr_resident<KA, decltype(sp)::value><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(),
-                                                                                dreg, dpol, seed, first_trajectory, sampled, d_stamps);
-      };
-      if (s->cfg.solver == 2)
-        k_os_mccfr_resident<KA><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), dreg,
-                                                            dpol, seed, first_trajectory, sampled,
-                                                            s->cfg.epsilon);
-      else if (split == 1 && KA >= 2) resident(std::integral_constant<int, 1>{});
-      else if (split == 2 && KA >= 2) resident(std::integral_constant<int, 2>{});
-      else
-        k_mccfr_resident_flat<KA><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), dreg,
-                                                              dpol, seed, first_trajectory, sampled);
-      return OSG_OK;
-    });
-    OSG_HIP(hipGetLastError());
-    s->last_kernel = s->cfg.solver == 2 ? "k_os_mccfr_resident"
-                                        : (split == 2 && s->A >= 2 ? "k_mccfr_resident<split 2>"
-                                                                   : (split == 1 && s->A >= 2 ? "k_mccfr_resident<split 1>"
-                                                                                              : (tree_global ? "k_mccfr_resident_flat<tree in L2>" : "k_mccfr_resident_flat")));
-    if (d_stamps && s->cfg.solver != 2 && split != 0) {   // (the flat kernel writes no stamps)
-      unsigned long long h[4];
-      OSG_HIP(hipMemcpyAsync(h, d_stamps, sizeof h, hipMemcpyDeviceToHost, st));
-      OSG_HIP(hipStreamSynchronize(st));
-      fprintf(stderr, "k_mccfr_resident (%lld trajectories, %u x %d lanes; workgroup 0, us): staging %.2f  lane 0's trajectory %.2f  "
-                      "rest of the workgroup + flush %.2f\n", static_cast<long long>(sampled), grid.x, threads,
-              (h[1] - h[0]) / 100.0, (h[2] - h[1]) / 100.0, (h[3] - h[2]) / 100.0);
-    }
-    return OSG_OK;
-  }
-  if (s->cfg.solver == 2) {  // OutcomeSamplingMCCFRSolver
-    const double eps = s->cfg.epsilon;
-    if (use_lds) {
-      static bool os_attr_set = false;
-      if (!os_attr_set) {
-        (void)raise_lds_cap(reinterpret_cast<const void*>(&k_os_mccfr<true>), 64 * 1024);
-        os_attr_set = true;
-      }
-      k_os_mccfr<true><<<dim3(static_cast<unsigned>(blocks)), dim3(256), lds, st>>>(
-          s->tree(), s->regrets(), dreg, dpol, seed, first_trajectory, trajectories, eps);
-    } else {
-      k_os_mccfr<false><<<dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st>>>(
-          s->tree(), s->regrets(), dreg, dpol, seed, first_trajectory, trajectories, eps);
-    }
-    OSG_HIP(hipGetLastError());
-    return OSG_OK;
-  }
-  if (use_lds) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)raise_lds_cap(reinterpret_cast<const void*>(&k_mccfr<true>), 64 * 1024);
-      attr_set = true;
-    }
-    k_mccfr<true><<<dim3(static_cast<unsigned>(blocks)), dim3(256), lds, st>>>(s->tree(), s->regrets(), dreg,
-                                                                                dpol, seed, first_trajectory,
-                                                                                trajectories);
-  } else {
-    k_mccfr<false><<<dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st>>>(s->tree(), s->regrets(), dreg,
-                                                                               dpol, seed, first_trajectory,
-                                                                               trajectories);
+  // OSG_MCCFR_SPLIT=0 / 1 / 2: at most that many traverser levels are spread over lanes (default 2);
+  // OSG_MCCFR_TREE=global | lds: where the flat kernel reads the tree from.  Both are read once per process.
+  static const int split_max = std::getenv("OSG_MCCFR_SPLIT") ? std::atoi(std::getenv("OSG_MCCFR_SPLIT")) : 2;
+  static const char* where = std::getenv("OSG_MCCFR_TREE");
+  MccfrLaunchInput in;
+  in.solver = s->cfg.solver; in.A = s->A; in.P = s->P; in.H = s->H; in.IA = static_cast<size_t>(IA);
+  in.resident_ok = s->resident.ok; in.resident_lds_bytes = s->resident.lds_bytes;
+  in.general_kernel = s->cfg.kernel == OSG_CFR_KERNEL_GENERAL;
+  in.cus = s->num_cus; in.trajectories = trajectories; in.split_max = split_max;
+  in.tree_where = !where ? MccfrTreeWhere::kUnset : (std::strcmp(where, "global") == 0 ? MccfrTreeWhere::kGlobal : MccfrTreeWhere::kLds);
+  const MccfrLaunchPlan lp = mccfr_launch_plan(in);
+  const dim3 grid(static_cast<unsigned>(lp.groups)), block(lp.threads);
+  const size_t shmem = lp.shmem_bytes;
+  const ResidentTree rt{reinterpret_cast<const uint2*>(s->resident.rec.get()), s->resident.uret, s->resident.uprob, s->resident.n_uret, s->resident.n_uprob, lp.tree_global ? 1 : 0};
+  // OSG_MCCFR_STAMPS=1: phase stamps of workgroup 0 (tools/probe_mccfr_shard.py); the solver's own buffer
+  const bool resident = lp.form != MccfrForm::kGeneralEs && lp.form != MccfrForm::kGeneralOs;
+  if (resident && std::getenv("OSG_MCCFR_STAMPS") && !s->d_mccfr_stamps) OSG_HIP(s->d_mccfr_stamps.alloc(4));
+  unsigned long long* const d_stamps = s->d_mccfr_stamps;
+  switch (lp.form) {
+    case MccfrForm::kGeneralEs:
+      if (shmem) k_mccfr<true><<<grid, block, shmem, st>>>(s->tree(), s->regrets(), dreg, dpol, seed, first_trajectory, trajectories);
+      else k_mccfr<false><<<grid, block, 0, st>>>(s->tree(), s->regrets(), dreg, dpol, seed, first_trajectory, trajectories);
+      break;
+    case MccfrForm::kGeneralOs:   // OutcomeSamplingMCCFRSolver
+      if (shmem) k_os_mccfr<true><<<grid, block, shmem, st>>>(s->tree(), s->regrets(), dreg, dpol, seed, first_trajectory, trajectories, s->cfg.epsilon);
+      else k_os_mccfr<false><<<grid, block, 0, st>>>(s->tree(), s->regrets(), dreg, dpol, seed, first_trajectory, trajectories, s->cfg.epsilon);
+      break;
+    case MccfrForm::kResidentOs:
+      with_int<1, 2, 3, 4>(s->A, [&](auto ka) {
+        k_os_mccfr_resident<decltype(ka)::value><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), dreg, dpol, seed,
+                                                                            first_trajectory, trajectories, s->cfg.epsilon);
+        return OSG_OK;
+      });
+      break;
+    case MccfrForm::kResidentSplit1:
+    case MccfrForm::kResidentSplit2:
+      with_int<2, 3, 4>(s->A, [&](auto ka) {   // (the split forms exist from two actions on)
+        constexpr int KA = decltype(ka)::value;
+        if (lp.split == 1) k_mccfr_resident<KA, 1><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), dreg, dpol, seed, first_trajectory, trajectories, d_stamps);
+        else k_mccfr_resident<KA, 2><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), dreg, dpol, seed, first_trajectory, trajectories, d_stamps);
+        return OSG_OK;
+      });
+      break;
+    case MccfrForm::kResidentFlat:
+    case MccfrForm::kResidentFlatTreeInL2:
+      with_int<1, 2, 3, 4>(s->A, [&](auto ka) {
+        k_mccfr_resident_flat<decltype(ka)::value><<<grid, block, shmem, st>>>(s->H, s->I, s->P, rt, s->d_nact, s->regrets(), dreg, dpol, seed,
+                                                                              first_trajectory, trajectories);
+        return OSG_OK;
+      });
+      break;
   }
   OSG_HIP(hipGetLastError());
+  if (lp.last_kernel) s->last_kernel = lp.last_kernel;
+  if (d_stamps && lp.split != 0) {   // (the flat kernel writes no stamps)
+    unsigned long long h[4];
+    OSG_HIP(hipMemcpyAsync(h, d_stamps, sizeof h, hipMemcpyDeviceToHost, st));
+    OSG_HIP(hipStreamSynchronize(st));
+    fprintf(stderr, "k_mccfr_resident (%lld trajectories, %u x %d lanes; workgroup 0, us): staging %.2f  lane 0's trajectory %.2f  "
+                    "rest of the workgroup + flush %.2f\n", static_cast<long long>(trajectories), grid.x, lp.threads,
+            (h[1] - h[0]) / 100.0, (h[2] - h[1]) / 100.0, (h[3] - h[2]) / 100.0);
+  }
   return OSG_OK;
 }
 

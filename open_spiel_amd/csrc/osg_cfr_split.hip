@@ -333,109 +333,38 @@ namespace osg_cfr_impl {
 int build_split(osg_cfr* s) {
   s->split.ok = false;
   if (s->cfg.solver != 0 || s->B != 1 || !s->path_kernel || s->A > kSplitMaxA || s->P + 1 > kMaxPlayers + 1) return OSG_OK;
-  if (s->H < 2000 || s->D >= 64) return OSG_OK;
-  // the cut: the first level that holds a node which is not a chance node
-  int L = 0;
-  for (; L < s->D; ++L) {
-    bool all_chance = true;
-    for (int h = s->level_off[L]; h < s->level_off[L + 1]; ++h) all_chance &= s->kind[h] == kChanceNode;
-    if (!all_chance) break;
-  }
-  if (L < 1 || L >= s->D - 1) return OSG_OK;
-  const int G = s->level_off[L + 1] - s->level_off[L];
-  hipDeviceProp_t prop;
-  OSG_HIP(hipGetDeviceProperties(&prop, s->ctx->device));
-  if (G < 8 || G > prop.multiProcessorCount) return OSG_OK;
-  // a subtree's histories, level by level: the descendants of a level-L node are a contiguous range on every level
-  std::vector<std::vector<int32_t>> hist(G);
-  std::vector<int32_t> sub_of(s->H, -1), loc_of(s->H, -1), level_of(s->H, 0);
-  for (int l = 0; l < s->D; ++l)
-    for (int h = s->level_off[l]; h < s->level_off[l + 1]; ++h) level_of[h] = l;
-  for (int g = 0; g < G; ++g) sub_of[s->level_off[L] + g] = g;
-  for (int h = s->level_off[L]; h < s->H; ++h) {
-    if (h >= s->level_off[L + 1]) sub_of[h] = sub_of[s->parent[h]];
-    const int g = sub_of[h];
-    loc_of[h] = static_cast<int32_t>(hist[g].size());
-    hist[g].push_back(h);
-  }
-  int NL = 0;
-  for (int g = 0; g < G; ++g) NL = std::max<int>(NL, static_cast<int>(hist[g].size()));
-  if (NL > 1024) return OSG_OK;
-  const int threads = std::max(64, (NL + 63) / 64 * 64);
-  std::vector<std::vector<int32_t>> mem_m(G), infos(G);
-  std::vector<int32_t> seen(s->I, -1);
-  for (int i = 0; i < s->I; ++i)
-    for (int m = s->mem_off[i]; m < s->mem_off[i + 1]; ++m) {
-      const int h = s->mem[m];
-      if (sub_of[h] < 0) return OSG_OK;  // a decision node above the cut
-      int decisions = 0;
-      for (int e = s->path_off[m]; e < s->path_off[m + 1]; ++e) decisions += ((s->path[e] >> 23) & 1) ? 0 : 1;
-      if (decisions > kSplitOwnerPath) return OSG_OK;
-      mem_m[sub_of[h]].push_back(m);
-      if (seen[i] != sub_of[h]) {  // members of one infostate inside one subtree are adjacent in DFS order or not: check all
-        bool have = false;
-        for (int32_t x : infos[sub_of[h]]) have |= x == i;
-        if (!have) infos[sub_of[h]].push_back(i);
-        seen[i] = sub_of[h];
-      }
-    }
-  int NM = 1, NI = 1;
-  for (int g = 0; g < G; ++g) {
-    NM = std::max<int>(NM, static_cast<int>(mem_m[g].size()));
-    NI = std::max<int>(NI, static_cast<int>(infos[g].size()));
-  }
-  if (NM > threads || NI > threads) return OSG_OK;
-  const size_t IA = static_cast<size_t>(s->I) * s->A;
-  const size_t lds = sizeof(double) * (static_cast<size_t>(NL) * s->P + NL + 3 * IA) + 16;
-  if (lds > 150 * 1024) return OSG_OK;
-  std::vector<int32_t> nloc(G), desc(static_cast<size_t>(G) * NL, kTerminalNode), fc(static_cast<size_t>(G) * NL, 0),
-      row(static_cast<size_t>(G) * NL, 0), glob(static_cast<size_t>(G) * NL, 0), mm(static_cast<size_t>(G) * NM, -1),
-      mh(static_cast<size_t>(G) * NM, 0), il(static_cast<size_t>(G) * NI, -1);
-  for (int g = 0; g < G; ++g) {
-    nloc[g] = static_cast<int32_t>(hist[g].size());
-    for (size_t j = 0; j < hist[g].size(); ++j) {
-      const int h = hist[g][j];
-      const size_t at = static_cast<size_t>(g) * NL + j;
-      desc[at] = s->kind[h] | (s->nchild[h] << 2) | (level_of[h] << 10) | ((s->actor[h] + 1) << 16);
-      fc[at] = s->kind[h] == kTerminalNode ? 0 : loc_of[s->first_child[h]];
-      row[at] = s->kind[h] == kDecisionNode ? s->info[h] * s->A : 0;
-      glob[at] = h;
-    }
-    for (size_t k = 0; k < mem_m[g].size(); ++k) {
-      mm[static_cast<size_t>(g) * NM + k] = mem_m[g][k];
-      mh[static_cast<size_t>(g) * NM + k] = loc_of[s->mem[mem_m[g][k]]];
-    }
-    for (size_t k = 0; k < infos[g].size(); ++k) il[static_cast<size_t>(g) * NI + k] = infos[g][k];
-  }
+  const SplitHostPlan hp = plan_split(s->host_tree(), SplitLimits{s->num_cus});
+  if (!hp.ok) return OSG_OK;
+  SplitPlan& sp = s->split;
   hipStream_t st = s->ctx->stream;
   int rc;
-  if ((rc = upload(nloc, s->split.nloc, st)) || (rc = upload(desc, s->split.desc, st)) ||
-      (rc = upload(fc, s->split.fc, st)) || (rc = upload(row, s->split.row, st)) ||
-      (rc = upload(glob, s->split.glob, st)) || (rc = upload(mm, s->split.mem_m, st)) ||
-      (rc = upload(mh, s->split.mem_hloc, st)) || (rc = upload(il, s->split.info, st)))
+  if ((rc = upload(hp.nloc, sp.nloc, st)) || (rc = upload(hp.desc, sp.desc, st)) ||
+      (rc = upload(hp.fc, sp.fc, st)) || (rc = upload(hp.row, sp.row, st)) ||
+      (rc = upload(hp.glob, sp.glob, st)) || (rc = upload(hp.mem_m, sp.mem_m, st)) ||
+      (rc = upload(hp.mem_hloc, sp.mem_hloc, st)) || (rc = upload(hp.info_list, sp.info, st)))
     return rc;
   const size_t M = s->mem.size();
-  OSG_HIP(s->split.terms.alloc(2 * kSplitRec * std::max<size_t>(M, 1)));
-  OSG_HIP(s->split.bar.alloc(4));
-  OSG_HIP(hipMemsetAsync(s->split.bar, 0, sizeof(unsigned int) * 4, st));
-  OSG_HIP(hipMemsetAsync(s->split.terms, 0, sizeof(double) * 2 * kSplitRec * std::max<size_t>(M, 1), st));
-  if (raise_lds_cap(split_kernel(s->P, false, threads), static_cast<int>(lds)) != hipSuccess ||
-      raise_lds_cap(split_kernel(s->P, false, threads, s->A, true), static_cast<int>(lds)) != hipSuccess ||
-      raise_lds_cap(split_kernel(s->P, false, threads, 0, false, true), static_cast<int>(lds)) != hipSuccess ||
-      raise_lds_cap(split_kernel(s->P, false, threads, s->A, true, true), static_cast<int>(lds)) != hipSuccess) {
+  OSG_HIP(sp.terms.alloc(2 * kSplitRec * std::max<size_t>(M, 1)));
+  OSG_HIP(sp.bar.alloc(4));
+  OSG_HIP(hipMemsetAsync(sp.bar, 0, sizeof(unsigned int) * 4, st));
+  OSG_HIP(hipMemsetAsync(sp.terms, 0, sizeof(double) * 2 * kSplitRec * std::max<size_t>(M, 1), st));
+  const int lds = static_cast<int>(hp.lds_bytes), br_lds = static_cast<int>(hp.br_lds_bytes);
+  if (raise_lds_cap(split_kernel(s->P, false, hp.threads), lds) != hipSuccess ||
+      raise_lds_cap(split_kernel(s->P, false, hp.threads, s->A, true), lds) != hipSuccess ||
+      raise_lds_cap(split_kernel(s->P, false, hp.threads, 0, false, true), lds) != hipSuccess ||
+      raise_lds_cap(split_kernel(s->P, false, hp.threads, s->A, true, true), lds) != hipSuccess) {
     (void)hipGetLastError();
     return OSG_OK;
   }
-  // the CFR-BR pass set keeps one more [I, A] array (the effective policy)
-  s->split.br_ok = lds + sizeof(double) * IA <= 158 * 1024;
-  if (s->split.br_ok && (raise_lds_cap(split_kernel(s->P, true, threads), static_cast<int>(lds + sizeof(double) * IA)) != hipSuccess ||
-                         raise_lds_cap(split_kernel(s->P, true, threads, s->A, true), static_cast<int>(lds + sizeof(double) * IA)) != hipSuccess)) {
+  sp.br_ok = hp.br_lds_bytes <= 158 * 1024;
+  if (sp.br_ok && (raise_lds_cap(split_kernel(s->P, true, hp.threads), br_lds) != hipSuccess ||
+                   raise_lds_cap(split_kernel(s->P, true, hp.threads, s->A, true), br_lds) != hipSuccess)) {
     (void)hipGetLastError();
-    s->split.br_ok = false;
+    sp.br_ok = false;
   }
-  s->split.G = G; s->split.L = L; s->split.NL = NL; s->split.NM = NM; s->split.NI = NI; s->split.threads = threads;
-  s->split.lds_bytes = lds;
-  s->split.ok = true;
+  sp.G = hp.G; sp.L = hp.L; sp.NL = hp.NL; sp.NM = hp.NM; sp.NI = hp.NI; sp.threads = hp.threads;
+  sp.lds_bytes = hp.lds_bytes;
+  sp.ok = true;
   return OSG_OK;
 }
 

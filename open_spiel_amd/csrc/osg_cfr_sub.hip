@@ -725,420 +725,87 @@ k_cfr_sub(Tree t, SmallTree st, SubTree sp, Tables tb, int iters, int iteration0
 
 namespace osg_cfr_impl {
 
-// The subtrees of k_cfr_sub: the same cut as build_split (the first level with a node that is not a chance node),
-// any number of subtrees (a workgroup takes several in turn when the cooperative grid is smaller), up to 8 x 1024
-// histories each.  Round 5, forest form: with more subtrees than compute units the bins of the workgroups are packed —
-// whole subtrees if they fit, else the pieces one level below the cut (SubTree's comment) — so that every workgroup
-// sweeps one bin per pass.  OSG_CFR_SUB_PACK=0 keeps a subtree per bin.
+// The bins of k_cfr_sub on the device: plan_sub and plan_sub_fold (osg_cfr_plan.h) work them out on the host tree; here
+// the LDS caps, the occupancy of the three forms of the kernel, the uploads.  OSG_CFR_SUB_PACK=0 keeps a subtree per bin.
 template <int kK, bool kBr = false, bool kDcfr = false> const void* cfr_sub_kernel() { return reinterpret_cast<const void*>(&k_cfr_sub<kK, kBr, kDcfr>); }
 const void* cfr_sub_kernel_of(int K, bool br, bool dcfr = false) {
   if (dcfr) return K == 2 ? cfr_sub_kernel<2, false, true>() : (K == 4 ? cfr_sub_kernel<4, false, true>() : cfr_sub_kernel<8, false, true>());   // (never with br)
   if (br) return K == 2 ? cfr_sub_kernel<2, true>() : (K == 4 ? cfr_sub_kernel<4, true>() : cfr_sub_kernel<8, true>());
   return K == 2 ? cfr_sub_kernel<2>() : (K == 4 ? cfr_sub_kernel<4>() : cfr_sub_kernel<8>());
 }
+// Raises the LDS cap of k_cfr_sub<K, br, dcfr> and asks how many of its workgroups a CU holds (0: it cannot run).
+static int cfr_sub_blocks_per_cu(int K, bool br, bool dcfr, size_t lds) {
+  const void* kern = cfr_sub_kernel_of(K, br, dcfr);
+  int per_cu = 0;
+  if (raise_lds_cap(kern, static_cast<int>(lds)) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kSubThreads, lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return per_cu;
+}
+static void print_sub_stats(const SubHostPlan& hp, int P) {   // how even the bins are: histories, levels and members per player
+  const int G = hp.G;
+  for (int q = -1; q < P; ++q) {
+    int64_t lo = INT64_MAX, hi = 0, sum = 0;
+    for (int g = 0; g < G; ++g) {
+      const int64_t v = q < 0 ? hp.bin_histories[g] : hp.bin_members[static_cast<size_t>(g) * P + q];
+      lo = std::min(lo, v); hi = std::max(hi, v); sum += v;
+    }
+    fprintf(stderr, "k_cfr_sub bins: %s min %lld mean %.1f max %lld over %d bins\n", q < 0 ? "histories" : (q == 0 ? "members p0" : (q == 1 ? "members p1" : "members p2+")),
+            static_cast<long long>(lo), static_cast<double>(sum) / G, static_cast<long long>(hi), G);
+  }
+  for (int g = 0; g < G; g += std::max(1, G / 12)) {
+    fprintf(stderr, "  bin %d: histories %d members", g, hp.bin_histories[g]);
+    for (int q = 0; q < P; ++q) fprintf(stderr, " %d", hp.bin_members[static_cast<size_t>(g) * P + q]);
+    fprintf(stderr, "\n");
+  }
+}
 int build_sub(osg_cfr* s) {
   s->sub.ok = false;
   if (s->cfg.solver != 0 || s->B != 1 || !s->path_kernel || s->A > kSplitMaxA || !s->cfg.alternating_updates) return OSG_OK;
-  if (s->H < 4096 || s->D >= 63 || s->H >= (1 << 23)) return OSG_OK;
-  int L = 0;
-  for (; L < s->D; ++L) {
-    bool all_chance = true;
-    for (int h = s->level_off[L]; h < s->level_off[L + 1]; ++h) all_chance &= s->kind[h] == kChanceNode;
-    if (!all_chance) break;
-  }
-  if (L < 1 || L >= s->D - 1) return OSG_OK;
-  if (s->level_off[L + 1] - s->level_off[L] < 8) return OSG_OK;
-  std::vector<int32_t> sub_of(s->H, -1), loc_of(s->H, -1), level_of(s->H, 0);
-  for (int l = 0; l < s->D; ++l)
-    for (int h = s->level_off[l]; h < s->level_off[l + 1]; ++h) level_of[h] = l;
-  // ---- the bins: which histories a workgroup sweeps together ----
-  // sizes of every history's subtree (children have larger indices than their parent)
-  std::vector<int32_t> sz(s->H, 1), szd(s->H, 0);
-  for (int h = s->H - 1; h >= 1; --h) {
-    szd[h] += s->kind[h] == kDecisionNode ? 1 : 0;
-    sz[s->parent[h]] += sz[h];
-    szd[s->parent[h]] += szd[h];
-  }
-  int cus = s->num_cus;
-  if (cus <= 0) {
-    hipDeviceProp_t dp;
-    if (hipGetDeviceProperties(&dp, s->ctx->device) != hipSuccess) { (void)hipGetLastError(); return OSG_OK; }
-    cus = std::max(1, dp.multiProcessorCount);
-  }
-  // longest-processing-time packing of the histories of level `lp` into at most `cus` bins, balanced by subtree size
-  auto pack = [&](int lp, std::vector<int32_t>* bin_of, int* bins) -> bool {
-    const int n = s->level_off[lp + 1] - s->level_off[lp], base = s->level_off[lp];
-    const int nb = std::min(n, cus);
-    std::vector<int32_t> order(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sz[base + a] > sz[base + b]; });
-    std::vector<int64_t> load(nb, 0), loadd(nb, 0), cnt(nb, 0);
-    bin_of->assign(n, 0);
-    for (int i : order) {
-      int best = 0;
-      for (int b = 1; b < nb; ++b)
-        if (load[b] < load[best]) best = b;
-      (*bin_of)[i] = best;
-      load[best] += sz[base + i]; loadd[best] += szd[base + i]; ++cnt[best];
-    }
-    for (int b = 0; b < nb; ++b) {
-      const int64_t nl = load[b], nd = loadd[b] + cnt[b];   // (+ the rows of the pieces' upper parents)
-      if (nl > 8 * kSubThreads || nd > kSubKD * kSubThreads || sizeof(double) * (nl + nd * s->A) > 150 * 1024) return false;
-    }
-    *bins = nb;
-    return true;
-  };
-  const int G0 = s->level_off[L + 1] - s->level_off[L];
-  int G = G0, piece_level = L;
-  bool upper = false;          // the histories of level L belong to no bin
-  std::vector<int32_t> bin_of;
+  SubLimits lim;
+  lim.cus = s->num_cus;
   const char* pk = std::getenv("OSG_CFR_SUB_PACK");
-  if (G0 > cus && !(pk && pk[0] == '0')) {
-    int nb = 0;
-    if (pack(L, &bin_of, &nb)) {
-      G = nb;
-    } else if (L + 1 < s->D - 1 && pack(L + 1, &bin_of, &nb)) {
-      G = nb; piece_level = L + 1; upper = true;
-    } else {
-      bin_of.clear();
-    }
-  }
-  if (bin_of.empty()) {
-    bin_of.resize(G0);
-    for (int g = 0; g < G0; ++g) bin_of[g] = g;
-  }
-  std::vector<std::vector<int32_t>> hist(G);
-  for (int h = s->level_off[piece_level]; h < s->H; ++h) {
-    sub_of[h] = h < s->level_off[piece_level + 1] ? bin_of[h - s->level_off[piece_level]] : sub_of[s->parent[h]];
-    const int g = sub_of[h];
-    loc_of[h] = static_cast<int32_t>(hist[g].size());
-    hist[g].push_back(h);
-  }
-  int NL = 0;
-  for (int g = 0; g < G; ++g) NL = std::max<int>(NL, static_cast<int>(hist[g].size()));
-  const int K = NL <= 2 * kSubThreads ? 2 : (NL <= 4 * kSubThreads ? 4 : 8);
-  if (NL > 8 * kSubThreads) return OSG_OK;
-  const size_t M = s->mem.size();
-  std::vector<std::vector<int32_t>> members(static_cast<size_t>(G) * s->P);
-  std::vector<int32_t> upper_members;            // forest form: the members of level L, in member order
-  std::vector<int32_t> upper_of(std::max<size_t>(M, 1), -1);
-  for (size_t m = 0; m < M; ++m) {
-    const int h = s->mem[m];
-    if (sub_of[h] < 0) {
-      if (!upper || level_of[h] != L) return OSG_OK;  // a decision node above the cut
-      upper_of[m] = static_cast<int32_t>(upper_members.size());
-      upper_members.push_back(static_cast<int32_t>(m));
-      continue;
-    }
-    members[static_cast<size_t>(sub_of[h]) * s->P + s->actor[h]].push_back(static_cast<int32_t>(m));
-  }
-  if (std::getenv("OSG_CFR_SUB_STATS")) {   // how even the bins are: histories, levels and members per player
-    for (int q = -1; q < s->P; ++q) {
-      int64_t lo = INT64_MAX, hi = 0, sum = 0;
-      for (int g = 0; g < G; ++g) {
-        const int64_t v = q < 0 ? static_cast<int64_t>(hist[g].size()) : static_cast<int64_t>(members[static_cast<size_t>(g) * s->P + q].size());
-        lo = std::min(lo, v); hi = std::max(hi, v); sum += v;
-      }
-      fprintf(stderr, "k_cfr_sub bins: %s min %lld mean %.1f max %lld over %d bins\n", q < 0 ? "histories" : (q == 0 ? "members p0" : (q == 1 ? "members p1" : "members p2+")),
-              static_cast<long long>(lo), static_cast<double>(sum) / G, static_cast<long long>(hi), G);
-    }
-    for (int g = 0; g < G; g += std::max(1, G / 12)) {
-      fprintf(stderr, "  bin %d: histories %zu members", g, hist[g].size());
-      for (int q = 0; q < s->P; ++q) fprintf(stderr, " %zu", members[static_cast<size_t>(g) * s->P + q].size());
-      fprintf(stderr, "\n");
-    }
-  }
-  std::vector<int32_t> nloc(G), desc(static_cast<size_t>(G) * NL, kTerminalNode | (63 << 10)), fc(static_cast<size_t>(G) * NL, 0),
-      aux(static_cast<size_t>(G) * NL, 0), mem_off(static_cast<size_t>(G) * s->P + 1, 0), sub_rec,
-      info_off(s->P + 1, 0), info_list;
-  // the decisions of one player on a root path: the codes of a member record are P groups of `per_player` int4 chunks
-  int most = 0;
-  {
-    std::vector<int> cnt(s->P);
-    for (size_t m = 0; m < M; ++m) {
-      std::fill(cnt.begin(), cnt.end(), 0);
-      for (int e = s->path_off[m]; e < s->path_off[m + 1]; ++e)
-        if (!((s->path[e] >> 23) & 1)) most = std::max(most, ++cnt[(s->path[e] >> 24) & 0xF]);
-    }
-  }
-  const int per_player = std::max(1, (most + 3) / 4);
-  if (per_player * s->P > kSubCodeChunks) return OSG_OK;   // more decisions on a path than the packed record keeps
-  const int PL = 4 * per_player * s->P;
-  std::vector<std::vector<int32_t>> dec_rows(G);
-  std::vector<std::map<int32_t, int32_t>> extra_row(G);
-  std::vector<int32_t> anc, filled(s->P);
-  int32_t n_members = 0;
-  std::vector<int32_t> dec_off(static_cast<size_t>(G) * (s->P + 2), 0);
-  std::vector<std::vector<double>> chance_probs(G);
-  for (int g = 0; g < G; ++g) {
-    nloc[g] = static_cast<int32_t>(hist[g].size());
-    // the bin's decision rows ordered by acting player (a pass re-fetches one player's rows only: SubTree's comment)
-    std::vector<int32_t> next(s->P + 1, 0);
-    for (int h : hist[g])
-      if (s->kind[h] == kDecisionNode) ++next[s->actor[h] + 1];
-    for (int q = 0; q < s->P; ++q) next[q + 1] += next[q];
-    for (int q = 0; q <= s->P; ++q) dec_off[static_cast<size_t>(g) * (s->P + 2) + q] = next[q];
-    dec_rows[g].assign(next[s->P], 0);
-    for (size_t j = 0; j < hist[g].size(); ++j) {
-      const int h = hist[g][j];
-      const size_t at = static_cast<size_t>(g) * NL + j;
-      desc[at] = s->kind[h] | (s->nchild[h] << 2) | (level_of[h] << 10) | ((s->actor[h] + 1) << 16);
-      fc[at] = s->kind[h] == kTerminalNode ? 0 : loc_of[s->first_child[h]];
-      aux[at] = h;
-      if (s->kind[h] == kDecisionNode) {
-        aux[at] = next[s->actor[h]]++;
-        dec_rows[g][aux[at]] = s->info[h] * s->A;
-      } else if (s->kind[h] == kChanceNode) {
-        aux[at] = static_cast<int32_t>(chance_probs[g].size());   // its outcome probabilities, staged in LDS
-        for (int c = 0; c < s->nchild[h]; ++c) chance_probs[g].push_back(s->edge_prob[s->first_child[h] + c]);
-      }
-    }
-    for (int q = 0; q < s->P; ++q) {
-      for (int32_t m : members[static_cast<size_t>(g) * s->P + q]) {
-        const int h = s->mem[m];
-        const size_t at = static_cast<size_t>(g) * NL + loc_of[h];
-        sub_rec.push_back(m);
-        sub_rec.push_back(loc_of[h]);
-        sub_rec.push_back(aux[at] | (static_cast<int32_t>(s->nact[s->info[h]]) << 24));
-        sub_rec.push_back(fc[at]);
-        // the root path, leaf to root: entry e of SmallTree::path is the edge out of the ancestor at depth e
-        const int len = s->path_off[m + 1] - s->path_off[m];
-        anc.resize(len);
-        for (int e = len - 1, x = s->parent[h]; e >= 0; --e, x = s->parent[x]) anc[e] = x;
-        double chance = 1.0;
-        std::vector<int32_t> codes(PL, -1);
-        std::fill(filled.begin(), filled.end(), 0);
-        for (int e = 0; e < len; ++e) {
-          const int code = s->path[s->path_off[m] + e];
-          if ((code >> 23) & 1) {
-            chance *= s->edge_prob[code & 0x7FFFFF];
-          } else {
-            const int pl = (code >> 24) & 0xF, a_idx = (code & 0x7FFFFF) - s->info[anc[e]] * s->A;
-            if (a_idx < 0 || a_idx >= s->A) return OSG_OK;   // (cannot happen)
-            int d_anc;
-            if (sub_of[anc[e]] == g) {
-              d_anc = aux[static_cast<size_t>(g) * NL + loc_of[anc[e]]];
-            } else if (upper && sub_of[anc[e]] < 0 && level_of[anc[e]] == L) {
-              // a deal root above the forest: its policy row rides behind the forest's own rows
-              auto it = extra_row[g].find(anc[e]);
-              if (it == extra_row[g].end()) {
-                it = extra_row[g].emplace(anc[e], static_cast<int32_t>(dec_rows[g].size())).first;
-                dec_rows[g].push_back(s->info[anc[e]] * s->A);
-              }
-              d_anc = it->second;
-            } else {
-              return OSG_OK;   // (cannot happen: decisions sit below the cut)
-            }
-            codes[static_cast<size_t>(pl) * 4 * per_player + filled[pl]++] = d_anc * s->A + a_idx;
-          }
-        }
-        int64_t bits;
-        memcpy(&bits, &chance, sizeof bits);
-        sub_rec.push_back(static_cast<int32_t>(bits & 0xFFFFFFFF));
-        sub_rec.push_back(static_cast<int32_t>(bits >> 32));
-        sub_rec.push_back(0);
-        sub_rec.push_back(0);
-        // the codes as 16-bit halves (a code indexes the bin's ND * A <= 16 384 staged policy entries; 0xFFFF pads), the
-        // record padded to whole 16-byte pieces
-        for (int c = 0; c < PL; c += 2)
-          sub_rec.push_back(static_cast<int32_t>((static_cast<uint32_t>(codes[c]) & 0xFFFFu) |
-                                                 ((static_cast<uint32_t>(codes[c + 1]) & 0xFFFFu) << 16)));
-        for (int c = PL / 2; c % 4 != 0; ++c) sub_rec.push_back(-1);
-        ++n_members;
-      }
-      mem_off[static_cast<size_t>(g) * s->P + q + 1] = n_members;
-    }
-  }
-  for (int q = 0; q < s->P; ++q) {
-    for (int i = 0; i < s->I; ++i)
-      if (s->info_player[i] == q) info_list.push_back(i);
-    info_off[q + 1] = static_cast<int32_t>(info_list.size());
-  }
-  int ND = 2, NCP = 2;
-  for (int g = 0; g < G; ++g) {
-    ND = std::max<int>(ND, static_cast<int>(dec_rows[g].size()));
-    NCP = std::max<int>(NCP, static_cast<int>(chance_probs[g].size()));
-  }
-  ND += ND & 1; NCP += NCP & 1;   // (even: the values and the fold's stage behind them stay 16-byte aligned)
-  std::vector<int32_t> ndec(G), dec_row(static_cast<size_t>(G) * ND, 0);
-  std::vector<double> chance_prob(static_cast<size_t>(G) * NCP, 0.0);
-  for (int g = 0; g < G; ++g) {
-    ndec[g] = static_cast<int32_t>(dec_rows[g].size());
-    dec_off[static_cast<size_t>(g) * (s->P + 2) + s->P + 1] = ndec[g];   // (the upper parents' rows sit behind the players')
-    std::copy(dec_rows[g].begin(), dec_rows[g].end(), dec_row.begin() + static_cast<size_t>(g) * ND);
-    std::copy(chance_probs[g].begin(), chance_probs[g].end(), chance_prob.begin() + static_cast<size_t>(g) * NCP);
-  }
-  // dynamic LDS: [policy rows ND * A | chance probabilities NCP | values NL | spare]; the fold stages 64-byte member
-  // records from the values on (one bin per workgroup: the rows stay) — the spare takes it to 2 048 records where there is room
-  const size_t base_doubles = static_cast<size_t>(ND) * s->A + NCP + NL;
-  if (sizeof(double) * base_doubles > 150 * 1024 || ND > kSubKD * kSubThreads) return OSG_OK;
-  const size_t lds_doubles = std::min<size_t>(static_cast<size_t>(ND) * s->A + NCP + static_cast<size_t>(kSubFoldX) * kSubThreads * kSubRecDoubles,
-                                              (158 * 1024) / sizeof(double));
-  const size_t lds = sizeof(double) * std::max(base_doubles, lds_doubles);
-  const int fold_cap = static_cast<int>(std::min<size_t>((lds / sizeof(double) - static_cast<size_t>(ND) * s->A - NCP) / kSubRecDoubles,
-                                                         static_cast<size_t>(kSubFoldX) * kSubThreads));
-  // forest form: the pieces' roots (their values leave through root_value) and the upper members' records
-  std::vector<int32_t> nroot, root_loc, root_idx, upper_rec;
-  int NR = 0;
-  const int root_base = s->level_off[piece_level];
-  if (upper) {
-    std::vector<std::vector<int32_t>> roots(G);
-    for (int h = root_base; h < s->level_off[piece_level + 1]; ++h) roots[sub_of[h]].push_back(h);
-    for (int g = 0; g < G; ++g) NR = std::max<int>(NR, static_cast<int>(roots[g].size()));
-    nroot.resize(G);
-    root_loc.assign(static_cast<size_t>(G) * NR, 0);
-    root_idx.assign(static_cast<size_t>(G) * NR, 0);
-    for (int g = 0; g < G; ++g) {
-      nroot[g] = static_cast<int32_t>(roots[g].size());
-      for (size_t r = 0; r < roots[g].size(); ++r) {
-        root_loc[static_cast<size_t>(g) * NR + r] = loc_of[roots[g][r]];
-        root_idx[static_cast<size_t>(g) * NR + r] = roots[g][r] - root_base;
-      }
-    }
-    for (int32_t m : upper_members) {
-      const int h = s->mem[m];
-      double chance = 1.0;   // the root path of a deal root holds chance edges only, multiplied in path order
-      for (int e = s->path_off[m]; e < s->path_off[m + 1]; ++e) {
-        const int code = s->path[e];
-        if (!((code >> 23) & 1)) return OSG_OK;   // (cannot happen: every level above the cut is a chance level)
-        chance *= s->edge_prob[code & 0x7FFFFF];
-      }
-      int64_t bits;
-      memcpy(&bits, &chance, sizeof bits);
-      upper_rec.push_back(s->first_child[h] - root_base);
-      upper_rec.push_back(s->info[h] * s->A);
-      upper_rec.push_back(s->nact[s->info[h]]);
-      upper_rec.push_back(0);
-      upper_rec.push_back(static_cast<int32_t>(bits & 0xFFFFFFFF));
-      upper_rec.push_back(static_cast<int32_t>(bits >> 32));
-      upper_rec.push_back(0);
-      upper_rec.push_back(0);
-    }
-  }
-  if (static_cast<unsigned long long>(M) * kSubRecDoubles * 8 >= (1ull << 31)) return OSG_OK;   // 32-bit record offsets
-  int widest = 0;   // the fold stages an infostate's member records in LDS: all of one infostate must fit a round
-  for (int i = 0; i < s->I; ++i) widest = std::max(widest, s->mem_off[i + 1] - s->mem_off[i]);
-  if (widest > fold_cap) return OSG_OK;
-  const void* kern = cfr_sub_kernel_of(K, false);
-  if (raise_lds_cap(kern, static_cast<int>(lds)) != hipSuccess) {
-    (void)hipGetLastError();
-    return OSG_OK;
-  }
-  // the CFR-BR form of the same kernel: taken when it can be resident on the same grid (else CFR-BR keeps the launches per phase)
-  s->sub.br_ok = false;
-  if (raise_lds_cap(cfr_sub_kernel_of(K, true), static_cast<int>(lds)) == hipSuccess) {
-    int per_cu_br = 0;
-    hipError_t eb;
-    if (K == 2) eb = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_br, k_cfr_sub<2, true>, kSubThreads, lds);
-    else if (K == 4) eb = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_br, k_cfr_sub<4, true>, kSubThreads, lds);
-    else eb = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_br, k_cfr_sub<8, true>, kSubThreads, lds);
-    if (eb == hipSuccess) s->sub.br_ok = per_cu_br >= 1;
-    else (void)hipGetLastError();
-  } else {
-    (void)hipGetLastError();
-  }
-  // the discounting form likewise (else a discounting solver keeps the launches per phase)
-  s->sub.dcfr_ok = false;
-  int per_cu_d = 0;
-  if (raise_lds_cap(cfr_sub_kernel_of(K, false, true), static_cast<int>(lds)) == hipSuccess) {
-    hipError_t ed;
-    if (K == 2) ed = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, k_cfr_sub<2, false, true>, kSubThreads, lds);
-    else if (K == 4) ed = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, k_cfr_sub<4, false, true>, kSubThreads, lds);
-    else ed = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, k_cfr_sub<8, false, true>, kSubThreads, lds);
-    if (ed != hipSuccess) { (void)hipGetLastError(); per_cu_d = 0; }
-  } else {
-    (void)hipGetLastError();
-  }
-  int per_cu = 0;
-  hipError_t e;
-  if (K == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_cfr_sub<2>, kSubThreads, lds);
-  else if (K == 4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_cfr_sub<4>, kSubThreads, lds);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_cfr_sub<8>, kSubThreads, lds);
-  hipDeviceProp_t prop;
-  if (e != hipSuccess || per_cu < 1 || hipGetDeviceProperties(&prop, s->ctx->device) != hipSuccess || !prop.cooperativeLaunch) {
-    (void)hipGetLastError();
-    return OSG_OK;
-  }
-  const int grid = std::min(G, per_cu * prop.multiProcessorCount);
-  s->sub.dcfr_ok = per_cu_d >= 1 && std::min(G, per_cu_d * prop.multiProcessorCount) >= grid;   // resident on the same grid
-  // the fold's shares: a workgroup's run of the updating player's infostates (info_list order), balanced by members
-  std::vector<int32_t> fold_info(info_list.size() * 4), fold_off(static_cast<size_t>(s->P) * (grid + 1), 0);
-  for (size_t e = 0; e < info_list.size(); ++e) {
-    const int i = info_list[e];
-    fold_info[4 * e] = i; fold_info[4 * e + 1] = s->nact[i]; fold_info[4 * e + 2] = s->mem_off[i];
-    fold_info[4 * e + 3] = s->mem_off[i + 1] - s->mem_off[i];
-  }
-  for (int q = 0; q < s->P; ++q) {
-    int64_t total = 0;
-    for (int e = info_off[q]; e < info_off[q + 1]; ++e) total += fold_info[4 * static_cast<size_t>(e) + 3] + 8;   // (+ the row's own cost)
-    int64_t run = 0;
-    int e = info_off[q];
-    for (int w = 0; w < grid; ++w) {
-      fold_off[static_cast<size_t>(q) * (grid + 1) + w] = e;
-      const int64_t upto = total * (w + 1) / grid;
-      while (e < info_off[q + 1] && run + (fold_info[4 * static_cast<size_t>(e) + 3] + 8) / 2 < upto) {
-        run += fold_info[4 * static_cast<size_t>(e) + 3] + 8;
-        ++e;
-      }
-    }
-    fold_off[static_cast<size_t>(q) * (grid + 1) + grid] = info_off[q + 1];
-    for (int w = grid - 1; w >= 0; --w)   // (everything is handed out: the last share takes what rounding left)
-      if (fold_off[static_cast<size_t>(q) * (grid + 1) + w] > fold_off[static_cast<size_t>(q) * (grid + 1) + w + 1])
-        fold_off[static_cast<size_t>(q) * (grid + 1) + w] = fold_off[static_cast<size_t>(q) * (grid + 1) + w + 1];
-  }
+  lim.pack = !(pk && pk[0] == '0');
+  const HostTree tree = s->host_tree();
+  const SubHostPlan hp = plan_sub(tree, lim);
+  if (std::getenv("OSG_CFR_SUB_STATS") && !hp.bin_histories.empty()) print_sub_stats(hp, s->P);
+  if (!hp.ok) return OSG_OK;
+  SubPlan& sp = s->sub;
+  // the plain form decides; the CFR-BR and discounting forms of the same kernel are taken when they can be resident on
+  // the same grid (else CFR-BR / a discounting solver keeps the launches per phase)
+  const int per_cu = cfr_sub_blocks_per_cu(hp.K, false, false, hp.lds_bytes);
+  if (per_cu < 1 || !s->cooperative_launch) return OSG_OK;
+  const int grid = std::min(hp.G, per_cu * s->num_cus);
+  sp.br_ok = cfr_sub_blocks_per_cu(hp.K, true, false, hp.lds_bytes) >= 1;
+  sp.dcfr_ok = std::min(hp.G, cfr_sub_blocks_per_cu(hp.K, false, true, hp.lds_bytes) * s->num_cus) >= grid;
+  const SubFoldPlan fold = plan_sub_fold(tree, hp, grid);
   hipStream_t st = s->ctx->stream;
   int rc;
-  if ((rc = upload(nloc, s->sub.nloc, st)) || (rc = upload(desc, s->sub.desc, st)) || (rc = upload(fc, s->sub.fc, st)) ||
-      (rc = upload(aux, s->sub.aux, st)) || (rc = upload(mem_off, s->sub.mem_off, st)) ||
-      (rc = upload(sub_rec, s->sub.rec, st)) ||
-      (rc = upload(info_off, s->sub.info_off, st)) || (rc = upload(info_list, s->sub.info_list, st)) ||
-      (rc = upload(ndec, s->sub.ndec, st)) || (rc = upload(dec_row, s->sub.dec_row, st)) ||
-      (rc = upload(dec_off, s->sub.dec_off, st)) || (rc = upload(chance_prob, s->sub.chance_prob, st)) ||
-      (rc = upload(fold_info, s->sub.fold_info, st)) || (rc = upload(fold_off, s->sub.fold_off, st)))
+  if ((rc = upload(hp.nloc, sp.nloc, st)) || (rc = upload(hp.desc, sp.desc, st)) || (rc = upload(hp.fc, sp.fc, st)) ||
+      (rc = upload(hp.aux, sp.aux, st)) || (rc = upload(hp.mem_off, sp.mem_off, st)) ||
+      (rc = upload(hp.sub_rec, sp.rec, st)) ||
+      (rc = upload(hp.info_off, sp.info_off, st)) || (rc = upload(hp.info_list, sp.info_list, st)) ||
+      (rc = upload(hp.ndec, sp.ndec, st)) || (rc = upload(hp.dec_row, sp.dec_row, st)) ||
+      (rc = upload(hp.dec_off, sp.dec_off, st)) || (rc = upload(hp.chance_prob, sp.chance_prob, st)) ||
+      (rc = upload(fold.fold_info, sp.fold_info, st)) || (rc = upload(fold.fold_off, sp.fold_off, st)) ||
+      (rc = upload(hp.term_val, sp.term_val, st)) || (rc = upload(hp.recbuf, sp.recbuf, st)))
     return rc;
-  {
-    // the terminal returns of every bin by player, in the bin's local order: a pass starts with one coalesced copy into LDS
-    const size_t n = static_cast<size_t>(G) * s->P * NL;
-    if (n * sizeof(double) > (size_t{1} << 31)) return OSG_OK;
-    std::vector<double> term_val(n, 0.0);
-    for (int g = 0; g < G; ++g)
-      for (size_t j = 0; j < hist[g].size(); ++j) {
-        const int h = hist[g][j];
-        if (s->kind[h] != kTerminalNode) continue;
-        for (int q = 0; q < s->P; ++q)
-          term_val[(static_cast<size_t>(g) * s->P + q) * NL + j] = s->term_ret[static_cast<size_t>(h) * s->P + q];
-      }
-    if ((rc = upload(term_val, s->sub.term_val, st))) return rc;
-  }
-  s->sub.NCP = NCP;
-  s->sub.keep_rows = grid >= G;
-  {
-    // the members' 64-byte records: zero, but an upper member's says which one it is (kSubFlagHi | 2 + u)
-    std::vector<double> recbuf(std::max<size_t>(M, 1) * kSubRecDoubles, 0.0);
-    for (size_t m = 0; m < M; ++m)
-      if (upper_of[m] >= 0) {
-        const int64_t bits = (static_cast<int64_t>(kSubFlagHi) << 32) | static_cast<int64_t>(2 + upper_of[m]);
-        memcpy(&recbuf[m * kSubRecDoubles], &bits, sizeof bits);
-      }
-    if ((rc = upload(recbuf, s->sub.recbuf, st))) return rc;
-  }
-  s->sub.forest = upper;
-  if (upper) {
-    if ((rc = upload(nroot, s->sub.nroot, st)) || (rc = upload(root_loc, s->sub.root_loc, st)) ||
-        (rc = upload(root_idx, s->sub.root_idx, st)) || (rc = upload(upper_rec, s->sub.upper_rec, st)))
+  if (hp.forest) {
+    if ((rc = upload(hp.nroot, sp.nroot, st)) || (rc = upload(hp.root_loc, sp.root_loc, st)) ||
+        (rc = upload(hp.root_idx, sp.root_idx, st)) || (rc = upload(hp.upper_rec, sp.upper_rec, st)))
       return rc;
-    const size_t n_roots = static_cast<size_t>(s->level_off[piece_level + 1] - root_base);
-    OSG_HIP(s->sub.root_value.alloc(n_roots));
-    OSG_HIP(hipMemsetAsync(s->sub.root_value, 0, sizeof(double) * std::max<size_t>(n_roots, 1), st));
-    s->sub.NR = NR;
+    OSG_HIP(sp.root_value.alloc(hp.piece_roots));
+    OSG_HIP(hipMemsetAsync(sp.root_value, 0, sizeof(double) * std::max(hp.piece_roots, 1), st));
+    sp.NR = hp.NR;
   }
-  s->sub.ND = ND;
-  s->sub.PL = PL;
-  OSG_HIP(s->sub.bar.alloc(kSubBarWords));
-  OSG_HIP(hipMemsetAsync(s->sub.bar, 0, sizeof(unsigned int) * kSubBarWords, st));
-  s->sub.G0 = G0;
-  s->sub.G = G; s->sub.L = L; s->sub.NL = NL; s->sub.K = K; s->sub.grid = grid; s->sub.lds_bytes = lds;
-  s->sub.ok = true;
+  OSG_HIP(sp.bar.alloc(kSubBarWords));
+  OSG_HIP(hipMemsetAsync(sp.bar, 0, sizeof(unsigned int) * kSubBarWords, st));
+  sp.forest = hp.forest; sp.keep_rows = fold.keep_rows;
+  sp.G0 = hp.G0; sp.G = hp.G; sp.L = hp.L; sp.NL = hp.NL; sp.K = hp.K; sp.ND = hp.ND; sp.PL = hp.PL; sp.NCP = hp.NCP;
+  sp.grid = grid; sp.lds_bytes = hp.lds_bytes;
+  sp.ok = true;
   return OSG_OK;
 }
 

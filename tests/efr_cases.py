@@ -434,20 +434,33 @@ def build_host_test(path, extra=()):
     return path
 
 
+def _i32(a):
+    return np.ascontiguousarray(a, np.int32).tobytes()
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, np.float64).tobytes()
+
+
+def write_layout(lay, f, more_sizes=()):
+    """The layout as the host programs read it: the sizes (and the caller's own, in the same header), the sixteen int
+    arrays, edge_prob and term_ret."""
+    f.write(_i32([lay.H, lay.I, lay.A, lay.P, lay.D, lay.M, len(lay.path), *more_sizes]))
+    for a in (lay.level_off, lay.parent, lay.first_child, lay.kind, lay.nchild, lay.aidx, lay.actor, lay.info, lay.mem_off,
+              lay.mem, lay.mem_index, lay.nact, lay.legal, lay.info_player, lay.path_off, lay.path):
+        f.write(_i32(a))
+    f.write(_f64(lay.edge_prob) + _f64(lay.term_ret))
+
+
 def write_case(v, r, path):
     """The input of `efr_host_test run`: the layout, the golden's deviation tables and its checkpoints."""
     _, game, name = runs(v)[r]
     lay = layout(v, r, game)
-    i32 = lambda a: np.ascontiguousarray(a, np.int32).tobytes()
-    f64 = lambda a: np.ascontiguousarray(a, np.float64).tobytes()
+    i32, f64 = _i32, _f64
     Lg = v[f"r{r}/dev_weights"].shape[1]
     C = len(v[f"r{r}/checkpoints"])
     with open(path, "wb") as f:
-        f.write(i32([lay.H, lay.I, lay.A, lay.P, lay.D, lay.M, len(lay.path), TYPES.index(name), C, len(v[f"r{r}/dev_target"]), Lg]))
-        for a in (lay.level_off, lay.parent, lay.first_child, lay.kind, lay.nchild, lay.aidx, lay.actor, lay.info, lay.mem_off,
-                  lay.mem, lay.mem_index, lay.nact, lay.legal, lay.info_player, lay.path_off, lay.path):
-            f.write(i32(a))
-        f.write(f64(lay.edge_prob) + f64(lay.term_ret))
+        write_layout(lay, f, (TYPES.index(name), C, len(v[f"r{r}/dev_target"]), Lg))
         for k in ("dev_count", "dev_target", "dev_source", "dev_weights_none", "dev_weights", "dev_memory", "checkpoints"):
             f.write(i32(v[f"r{r}/{k}"]))
         for c in range(C):
