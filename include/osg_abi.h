@@ -1070,6 +1070,58 @@ int osg_deep_cfr_traverse(osg_cfr* s, const float* d_advantages, int player, int
 int osg_deep_cfr_staged(osg_cfr* s, int64_t* sizes, int64_t* d_adv_offsets, int32_t* d_adv_info, float* d_adv_values,
                         int64_t* d_strat_offsets, int32_t* d_strat_info, float* d_strat_values, int32_t* d_draws);
 
+/* ---- NFSP (open_spiel/python/pytorch/nfsp.py, dqn.py) ---------------------------------------------
+ * The part of Neural Fictitious Self-Play (and, with anticipatory 1, of DQN self-play) that the reference runs at one
+ * decision per interpreter step: playing episodes, choosing actions from the two networks, forming DQN transitions and
+ * supervised rows and appending them to a ring and a reservoir.  The arithmetic is open_spiel_amd/csrc/osg_nfsp.h.
+ *
+ * osg_transition_ring: dqn.ReplayBuffer on the device.  A row is (infostate index i32, action id i32, reward f32, next
+ *   infostate index i32 — -1 at the end of an episode —, final u8); the reference also stores the next state's tensor
+ *   and legal mask, which reach its loss only multiplied by `not final`: whoever forms a batch supplies zeros there.
+ *   The row with entry index n (0-based over the ring's life, osg_transition_ring_clear restarts it) goes to slot
+ *   n % capacity.
+ * osg_transition_ring_append: m rows (device arrays [m]) as m sequential appends in row order; of the rows that meet
+ *   in a slot the last stays.  No atomics: row r stays iff r + capacity >= m.
+ * osg_transition_ring_sizes: rows held, entry index, capacity.
+ * osg_transition_ring_sample: d_slots [m] i64 = m distinct filled slots: the m smallest of the keys
+ *   Rng(seed, slot, stream).next(), ascending by (key, slot), as osg_reservoir_sample.
+ * osg_transition_ring_rows: the rows d_slots [m] i64 names (device), any output may be NULL. */
+typedef struct osg_transition_ring osg_transition_ring;
+int osg_transition_ring_create(osg_ctx* ctx, int64_t capacity, osg_transition_ring** out);
+int osg_transition_ring_destroy(osg_transition_ring* ring);
+int osg_transition_ring_sizes(osg_transition_ring* ring, int64_t* size, int64_t* entry_index, int64_t* capacity);
+int osg_transition_ring_clear(osg_transition_ring* ring);
+int osg_transition_ring_append(osg_transition_ring* ring, int64_t m, const int32_t* d_info, const int32_t* d_action,
+                               const float* d_reward, const int32_t* d_next_info, const uint8_t* d_final);
+int osg_transition_ring_sample(osg_transition_ring* ring, uint64_t seed, uint64_t stream, int64_t m, int64_t* d_slots);
+int osg_transition_ring_rows(osg_transition_ring* ring, const int64_t* d_slots, int64_t m, int32_t* d_info, int32_t* d_action,
+                             float* d_reward, int32_t* d_next_info, uint8_t* d_final);
+/* osg_nfsp_collect: `episodes` self-play episodes on any osg_cfr object (its tables are not touched), one launch and
+ *   one host wait.  d_q [I, Amax] f32 (device) holds the Q-network output of every infostate (row i from the network
+ *   of infostate i's player) and d_avg_probs [I, Amax] f32 its average-policy probabilities by action id (the softmax
+ *   over the legal logits: zero at illegal ids); both are frozen for the call.  eps, anticipatory [P] (host) are every
+ *   player's exploration rate and anticipatory parameter.  Episode g = first_episode + j draws from Rng(seed, g, 0):
+ *   P uniforms for the players' modes (BEST_RESPONSE iff u < anticipatory[p]), then one per chance node (NumPy's
+ *   choice(p=)), at a BEST_RESPONSE decision one for the explore test and, if it explores, below(n) for the action, at
+ *   an AVERAGE_POLICY decision one for choice(p=) over all Amax ids.  Player p's transitions go to rings[p] and the
+ *   supervised rows (infostate, probs f32 [Amax]) of its BEST_RESPONSE decisions to reservoirs[p] (iteration field 0),
+ *   in the order of the reference's one-episode-after-another loop; rings, reservoirs or any entry may be NULL: nothing
+ *   is committed there.  totals (host, may be NULL) [P, 4]: transitions, supervised rows, steps of the DQN agent (its
+ *   decisions + 1 in every BEST_RESPONSE episode) and steps of the NFSP agent (decisions + 1 in every episode).
+ *   Served: what osg_deep_cfr_traverse serves, with at most 8 players and 15 decisions of one player on a path; the
+ *   rest is OSG_ERR_UNSUPPORTED.
+ * osg_nfsp_staged: the rows of the last osg_nfsp_collect in sequence order — player by player, a player's rows by
+ *   episode, then by time — with offsets [P * episodes + 1] i64 (entry p * episodes + j: the first row of player p in
+ *   episode j), the draws each episode consumed and its modes (bit p: BEST_RESPONSE) [episodes] i32 (device outputs,
+ *   any may be NULL); sizes (host, may be NULL) [4 + P]: episodes, transitions, supervised rows, rows staged per
+ *   (player, episode), and every player's exact bound. */
+int osg_nfsp_collect(osg_cfr* s, const float* d_q, const float* d_avg_probs, const double* eps, const double* anticipatory,
+                     uint64_t seed, int64_t first_episode, int64_t episodes, osg_transition_ring* const* rings,
+                     osg_reservoir* const* reservoirs, int64_t* totals);
+int osg_nfsp_staged(osg_cfr* s, int64_t* sizes, int64_t* d_ring_offsets, int32_t* d_ring_info, int32_t* d_ring_action,
+                    float* d_ring_reward, int32_t* d_ring_next_info, uint8_t* d_ring_final, int64_t* d_sl_offsets,
+                    int32_t* d_sl_info, float* d_sl_probs, int32_t* d_draws, int32_t* d_modes);
+
 /* ---- multi-GPU exchange step ---------------------------------------------------
  * One process per GPU.  Units shard by global index with no data-path collective; the ONE exchange
  * on the path is external-sampling MCCFR's all-reduce(sum) of the regret / average-policy delta

@@ -8,7 +8,8 @@ tabular CFR / Discounted CFR / external-sampling MCCFR / extensive-form fictitio
 magnetic mirror descent / extensive-form regret minimization, payoff tensors / policy aggregation / PSRO over populations of policies, and PSRO's
 meta-strategy solvers (projected replicator dynamics, regret matching) on batches of normal-form meta-games, and
 AlphaZero self-play (policy targets, moves, trajectories and a replay buffer on the device), and Deep CFR (traversals,
-sampled advantages and reservoir buffers on the device; the networks are torch's).
+sampled advantages and reservoir buffers on the device; the networks are torch's), and NFSP / DQN self-play (episodes,
+transitions, supervised rows, the replay ring and the reservoirs on the device).
 The C-ABI is include/osg_abi.h.
 """
 from ._abi import OsgError, describe, lib  # noqa: F401
@@ -52,6 +53,10 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".deep_cfr", __name__)
         return module if name == "deep_cfr" else getattr(module, name)
+    if name in ("NFSPSolver", "TransitionRing", "nfsp"):
+        import importlib
+        module = importlib.import_module(".nfsp", __name__)
+        return module if name == "nfsp" else getattr(module, name)
     if name in ("BatchedEnvironment", "TimeStep", "StepType", "ObservationType"):
         from . import vector_env
         return getattr(vector_env, name)

@@ -273,6 +273,15 @@ SIGNATURES = {
     "osg_reservoir_rows": (INT, [VP, VP, I64, VP, VP, VP]),
     "osg_deep_cfr_traverse": (INT, [VP, VP, INT, INT, U64, I64, I64, VP, VP, VP]),
     "osg_deep_cfr_staged": (INT, [VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "osg_transition_ring_create": (INT, [VP, I64, C.POINTER(VP)]),
+    "osg_transition_ring_destroy": (INT, [VP]),
+    "osg_transition_ring_sizes": (INT, [VP, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
+    "osg_transition_ring_clear": (INT, [VP]),
+    "osg_transition_ring_append": (INT, [VP, I64, VP, VP, VP, VP, VP]),
+    "osg_transition_ring_sample": (INT, [VP, U64, U64, I64, VP]),
+    "osg_transition_ring_rows": (INT, [VP, VP, I64, VP, VP, VP, VP, VP]),
+    "osg_nfsp_collect": (INT, [VP, VP, VP, VP, VP, U64, I64, I64, VP, VP, VP]),
+    "osg_nfsp_staged": (INT, [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     "osg_cfr_infostate_key": (INT, [VP, I64, C.c_char_p, INT]),
     "osg_cfr_best_response_history_values": (INT, [VP, INT, VP, INT, VP]),
     "osg_cfr_tree_edges": (INT, [VP, VP, VP]),

@@ -13,6 +13,7 @@
 //   osg_cfr_mmd.hip     k_mmd_small, k_mmd_*          magnetic mirror descent (MmdState lives there)
 //   osg_cfr_efr.hip     k_efr_resident, k_efr_*       extensive-form regret minimization (osg_efr.h has the arithmetic)
 //   osg_deep_cfr.hip    k_dcfr_*, k_res_*             Deep CFR traversals and reservoir buffers (osg_deep_cfr.h has the arithmetic)
+//   osg_nfsp.hip        k_nfsp_*, k_ring_*            NFSP self-play episodes and the DQN transition ring (osg_nfsp.h has the arithmetic)
 //
 // Every kernel is launched from the translation unit that defines it; what crosses the units are the device-side
 // argument structs below (views: raw pointers), the per-family plans that own the memory behind them (SplitPlan,
@@ -541,6 +542,8 @@ struct osg_cfr {
   // Deep CFR (osg_deep_cfr.hip): the legal ids, the launch's strategy table and the staged rows of the last
   // osg_deep_cfr_traverse, built at the first call (a DeepState; its deleter comes with the pointer)
   std::shared_ptr<void> deep;
+  // NFSP (osg_nfsp.hip): the legal ids, the row bounds and the staged rows of the last osg_nfsp_collect (an NfspState)
+  std::shared_ptr<void> nfsp;
 
   Tree tree() const {
     Tree t;
@@ -704,6 +707,11 @@ int build_resident_tree(osg_cfr* s);
 // ---- osg_cfr_mmd.hip ----
 bool mmd_mode(const osg_cfr* s);       // osg_mmd_set_params was accepted: pi and avg_x live in the cur and cum tables
 int mmd_after_reset(osg_cfr* s);       // avg_x = x of the fresh uniform policy
+// ---- osg_deep_cfr.hip ----
+int deep_supported(const osg_cfr* s, const char* who);   // what Deep CFR and NFSP serve: rows of at most 4 action ids, every id below the width
+bool reservoir_serves(const osg_reservoir* b, const osg_cfr* s);   // the solver's row width and context
+// m sequential appends of device rows, in row order (osg_reservoir_append without its argument checks)
+int reservoir_append(osg_reservoir* b, int64_t m, const int32_t* d_info, int32_t iteration, const float* d_values);
 // ---- osg_cfr_efr.hip ----
 bool efr_mode(const osg_cfr* s);       // osg_efr_set_deviations was accepted
 int efr_after_reset(osg_cfr* s);       // R and y back to 0

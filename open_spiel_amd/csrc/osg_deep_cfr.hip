@@ -69,6 +69,11 @@ __global__ void k_res_keys(uint64_t* key, int64_t* slot, uint64_t seed, uint64_t
   slot[k] = k;
 }
 
+}  // namespace
+
+namespace osg_cfr_impl {
+bool reservoir_serves(const osg_reservoir* b, const osg_cfr* s) { return b->A == s->A && b->ctx == s->ctx; }
+
 int reservoir_append(osg_reservoir* b, int64_t m, const int32_t* d_info, int32_t iteration, const float* d_values) {
   if (m == 0) return OSG_OK;
   hipStream_t st = b->ctx->stream;
@@ -80,6 +85,9 @@ int reservoir_append(osg_reservoir* b, int64_t m, const int32_t* d_info, int32_t
   b->add_calls += m;
   return OSG_OK;
 }
+}  // namespace osg_cfr_impl
+
+namespace {
 
 // ---- traversal ------------------------------------------------------------------------------------------------------------
 struct DeepState {   // what a solver holds for Deep CFR, built at the first call
@@ -244,6 +252,9 @@ int deep_state(osg_cfr* s, DeepState** out) {
   return OSG_OK;
 }
 
+}  // namespace
+
+namespace osg_cfr_impl {
 int deep_supported(const osg_cfr* s, const char* who) {
   if (s->A > kMaxA || s->A > kDcfrMaxA)
     return set_error(OSG_ERR_UNSUPPORTED, std::string(who) + ": decision nodes wider than 4 actions");
@@ -251,8 +262,7 @@ int deep_supported(const osg_cfr* s, const char* who) {
     if (id >= s->A) return set_error(OSG_ERR_UNSUPPORTED, std::string(who) + ": an action id beyond the table's width");
   return OSG_OK;
 }
-
-}  // namespace
+}  // namespace osg_cfr_impl
 
 extern "C" {
 

@@ -810,6 +810,60 @@ class TabularSolver:
         out["bounds"] = (int(sizes[3]), int(sizes[4]))
         return out
 
+    def nfsp_collect(self, q_values, avg_probs, epsilon, anticipatory, seed, episodes, first_episode=0, rings=None,
+                     reservoirs=None):
+        """`episodes` NFSP self-play episodes (nfsp.py / dqn.py under the loop of examples/kuhn_nfsp.py) against
+        q_values and avg_probs, [I, Amax] float32 device tensors by action id (the Q-network outputs and the average
+        policy's probabilities, zero at illegal ids).  epsilon / anticipatory: a number or one per player.  Player p's
+        DQN transitions go to rings[p] (nfsp.TransitionRing) and the supervised rows of its BEST_RESPONSE decisions to
+        reservoirs[p] (deep_cfr.ReservoirBuffer) in the reference's append order; a list or an entry may be None.
+        Returns an int64 array [P, 4]: transitions, supervised rows, DQN-agent steps, NFSP-agent steps per player."""
+        P = _abi.describe(self.game_string).num_players
+        want = (self.num_infostates, self.amax)
+        for t in (q_values, avg_probs):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != want or not t.is_contiguous()
+                    or t.device != self.ctx.device):
+                raise OsgError(f"nfsp_collect: expected contiguous float32 tensors of shape {want} on {self.ctx.device}")
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(epsilon, np.float64), (P,)))
+        ant = np.ascontiguousarray(np.broadcast_to(np.asarray(anticipatory, np.float64), (P,)))
+
+        def handles(bufs):
+            if bufs is None:
+                return None
+            if len(bufs) != P:
+                raise OsgError(f"nfsp_collect: expected {P} buffers (entries may be None)")
+            return (C.c_void_p * P)(*[None if b is None else b._h for b in bufs])
+
+        totals = np.zeros((P, 4), np.int64)
+        check(lib().osg_nfsp_collect(self._h, q_values.data_ptr(), avg_probs.data_ptr(), eps.ctypes.data, ant.ctypes.data,
+                                     int(seed) & (2 ** 64 - 1), int(first_episode), int(episodes), handles(rings),
+                                     handles(reservoirs), totals.ctypes.data))
+        return totals
+
+    def nfsp_staged(self):
+        """The rows of the last nfsp_collect in sequence order (player by player, a player's rows by episode, then by
+        time): a dict of device tensors ring_offsets / sl_offsets [P * E + 1] int64 (entry p * E + j: the first row of
+        player p in episode j), ring_info / ring_action / ring_next [R] int32, ring_reward [R] float32, ring_final [R]
+        uint8, sl_info [S] int32, sl_probs [S, Amax] float32, draws / modes [E] int32 (bit p of modes: BEST_RESPONSE),
+        and `bounds`, the most rows of either kind an episode can give each player."""
+        P = _abi.describe(self.game_string).num_players
+        sizes = (C.c_int64 * (4 + max(P, 8)))()
+        check(lib().osg_nfsp_staged(self._h, sizes, *([None] * 11)))
+        E, nr, ns = int(sizes[0]), int(sizes[1]), int(sizes[2])
+        dev = self.ctx.device
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)   # noqa: E731
+        out = dict(ring_offsets=torch.zeros(P * E + 1, dtype=torch.int64, device=dev), ring_info=i32(nr), ring_action=i32(nr),
+                   ring_reward=torch.empty(nr, dtype=torch.float32, device=dev), ring_next=i32(nr),
+                   ring_final=torch.empty(nr, dtype=torch.uint8, device=dev),
+                   sl_offsets=torch.zeros(P * E + 1, dtype=torch.int64, device=dev), sl_info=i32(ns),
+                   sl_probs=torch.empty((ns, self.amax), dtype=torch.float32, device=dev), draws=i32(E), modes=i32(E))
+        check(lib().osg_nfsp_staged(self._h, None, *[out[k].data_ptr() for k in (
+            "ring_offsets", "ring_info", "ring_action", "ring_reward", "ring_next", "ring_final", "sl_offsets", "sl_info",
+            "sl_probs", "draws", "modes")]))
+        self.ctx.synchronize()
+        out["bounds"] = tuple(int(sizes[4 + p]) for p in range(P))
+        return out
+
     def evaluate_policy(self, which="average", table=None):
         """NashConv / exploitability / expected returns / best-response values of a policy on the
         device (algorithms::NashConv, Exploitability, ExpectedReturns, TabularBestResponse).
