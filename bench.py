@@ -234,7 +234,7 @@ def secondary_workloads(osa, torch, dist, ctx, rank, world, with_cpu, host_barri
     def max_over_ranks(x):
         if world == 1:
             return x
-        t = torch.tensor([x], dtype=torch.float64, device="cuda")
+        t = torch.tensor([x], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
@@ -927,7 +927,7 @@ def mccfr_quality(osa, torch, dist, ctx, rank, world, batch, budget_s):
     def max_over_ranks(x):
         if world == 1:
             return x
-        t = torch.tensor([x], dtype=torch.float64, device="cuda")
+        t = torch.tensor([x], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
@@ -1570,7 +1570,7 @@ def main():
         """[x of rank 0, x of rank 1, ...] on every rank."""
         if world == 1:
             return [float(x)]
-        t = torch.zeros(world, dtype=torch.float64, device="cuda")
+        t = torch.zeros(world, dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         t[rank] = x
         dist.all_reduce(t)
         return [float(v) for v in t.tolist()]

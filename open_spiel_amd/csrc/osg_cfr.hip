@@ -333,6 +333,25 @@ int cfr_sub_error(const osg_cfr* s) {
   return OSG_OK;
 }
 
+// The kernels that spin on a grid barrier go out COOPERATIVELY: the runtime starts the grid only once all of it fits, so a
+// busy device makes the launch wait instead of starving a barrier.  OSG_CFR_PLAIN_LAUNCH=1 asks for an ordinary launch
+// (hosts that run the solver alone on the device: 20 us less per call).  The runtime serves cooperative launches from a
+// queue of their own, and where it cannot acquire one for this process — seen on a virtualised device in a host program
+// started by a process that had made cooperative launches itself — the launch returns hipErrorIllegalState with
+// nothing enqueued.  That process then makes ordinary launches of the same kernels, as with the switch: the grids
+// are at most one workgroup per CU, and the barrier's bound still turns a grid that was starved into an error.
+hipError_t launch_grid_barrier_kernel(const void* kern, dim3 grid, dim3 block, void** args, size_t lds_bytes, hipStream_t st) {
+  static const bool plain = std::getenv("OSG_CFR_PLAIN_LAUNCH") && std::getenv("OSG_CFR_PLAIN_LAUNCH")[0] == '1';
+  static bool no_cooperative_queue = false;   // (learnt once per process; a race only repeats the refused attempt)
+  if (!plain && !__atomic_load_n(&no_cooperative_queue, __ATOMIC_RELAXED)) {
+    const hipError_t e = hipLaunchCooperativeKernel(kern, grid, block, args, static_cast<unsigned>(lds_bytes), st);
+    if (e != hipErrorIllegalState) return e;
+    (void)hipGetLastError();
+    __atomic_store_n(&no_cooperative_queue, true, __ATOMIC_RELAXED);
+  }
+  return hipLaunchKernel(kern, grid, block, args, lds_bytes, st);
+}
+
 // The factors of iteration t as every kernel uses them (Discount in osg_cfr_internal.h): Python's `t**a / (t**a + 1)` and
 // `t**g` of discounted_cfr.py:184,203-208 — float pow is libm's pow, and so is std::pow here, in the same order.
 void discount_factors(double alpha, double beta, double gamma, int iteration, double out[3]) {

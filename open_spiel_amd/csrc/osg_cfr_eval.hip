@@ -590,10 +590,8 @@ static int launch_grid_eval(osg_cfr* s, const EvalArrays& ea, const double* src,
     EvalArrays eaa = ea;
     const double* pp = pol;
     void* args[] = {&tt, &eaa, &pp, &d_ev, &gp};
-    static const bool plain = std::getenv("OSG_CFR_PLAIN_LAUNCH") && std::getenv("OSG_CFR_PLAIN_LAUNCH")[0] == '1';
     const void* kern = reinterpret_cast<const void*>(&k_geval_persist);
-    if (plain) OSG_HIP(hipLaunchKernel(kern, dim3(static_cast<unsigned>(s->eval.grid)), dim3(kGEvalThreads), args, 0, st));
-    else OSG_HIP(hipLaunchCooperativeKernel(kern, dim3(static_cast<unsigned>(s->eval.grid)), dim3(kGEvalThreads), args, 0, st));
+    OSG_HIP(launch_grid_barrier_kernel(kern, dim3(static_cast<unsigned>(s->eval.grid)), dim3(kGEvalThreads), args, 0, st));
     record_eval_form(s, EvalForm::kGridPersist);
     return OSG_OK;
   }

@@ -680,6 +680,9 @@ int cfr_sub_error(const osg_cfr* s);   // a grid barrier timed out in an earlier
 void discount_factors(double alpha, double beta, double gamma, int iteration, double out[3]);
 // The factor table of iterations iteration0 + 1 ... iteration0 + iters on the device (null where the solver does not discount).
 int cfr_discount_table(osg_cfr* s, int iteration0, int iters, const double** d_table);
+// One launch of a kernel that spins on a grid barrier (k_cfr_split, k_cfr_sub, k_geval_persist): cooperative, unless
+// OSG_CFR_PLAIN_LAUNCH=1 or the runtime has no cooperative queue for this process (then an ordinary launch).
+hipError_t launch_grid_barrier_kernel(const void* kern, dim3 grid, dim3 block, void** args, size_t lds_bytes, hipStream_t st);
 // ---- osg_cfr_small.hip ----
 void cfr_small_prepare(osg_cfr* s);    // LDS caps of k_cfr<true> / k_cfr_small (clears lds_resident / small_tree where refused)
 int cfr_small_iterate(osg_cfr* s, Tables tb, int iters, unsigned grid_b);   // k_cfr_small / k_cfr

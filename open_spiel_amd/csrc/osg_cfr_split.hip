@@ -387,9 +387,7 @@ int launch_split(osg_cfr* s, SmallTree stree, SplitTree sp, Tables tb, int iters
   // launch costs 20 us per call (47.6 vs 27.6 us per one-iteration launch, CFR-BR 1.30e4 vs 1.82e4 it/s), which only the
   // calling pattern "one iteration per call" notices; without it the grid is resident together only as long as nothing
   // else holds the CUs (the barrier's 4 s bound then turns a starved launch into an error instead of a wait)
-  static const bool plain = std::getenv("OSG_CFR_PLAIN_LAUNCH") && std::getenv("OSG_CFR_PLAIN_LAUNCH")[0] == '1';
-  if (plain) OSG_HIP(hipLaunchKernel(kern, grid, block, args, lds, st));
-  else OSG_HIP(hipLaunchCooperativeKernel(kern, grid, block, args, static_cast<unsigned>(lds), st));
+  OSG_HIP(launch_grid_barrier_kernel(kern, grid, block, args, lds, st));
   return OSG_OK;
 }
 

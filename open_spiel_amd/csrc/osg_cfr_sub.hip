@@ -861,10 +861,7 @@ static int cfr_sub_run(osg_cfr* s, Tables tb, int iters, const int32_t* br_best,
     const void* kern = cfr_sub_kernel_of(s->sub.K, br_best != nullptr, disc != nullptr);
     // (OSG_CFR_PLAIN_LAUNCH=1 as for k_cfr_split: an ordinary launch, for hosts that own the device — and for runs under
     // rocprofv3 --kernel-trace, where a process that made a cooperative launch crashes in an exit handler)
-    static const bool plain = std::getenv("OSG_CFR_PLAIN_LAUNCH") && std::getenv("OSG_CFR_PLAIN_LAUNCH")[0] == '1';
-    if (plain) OSG_HIP(hipLaunchKernel(kern, dim3(static_cast<unsigned>(s->sub.grid)), dim3(kSubThreads), args, s->sub.lds_bytes, st));
-    else OSG_HIP(hipLaunchCooperativeKernel(kern, dim3(static_cast<unsigned>(s->sub.grid)), dim3(kSubThreads), args,
-                                            static_cast<unsigned>(s->sub.lds_bytes), st));
+    OSG_HIP(launch_grid_barrier_kernel(kern, dim3(static_cast<unsigned>(s->sub.grid)), dim3(kSubThreads), args, s->sub.lds_bytes, st));
   }
   if (sp.stamps) {
     unsigned long long h[8 * kMaxPlayers];

@@ -36,13 +36,34 @@ def shard_range(total, rank, world_size):
     return first, count
 
 
+def _through_host(tensor):
+    """gloo is a host transport: a device tensor travels over it as a host copy (the ranks-share-a-device test
+    hook; RCCL takes device tensors as they are)."""
+    return tensor.is_cuda and dist.get_backend() == "gloo"
+
+
+class _HostStagedWork:
+    """An asynchronous all-reduce(sum) of a device tensor over gloo: the host copy is reduced, wait() copies the sums back."""
+
+    def __init__(self, tensor):
+        self.tensor, self.host = tensor, tensor.cpu()
+        self.work = dist.all_reduce(self.host, op=dist.ReduceOp.SUM, async_op=True)
+
+    def wait(self):
+        self.work.wait()
+        self.tensor.copy_(self.host)
+
+
 def allreduce_sum_(tensor, comm=None):
     """In-place sum over ranks: through `comm` (a OneShotComm) when given, else torch.distributed (RCCL over
-    xGMI for device tensors, gloo for CPU tensors)."""
+    xGMI for device tensors, gloo for CPU tensors and for host copies of device tensors)."""
     if comm is not None:
         return comm.allreduce_sum_(tensor)
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        dist.all_reduce(tensor, op=dist.ReduceOp.SUM)
+        if _through_host(tensor):
+            _HostStagedWork(tensor).wait()
+        else:
+            dist.all_reduce(tensor, op=dist.ReduceOp.SUM)
     return tensor
 
 
@@ -220,7 +241,8 @@ class ShardedMccfr:
             self.comm.begin(buf)
             work = self.comm
         elif self.world_size > 1:
-            work = dist.all_reduce(buf, op=dist.ReduceOp.SUM, async_op=True)
+            work = (_HostStagedWork(buf) if _through_host(buf)
+                    else dist.all_reduce(buf, op=dist.ReduceOp.SUM, async_op=True))
         self._fold_pending()                       # mini-batch k - 1: waits for ITS all-reduce only
         self._pending = (cur, work)
         self._k += 1
@@ -276,9 +298,11 @@ def gather_root_results(local, total_roots):
     pad = max(counts)
     buf = local.new_zeros((pad,) + tuple(local.shape[1:]))
     buf[:local.shape[0]] = local
+    if _through_host(buf):
+        buf = buf.cpu()
     out = [torch.empty_like(buf) for _ in range(world_size)]
     dist.all_gather(out, buf)
-    return torch.cat([o[:c] for o, c in zip(out, counts)])
+    return torch.cat([o[:c] for o, c in zip(out, counts)]).to(local.device)
 
 
 def reduce_root_statistics(child_visits, child_reward):
