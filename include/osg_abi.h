@@ -1019,6 +1019,29 @@ int osg_alpharank(osg_ctx* ctx, int n_players, const int32_t* shape, int64_t n_p
                   const double* tensors /* [n_problems, P, K_0 .. K_{P-1}] */, const osg_alpharank_cfg* cfgs, int64_t n_cfgs,
                   double* pi, double* marginals, double* eps_used, int32_t* iterations, int32_t* status, int on_host);
 
+/* ---- the exact Nash equilibrium of a batch of two-player zero-sum matrix games ---------------------
+ * psro_v2's "nash" (meta_strategies.nash_strategy -> lp_solver.solve_zero_sum_matrix_game) without an LP library: a
+ * primal simplex with Bland's rule on the condensed tableau of  max 1^T y'  s.t.  A' y' <= 1, y' >= 0,  A' the matrix
+ * normalised into [1, 2].  A problem is one matrix [rows, cols], row-major, of the ROW player's payoffs (the row player
+ * maximises); a call holds n_problems of one shape and solves each in one workgroup, the tableau and its labels in LDS
+ * from the first pivot to the last.  csrc/osg_nash_lp.h has every formula, the two constants (eps = 1e-12, exact ratio
+ * ties) and the one order of every operation (the multiply-subtract is not fused).  The bits of a problem's result depend
+ * on its matrix alone, not on its position, on n_problems, on the other problems or on on_host.
+ *   row_strategy [n_problems, rows], col_strategy [n_problems, cols]   an equilibrium pair: no weight is negative and
+ *             each sums to 1 within rounding
+ *   value     [n_problems]: the row player's equilibrium payoff (the column player's is its negative)
+ *   pivots    [n_problems] or NULL: the pivots made
+ *   status    [n_problems]: 0; 1: the matrix has an entry that is not finite; 2: no optimum after 20 000 pivots (a cap
+ *             against cycling on rounding noise; Bland's rule does not cycle in exact arithmetic).  With 1 or 2 the
+ *             problem's strategies and value are NaN; the other problems of the call are unaffected.
+ * on_host = 1: the matrices and every output are host memory and the call returns when the outputs have arrived;
+ * on_host = 0: they are device memory and the launch is enqueued on the context's stream.
+ * A refused call writes nothing.  OSG_ERR_INVALID: a null ctx, n_problems < 0, with n_problems > 0 a null matrices,
+ * row_strategy, col_strategy, value or status.  OSG_ERR_UNSUPPORTED: rows or cols outside 1..64 (the message names both), more than 2^20 problems.
+ * n_problems = 0 with a served shape is OSG_OK and touches nothing (the arrays may then be NULL). */
+int osg_nash_lp(osg_ctx* ctx, int rows, int cols, int64_t n_problems, const double* matrices /* [n_problems, rows, cols] */,
+                double* row_strategy, double* col_strategy, double* value, int32_t* pivots, int32_t* status, int on_host);
+
 /* ---- Deep CFR (open_spiel/python/pytorch/deep_cfr.py) --------------------------------------------
  * The networks are the caller's (torch); the device does what the reference does one tree node per interpreter step:
  * the traversals, the sampled advantages and the reservoir appends.  The arithmetic is

@@ -39,7 +39,7 @@ def __getattr__(name):
     if name == "PSROSolver":
         from . import psro
         return psro.PSROSolver
-    if name in ("meta_solvers", "solve_meta_games", "solve_alpharank"):   # (the reference-named solvers: by the module)
+    if name in ("meta_solvers", "solve_meta_games", "solve_alpharank", "solve_zero_sum_matrix_games"):   # (the reference-named solvers: by the module)
         import importlib
         module = importlib.import_module(".meta_solvers", __name__)
         return module if name == "meta_solvers" else getattr(module, name)

@@ -263,6 +263,7 @@ SIGNATURES = {
     "osg_cfr_aggregate_policies": (INT, [VP, VP, INT, VP, C.c_double, INT, VP]),
     "osg_meta_solve": (INT, [VP, INT, VP, I64, VP, VP, I64, VP, VP, VP, INT]),
     "osg_alpharank": (INT, [VP, INT, VP, I64, VP, VP, I64, VP, VP, VP, VP, VP, INT]),
+    "osg_nash_lp": (INT, [VP, INT, INT, I64, VP, VP, VP, VP, VP, VP, INT]),
     "osg_cfr_infostate_tensors": (INT, [VP, VP, INT]),
     "osg_reservoir_create": (INT, [VP, INT, I64, U64, U64, C.POINTER(VP)]),
     "osg_reservoir_destroy": (INT, [VP]),

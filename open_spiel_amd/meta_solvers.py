@@ -10,7 +10,12 @@ Alpha-rank, psro_v2's default meta-solver (open_spiel/python/egt/alpharank.py), 
 sweep_pi_vs_epsilon, alpharank_strategy and get_alpharank_marginals under the reference's names and defaults, and the
 batched solve_alpharank over osg_alpharank.  Its stationary distributions come from a Grassmann-Taksar-Heyman
 elimination (csrc/osg_alpharank.h) instead of the reference's eigen-solve: no negative masses, small masses accurate to
-a relative 8 n 2^-53, and no "Expected 1 stationary distribution" where the chain is irreducible."""
+a relative 8 n 2^-53, and no "Expected 1 stationary distribution" where the chain is irreducible.
+
+The exact Nash equilibrium of a two-player zero-sum meta-game, psro_v2's "nash" (meta_strategies.nash_strategy over
+lp_solver.solve_zero_sum_matrix_game), is solve_zero_sum_matrix_game(s) and nash_strategy: a simplex with Bland's rule
+in one workgroup's LDS (csrc/osg_nash_lp.h, osg_nash_lp), no LP library.  An equilibrium pair certifies itself:
+min_j (x^T A)_j <= v <= max_i (A y)_i."""
 import ctypes as C
 
 import numpy as np
@@ -41,7 +46,8 @@ def solve_meta_games(ctx, tensors, method, iterations=int(1e5), dt=1e-3, gamma=1
     return_last the last iterate as well.  device=True: tensors and initial are float64 torch tensors on the context's
     device, and so are the results, which are enqueued on its stream; otherwise NumPy arrays."""
     if method not in METHODS:
-        raise OsgError(f"solve_meta_games: method must be 'prd' or 'rm', not {method!r}")
+        raise OsgError(f"solve_meta_games: method must be 'prd' or 'rm', not {method!r} (the exact Nash equilibrium of a "
+                       "two-player zero-sum meta-game is 'nash_lp': solve_zero_sum_matrix_games, nash_strategy)")
     if form not in FORMS:
         raise OsgError(f"solve_meta_games: form must be None, 'lds' or 'global', not {form!r}")
     if device:
@@ -219,3 +225,61 @@ def alpharank_strategy(ctx, payoff_tensors, return_joint=False, **unused_kwargs)
     if return_joint:
         return marginals, (np.array(out["pi"][0]) if len(tables) == 1 else np.array(out["pi"][0]).reshape(tables[0].shape))
     return marginals
+
+
+# ---- the exact Nash equilibrium of a two-player zero-sum meta-game (psro_v2's "nash"; lp_solver.py) ----
+def solve_zero_sum_matrix_games(ctx, matrices, device=False):
+    """The batched form: one call of osg_nash_lp.  matrices [B, rows, cols]: B zero-sum matrix games of one shape, each the
+    ROW player's payoffs (the row player maximises); rows and cols from 1 to 64.  Returns a dict: row [B, rows] and col
+    [B, cols], an equilibrium pair per game; value [B], the row player's; pivots [B]; status [B] (0; 1: an entry is not
+    finite; 2: no optimum after 20 000 pivots; with 1 or 2 the game's strategies and value are NaN).  device=True: matrices
+    is a float64 torch tensor on the context's device and so are the results, which are enqueued on its stream; otherwise
+    NumPy arrays."""
+    if device:
+        t = torch.as_tensor(matrices, dtype=torch.float64, device=ctx.device).contiguous()
+        addr = lambda x: x.data_ptr()
+        empty = lambda shape, kind=torch.float64: torch.empty(shape, dtype=kind, device=ctx.device)
+        i32 = torch.int32
+    else:
+        t = np.ascontiguousarray(matrices, np.float64)
+        addr = lambda x: x.ctypes.data
+        empty = lambda shape, kind=np.float64: np.empty(shape, kind)
+        i32 = np.int32
+    if t.ndim != 3:
+        raise OsgError(f"solve_zero_sum_matrix_games: expected matrices of shape [B, rows, cols], not {tuple(t.shape)}")
+    B, rows, cols = (int(k) for k in t.shape)
+    out = dict(row=empty((B, rows)), col=empty((B, cols)), value=empty((B,)), pivots=empty((B,), i32), status=empty((B,), i32))
+    check(lib().osg_nash_lp(ctx._h, rows, cols, B, addr(t), addr(out["row"]), addr(out["col"]), addr(out["value"]),
+                            addr(out["pivots"]), addr(out["status"]), 0 if device else 1))
+    return out
+
+
+def solve_zero_sum_matrix_game(ctx, matrix):
+    """lp_solver.solve_zero_sum_matrix_game on the device: (p0, p1, v0, v1) for the row player's payoff matrix (the
+    reference takes a pyspiel matrix game; its row utilities are this matrix).  A matrix that is not finite is a
+    ValueError, a solve that found no optimum a RuntimeError."""
+    out = solve_zero_sum_matrix_games(ctx, np.asarray(matrix, np.float64)[None])
+    status = int(out["status"][0])
+    if status == 1:
+        raise ValueError("solve_zero_sum_matrix_game: the payoff matrix has an entry that is not finite")
+    if status == 2:
+        raise RuntimeError(f"solve_zero_sum_matrix_game: no optimum after {int(out['pivots'][0])} pivots")
+    value = float(out["value"][0])
+    return np.array(out["row"][0]), np.array(out["col"][0]), value, -value
+
+
+def nash_strategy(ctx, payoff_tensors, return_joint=False, **unused_kwargs):
+    """psro_v2/meta_strategies.nash_strategy on payoff tensors: the exact equilibrium of a two-player zero-sum meta-game,
+    one weight vector per player, and with return_joint the product distribution [K_0, K_1] as well.  The two tables
+    must be zero-sum (max |T0 + T1| <= 1e-9 max(1, max |T0|): a guard against a general-sum game, not an accuracy
+    claim); the solve is on T0."""
+    tables = [np.asarray(x, np.float64) for x in payoff_tensors]
+    if len(tables) != 2:
+        raise NotImplementedError("nash_strategy solver works only for 2p zero-sum"
+                                  "games, but was invoked for a {} player game".format(len(tables)))
+    if tables[0].ndim != 2 or tables[0].shape != tables[1].shape:
+        raise ValueError(f"nash_strategy: expected two tables of one shape [K_0, K_1], not {[t.shape for t in tables]}")
+    if not np.abs(tables[0] + tables[1]).max() <= 1e-9 * max(1.0, np.abs(tables[0]).max()):
+        raise ValueError("nash_strategy: the meta-game is not zero-sum (or not finite)")
+    p0, p1, _, _ = solve_zero_sum_matrix_game(ctx, tables[0])
+    return ([p0, p1], np.outer(p0, p1)) if return_joint else [p0, p1]
