@@ -1024,7 +1024,7 @@ int osg_alpharank(osg_ctx* ctx, int n_players, const int32_t* shape, int64_t n_p
  * primal simplex with Bland's rule on the condensed tableau of  max 1^T y'  s.t.  A' y' <= 1, y' >= 0,  A' the matrix
  * normalised into [1, 2].  A problem is one matrix [rows, cols], row-major, of the ROW player's payoffs (the row player
  * maximises); a call holds n_problems of one shape and solves each in one workgroup, the tableau and its labels in LDS
- * from the first pivot to the last.  csrc/osg_nash_lp.h has every formula, the two constants (eps = 1e-12, exact ratio
+ * from the first pivot to the last.  csrc/osg_nash_lp.h has every formula, the constants (eps = 1e-12, pivots above 1e-9, exact
  * ties) and the one order of every operation (the multiply-subtract is not fused).  The bits of a problem's result depend
  * on its matrix alone, not on its position, on n_problems, on the other problems or on on_host.
  *   row_strategy [n_problems, rows], col_strategy [n_problems, cols]   an equilibrium pair: no weight is negative and

@@ -8,6 +8,8 @@
 //
 // Normalise.  lo = min A, span = max A - lo, A' = (A - lo) / span + 1 in [1, 2] (span = 0, a constant matrix: A' = 1).
 //   Equilibria do not change and the value of A' is at least 1 > 0.  An entry that is not finite: status 1, NaN outputs.
+//   A finite matrix whose max A - lo overflows is normalised from its halved entries (nl_range: every entry, lo and the
+//   span times 0.5, the value times 2 at the end); every other matrix keeps factors of 1, which change no bit.
 // LP.  maximise 1^T y' subject to A' y' <= 1, y' >= 0: y = y' / sum y', the value of A' is 1 / sum y', and the duals
 //   x' of the rows give x the same way.  y' = 0 is feasible and A' >= 1 bounds the LP: no phase 1.
 // Tableau.  t [m + 1, n + 1] at t[i * ld + j]: rows 0 .. m-1 are the constraints (the slacks are the first basis),
@@ -15,7 +17,7 @@
 //   CONDENSED: only the non-basic columns are kept, and a pivot swaps the label of its column with the label of its
 //   row.  Labels: 0 .. n-1 the variables y', n .. n+m-1 the slacks.
 // Entering column (Bland): of the columns j < n with t[m][j] < -kNlEps the one with the smallest label; none: optimal.
-// Leaving row: of the rows i < m with t[i][c] > kNlEps those with the smallest ratio t[i][n] / t[i][c]; of these the
+// Leaving row: of the rows i < m with t[i][c] > kNlPivotEps those with the smallest ratio t[i][n] / t[i][c]; of these the
 //   one with the smallest label.  No such row (impossible for a bounded LP in exact arithmetic): status 2.
 // Pivot on p = t[r][c], every element from the values BEFORE the pivot:
 //     t[r][j] = t[r][j] / p            j != c         (nl_scaled)
@@ -40,16 +42,24 @@
 namespace osg {
 
 constexpr int kNlMaxSide = 64;          // rows, cols: a wavefront holds a row or a column of labels, one per lane
-// A reduced cost above -kNlEps does not enter and an entry at or below kNlEps is no pivot.  The normalised entries lie in
-// [1, 2] and a few hundred rank-1 updates leave rounding noise of 1e-15 .. 1e-13 on an entry that is 0 in exact
-// arithmetic; 1e-12 lies above that noise, so it is never pivoted on or chased as an improvement, and below the
-// certificate's bound: a reduced cost that is ignored costs the duality gap at most kNlEps * sum y' <= 1e-12.
+// A reduced cost above -kNlEps does not enter.  The normalised entries lie in [1, 2] and a few hundred rank-1 updates
+// leave rounding noise on an entry that is 0 in exact arithmetic: mostly 1e-17 .. 1e-13, up to 3e-11 where Bland's rule
+// has divided by small true entries (1e-6, 1e-5) on the way.  A reduced cost of that size that is chased costs a pivot
+// or two; one that is ignored costs the duality gap at most kNlEps * sum y' <= 1e-12, below the certificate's bound.
 constexpr double kNlEps = 1e-12;
+// An entry at or below kNlPivotEps is no pivot.  Dividing by noise is the one mistake the tableau does not recover from,
+// so this is not the reduced costs' threshold, as it once was: at a degenerate vertex of a 63 x 64 table over
+// {-1, 0, 1} an exact zero that had become 1.04e-12 was pivoted on, which put a linearly dependent column into the
+// basis, and the solve ended "optimal" 570 pivots later with a duality gap of 0.087.  1e-9 lies between the noise
+// (3e-11 at the most over the tested matrices) and the smallest true entries met in a pivot column (1e-6).  A true
+// entry e below it that is passed over lets its row's right-hand side end at -e * ratio at the worst, which the
+// read-out clamps.
+constexpr double kNlPivotEps = 1e-9;
 // Ratios tie only when they are EQUAL.  A degenerate vertex has right-hand sides that are exactly 0 (0 - c * 0), so its
 // ties are exact and Bland's smallest-label rule sees them all; a tolerance would make "tie" intransitive, and the
 // choice among near-ties would no longer be a minimum-ratio choice, which Bland's termination argument needs.
 constexpr double kNlRatioTie = 0.0;
-// A safety cap against cycling on rounding noise, not a tuning figure: the listed cases need fewer than 500 pivots.
+// A safety cap against cycling on rounding noise, not a tuning figure: the tested matrices need fewer than 700 pivots.
 constexpr int kNlMaxPivots = 20000;
 enum NlStatus { kNlOk = 0, kNlNotFinite = 1, kNlNoOptimum = 2 };
 
@@ -59,9 +69,16 @@ OSG_HD bool nl_is_finite(double x) { return x - x == 0.0; }
 // pairs of LDS banks (2 * ld * i mod 64 takes every even value once) while a row's elements are consecutive anyway.
 OSG_HD int nl_stride(int cols) { return (cols + 1) | 1; }
 
+// What a matrix with the minimum lo and the maximum hi is normalised with: entry * pre, then (.. - base) / span + 1.
+// pre is 1 unless hi - lo overflows (then 0.5: the halves' difference is finite), and nl_value's result is divided by it.
+OSG_HD void nl_range(double lo, double hi, double* pre, double* base, double* span) {
+  *pre = nl_is_finite(hi - lo) ? 1.0 : 0.5;
+  *base = lo * *pre;
+  *span = hi * *pre - *base;
+}
 OSG_HD double nl_normalise(double a, double lo, double span) { return span > 0.0 ? (a - lo) / span + 1.0 : 1.0; }
 OSG_HD bool nl_enters(double cost) { return cost < -kNlEps; }
-OSG_HD bool nl_pivotable(double entry) { return entry > kNlEps; }
+OSG_HD bool nl_pivotable(double entry) { return entry > kNlPivotEps; }
 OSG_HD double nl_ratio(double rhs, double entry) { return rhs / entry; }
 OSG_HD bool nl_ties(double ratio, double best) { return ratio - best <= kNlRatioTie; }   // (best is the minimum)
 OSG_HD double nl_scaled(double t, double p) { return t / p; }
@@ -102,10 +119,11 @@ inline int nl_solve(const double* a, int m, int n, double* t, int* row_label, in
     lo = a[e] < lo ? a[e] : lo;
     hi = a[e] > hi ? a[e] : hi;
   }
-  const double span = hi - lo;
+  double pre, base, span;
+  nl_range(lo, hi, &pre, &base, &span);
   if (status == kNlOk) {
     for (int i = 0; i <= m; ++i)
-      for (int j = 0; j <= n; ++j) t[i * ld + j] = i < m ? (j < n ? nl_normalise(a[i * n + j], lo, span) : 1.0) : (j < n ? -1.0 : 0.0);
+      for (int j = 0; j <= n; ++j) t[i * ld + j] = i < m ? (j < n ? nl_normalise(a[i * n + j] * pre, base, span) : 1.0) : (j < n ? -1.0 : 0.0);
     for (int j = 0; j < n; ++j) col_label[j] = j;
     for (int i = 0; i < m; ++i) row_label[i] = n + i;
   }
@@ -156,7 +174,7 @@ inline int nl_solve(const double* a, int m, int n, double* t, int* row_label, in
   const double sy = nl_sum(y, n), sx = nl_sum(x, m);
   for (int i = 0; i < m; ++i) x[i] = x[i] / sx;
   for (int j = 0; j < n; ++j) y[j] = y[j] / sy;
-  *value = nl_value(sy, span, lo);
+  *value = nl_value(sy, span, base) / pre;
   return status;
 }
 

@@ -128,10 +128,11 @@ __global__ void __launch_bounds__(kNlThreads) k_nash_lp(NlCall c) {
     lo = yv[w] < lo ? yv[w] : lo;
     hi = yv[kNlWaves + w] > hi ? yv[kNlWaves + w] : hi;
   }
-  const double span = hi - lo;
+  double pre, base, span;
+  nl_range(lo, hi, &pre, &base, &span);
   for (int e = tid; e < m * n; e += kNlThreads) {
     double* cell = t + (e / n) * ld + e % n;
-    *cell = nl_normalise(*cell, lo, span);
+    *cell = nl_normalise(*cell * pre, base, span);
   }
   for (int i = tid; i < m; i += kNlThreads) { t[i * ld + n] = 1.0; row_label[i] = n + i; }
   for (int j = tid; j < n; j += kNlThreads) { t[m * ld + j] = -1.0; col_label[j] = j; }
@@ -201,7 +202,7 @@ __global__ void __launch_bounds__(kNlThreads) k_nash_lp(NlCall c) {
     const double total = wave_nl_sum(mine, n);
     if (lane < n) c.y[b * n + lane] = mine / total;
     if (lane == 0) {
-      c.value[b] = nl_value(total, span, lo);
+      c.value[b] = nl_value(total, span, base) / pre;
       if (c.pivots) c.pivots[b] = done;
       c.status[b] = kNlOk;
     }

@@ -64,8 +64,9 @@ Answer as_the_kernel(const std::vector<double>& a, int m, int n) {
     hi = a[e] > hi ? a[e] : hi;
   }
   if (out.status != kNlOk) return out;
-  const double span = hi - lo;
-  for (int e = 0; e < m * n; ++e) t[(e / n) * ld + e % n] = nl_normalise(a[e], lo, span);
+  double pre, base, span;
+  nl_range(lo, hi, &pre, &base, &span);
+  for (int e = 0; e < m * n; ++e) t[(e / n) * ld + e % n] = nl_normalise(a[e] * pre, base, span);
   for (int i = 0; i < m; ++i) { t[i * ld + n] = 1.0; row_label[i] = n + i; }
   for (int j = 0; j < n; ++j) { t[m * ld + j] = -1.0; col_label[j] = j; }
   for (;;) {
@@ -114,7 +115,7 @@ Answer as_the_kernel(const std::vector<double>& a, int m, int n) {
   const double sy = nl_sum(yv.data(), n), sx = nl_sum(xv.data(), m);
   for (int i = 0; i < m; ++i) out.x[i] = xv[i] / sx;
   for (int j = 0; j < n; ++j) out.y[j] = yv[j] / sy;
-  out.v[0] = nl_value(sy, span, lo);
+  out.v[0] = nl_value(sy, span, base) / pre;
   return out;
 }
 

@@ -2,9 +2,17 @@
 tests/native/nash_lp_host_test.cpp runs the header's functions in the kernel's arrangement and through nl_solve on every
 case of nash_lp_cases.CASES.  Both must give the NumPy restatement's x, y, v and pivot count bit for bit; the program is
 built once more with the address and undefined-behaviour sanitizers, as a stand-alone binary, and run.  The restatement's
-answers pass the certificate against HiGHS."""
+answers pass the certificate against HiGHS.
+
+The same on the generated sweep (nash_lp_cases.sweep: all 100 ordered pairs of ten side lengths next to the kernel's
+layout edges, nine families): status 0, the certificate without a solver, what each family is known by (an analytic
+value, a saddle point, a constant), HiGHS's value on one matrix per family, and the host program bit for bit.  Then what
+must hold between solves: a power-of-two multiple changes nothing but the value's exponent, the transposed negative has
+the negated value, a permutation keeps it; and the ends of the fp64 range, a span that overflows and one that is
+subnormal."""
 import subprocess
 
+import numpy as np
 import pytest
 
 import nash_lp_cases as nc
@@ -31,3 +39,80 @@ def test_the_restatement_passes_the_certificate(name):
     x, y, v, pivots, status = nc.restated(name)
     assert pivots <= 1000   # (the cap of 20 000 is far away)
     nc.certify(nc.CASES[name], x, y, v, status, name)
+
+
+# ---- the sweep ----
+@pytest.fixture(scope="module")
+def swept():
+    return {k: nc.solve(nc.sweep_matrix(*k)) for k in nc.sweep()}
+
+
+@pytest.mark.parametrize("m", nc.SIDES)
+def test_the_sweep_passes_the_certificate_and_its_family_property(swept, m):
+    for n in nc.SIDES:
+        for family in nc.families(m, n):
+            A, (x, y, v, pivots, status), what = nc.sweep_matrix(m, n, family), swept[m, n, family], f"{family} {m}x{n}"
+            assert status == 0 and pivots < nc.MAX_PIVOTS, what
+            b = nc.sweep_bound(family)
+            g = nc.certificate(A, x, y, v, status, b, what)
+            print(f"{what}: {pivots} pivots, gap {g:.3g} (relative; bound {b:.3g})")
+            nc.family_property(family, A, x, y, v, b, what)
+
+
+@pytest.mark.parametrize("family", nc.FAMILIES)
+def test_the_sweep_has_the_value_of_highs(swept, family):
+    x, y, v, pivots, status = swept[33, 33, family]
+    dv = nc.value_against_highs(nc.sweep_matrix(33, 33, family), v, nc.sweep_bound(family), family)
+    print(f"{family} 33x33: |v - v_highs| {dv:.3g} (relative; bound {nc.sweep_bound(family):.3g})")
+
+
+def _scaled():
+    return [(name, k, np.ldexp(A, k)) for name, A in nc.scaling_matrices().items() for k in nc.SCALINGS]
+
+
+def test_header_functions_reproduce_the_restatement_on_the_sweep_bit_for_bit(tmp_path, swept):
+    solved = [(nc.sweep_matrix(*k), answer) for k, answer in swept.items()]
+    solved += [(A, nc.solve(A)) for _, A, _ in nc.range_cases()] + [(A, nc.solve(A)) for _, _, A in _scaled()]
+    nc.write_matrices(tmp_path / "sweep.bin", solved)
+    exe = nc.build_host_test(str(tmp_path / "nash_lp_host_test"))
+    r = subprocess.run([exe, str(tmp_path / "sweep.bin")], capture_output=True, text=True, timeout=300)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.stdout.rstrip().endswith(f"ok: {len(solved)} cases, both arrangements, bit-equal to the restatement") and "FAILED" not in r.stdout
+
+
+# ---- between solves ----
+@pytest.mark.parametrize("name", list(nc.scaling_matrices()))
+def test_a_power_of_two_multiple_changes_only_the_values_exponent(name):
+    A = nc.scaling_matrices()[name]
+    x, y, v, pivots, status = nc.solve(A)
+    assert status == 0
+    for k in nc.SCALINGS:
+        xk, yk, vk, pivots_k, status_k = nc.solve(np.ldexp(A, k))
+        assert status_k == 0 and pivots_k == pivots and np.array_equal(xk, x) and np.array_equal(yk, y), (name, k)
+        assert vk == np.ldexp(v, k) and np.isfinite(vk), (name, k)
+
+
+@pytest.mark.parametrize("name", list(nc.scaling_matrices()))
+def test_the_transposed_negative_and_a_permutation_keep_the_value(name):
+    A, b = nc.scaling_matrices()[name], nc.bound()
+    x, y, v, _, status = nc.solve(A)
+    xt, yt, vt, _, status_t = nc.solve(-A.T)
+    nc.certificate(-A.T, xt, yt, vt, status_t, b, name)
+    assert status == 0 and abs(vt + v) <= b * nc.scale(A), (name, vt, v)
+    rng = np.random.default_rng(9300)
+    rows, cols = rng.permutation(A.shape[0]), rng.permutation(A.shape[1])
+    P = A[rows][:, cols]
+    xp, yp, vp, _, status_p = nc.solve(P)
+    nc.certificate(P, xp, yp, vp, status_p, b, name)
+    assert abs(vp - v) <= b * nc.scale(A), (name, vp, v)
+    nc.certificate(A, xp[np.argsort(rows)], yp[np.argsort(cols)], vp, status_p, b, name)   # the pair, carried back
+
+
+# ---- the fp64 range ----
+@pytest.mark.parametrize("case", nc.range_cases(), ids=lambda c: c[0])
+def test_a_span_that_overflows_or_is_subnormal(case):
+    name, A, k = case
+    x, y, v, pivots, status = nc.solve(A)
+    g = nc.certify_range(A, k, x, y, v, status, nc.bound(), name)
+    print(f"{name}: v {v!r}, {pivots} pivots, gap {g:.3g} on the matrix times 2**{k}")

@@ -1,7 +1,12 @@
 """The exact Nash meta-solver on the device (osg_nash_lp in include/osg_abi.h; open_spiel_amd.meta_solvers;
 PSROSolver(meta_solver="nash_lp")) against the NumPy restatement of open_spiel_amd/csrc/osg_nash_lp.h (nash_lp_cases.solve:
 array_equal, since both evaluate the one order the header fixes without fused multiply-adds) and against the certificate
-of a Nash pair with HiGHS's value (nash_lp_cases.certify)."""
+of a Nash pair with HiGHS's value (nash_lp_cases.certify).
+
+The generated sweep (nash_lp_cases.sweep) walks the kernel's layout edges: 64 columns (lane 0's second column), fewer
+rows or columns than lanes, strides next to 32 and 64, more cells than threads, and LDS above the default cap.  Every
+matrix of it, the ends of the fp64 range and the power-of-two multiples must equal the restatement, whose answers
+tests/test_nash_lp_native.py certifies on the CPU, wherever the problem sits in a batch of 4096."""
 import numpy as np
 import pytest
 
@@ -95,3 +100,76 @@ def test_psro_with_the_device_nash_solver_is_psro_with_the_restatement(ctx, game
     assert all(np.array_equal(a, b) for a, b in zip(on_device.meta_games(), on_host.meta_games()))
     assert all(np.array_equal(a, b) for a, b in zip(on_device.policies(), on_host.policies()))
     assert any(not np.allclose(w, 1.0 / len(w)) for w in got), "the meta-strategies stayed uniform"
+
+
+# ---- the sweep ----
+_SWEPT = {}
+
+
+def _swept(m, n, family):
+    if (m, n, family) not in _SWEPT:
+        _SWEPT[m, n, family] = nc.solve(nc.sweep_matrix(m, n, family))
+    return _SWEPT[m, n, family]
+
+
+def _both_ways(ctx, batch):
+    """The batch through host pointers and through device pointers."""
+    import torch
+    import open_spiel_amd.meta_solvers as ms
+    on_device = ms.solve_zero_sum_matrix_games(ctx, torch.as_tensor(batch, device=ctx.device), device=True)
+    return ms.solve_zero_sum_matrix_games(ctx, batch), {k: v.cpu().numpy() for k, v in on_device.items()}
+
+
+def _without_pivots(ctx, batch):
+    """osg_nash_lp with a null `pivots`, which the ABI allows and the Python wrapper never passes."""
+    from open_spiel_amd._abi import check, lib
+    B, rows, cols = batch.shape
+    out = dict(row=np.empty((B, rows)), col=np.empty((B, cols)), value=np.empty(B), status=np.empty(B, np.int32))
+    check(lib().osg_nash_lp(ctx._h, rows, cols, B, batch.ctypes.data, out["row"].ctypes.data, out["col"].ctypes.data,
+                            out["value"].ctypes.data, None, out["status"].ctypes.data, 1))
+    return out
+
+
+@pytest.mark.parametrize("m", nc.SIDES)
+def test_device_is_the_restatement_on_the_sweep(ctx, m):
+    for n in nc.SIDES:
+        families = nc.families(m, n)
+        batch = np.stack([nc.sweep_matrix(m, n, f) for f in families])
+        outs = _both_ways(ctx, batch)
+        for k, family in enumerate(families):
+            for out in outs:
+                _same(out, k, _swept(m, n, family), f"{family} {m}x{n}")
+        if n == m:
+            bare = _without_pivots(ctx, batch)
+            assert all(np.array_equal(bare[key], outs[0][key], equal_nan=True) for key in bare), f"{m}x{n}, pivots null"
+
+
+def test_device_is_the_restatement_at_the_ends_of_the_range_and_on_power_of_two_multiples(ctx):
+    extra = [(name, A) for name, A, _ in nc.range_cases()]
+    extra += [(f"{name} * 2**{k}", np.ldexp(A, k)) for name, A in nc.scaling_matrices().items() for k in (0, *nc.SCALINGS)]
+    for shape in sorted({A.shape for _, A in extra}):
+        names, batch = zip(*[(name, A) for name, A in extra if A.shape == shape])
+        for out in _both_ways(ctx, np.stack(batch)):
+            for k, name in enumerate(names):
+                _same(out, k, nc.solve(batch[k]), name)
+    for name, A in nc.scaling_matrices().items():   # device against device: the same bits, the value's exponent moved
+        out = _both_ways(ctx, np.stack([np.ldexp(A, k) for k in (0, *nc.SCALINGS)]))[1]
+        for at, k in enumerate(nc.SCALINGS, 1):
+            assert all(np.array_equal(out[key][at], out[key][0]) for key in ("row", "col", "pivots", "status")), (name, k)
+            assert out["value"][at] == np.ldexp(out["value"][0], k), (name, k)
+
+
+@pytest.mark.parametrize("m", nc.SIDES)
+def test_a_sweep_problems_bits_do_not_depend_on_its_place_among_4096(ctx, m):
+    import torch
+    import open_spiel_amd.meta_solvers as ms
+    for n in nc.SIDES:
+        families = nc.families(m, n)
+        rng = np.random.default_rng(m * 100 + n)
+        which = rng.permutation(np.arange(4096) % len(families))
+        stack = torch.as_tensor(np.stack([nc.sweep_matrix(m, n, f) for f in families]), device=ctx.device)
+        out = ms.solve_zero_sum_matrix_games(ctx, stack[torch.as_tensor(which, device=ctx.device)], device=True)
+        places = np.sort(rng.choice(4096, 64, replace=False))
+        out = {key: v[torch.as_tensor(places, device=ctx.device)].cpu().numpy() for key, v in out.items()}
+        for k, place in enumerate(places):
+            _same(out, k, _swept(m, n, families[which[place]]), f"{families[which[place]]} {m}x{n} at {place}")
