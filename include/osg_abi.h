@@ -1144,6 +1144,50 @@ int osg_nfsp_collect(osg_cfr* s, const float* d_q, const float* d_avg_probs, con
 int osg_nfsp_staged(osg_cfr* s, int64_t* sizes, int64_t* d_ring_offsets, int32_t* d_ring_info, int32_t* d_ring_action,
                     float* d_ring_reward, int32_t* d_ring_next_info, uint8_t* d_ring_final, int64_t* d_sl_offsets,
                     int32_t* d_sl_info, float* d_sl_probs, int32_t* d_draws, int32_t* d_modes);
+/* ---- the fused learner of NFSP and DQN --------------------------------------------------------
+ * DQN.learn (dqn.py:501-569) and NFSP._learn (nfsp.py:364-409) with SGD, for every update a chunk of self-play owes,
+ * in one launch: the batches are drawn by two batched calls, and one workgroup per network runs its updates one after
+ * another with the weights, the batch and the activations in LDS (open_spiel_amd/csrc/osg_mlp_train.hip; the layout
+ * is osg_mlp_plan.h).
+ *
+ * osg_transition_ring_sample_many / osg_reservoir_sample_many: d_slots [n_streams, m] i64 (device); row u is what
+ *   osg_transition_ring_sample / osg_reservoir_sample return for streams[u] (host array), whatever n_streams and u.
+ *   A workgroup per stream recomputes every key, keeps those below a threshold near (2 m + 16) / size * 2^64 in LDS —
+ *   widening it fourfold while fewer than m qualify, halving it while the list overflows — and orders them by
+ *   (key, slot).  1 <= m <= 1024, m <= rows held, n_streams >= 1; else OSG_ERR_INVALID.
+ * osg_nfsp_learn: n_jobs networks, job j's `updates` sequential SGD updates by workgroup j.  kind 0 (DQN): rows of `ring`;
+ *   target = reward at a final row, else reward + discount * (max over the legal next actions of the target network);
+ *   loss 0 mse, 1 huber (F.smooth_l1_loss(beta = huber_beta)) of the online network's value at the taken action, mean over
+ *   the batch.  kind 1 (supervised): rows of `reservoir`; softmax over the LEGAL logits (illegal ids take no part and get
+ *   gradient 0: the value and gradient the reference's finfo.min penalty gives), cross-entropy against the stored
+ *   probabilities, mean over the batch; clip > 0: nn.utils.clip_grad_norm_(clip) before the step.
+ *   widths [n_linear + 1]: inputs S, the hidden widths, outputs A; d_params: the flat fp32 parameters in nn.Linear layout
+ *   (weight [out, in], then bias, per layer), updated in place; d_target_params the same, read only (kind 0);
+ *   d_tensors [infostates, S] f32, d_legal_mask [infostates, A] u8; d_slots [updates, batch] i64 from the calls above;
+ *   d_loss [updates] f32 (NaN for an update that met a slot, infostate or action out of range: such a row counts as
+ *   zeros).  fp32 throughout (v_mfma_f32_16x16x4_f32), every sum in one fixed order, no floating-point atomics: a job's
+ *   bits do not depend on the other jobs.  Does not wait.  Served: n_linear 2 or 3, hidden widths 1..128, S <= 256,
+ *   A <= 16, batch 1..128, and what fits the device's LDS per workgroup; the rest is OSG_ERR_UNSUPPORTED. */
+typedef struct osg_nfsp_learn_job {
+  int32_t kind, n_linear;
+  int32_t widths[4];
+  int32_t batch, loss;
+  int64_t updates, infostates;
+  float* d_params;
+  const float* d_target_params;
+  const float* d_tensors;
+  const uint8_t* d_legal_mask;
+  osg_transition_ring* ring;
+  osg_reservoir* reservoir;
+  const int64_t* d_slots;
+  float* d_loss;
+  double learning_rate, discount, huber_beta, clip;
+} osg_nfsp_learn_job;
+int osg_transition_ring_sample_many(osg_transition_ring* ring, uint64_t seed, const uint64_t* streams, int64_t n_streams, int64_t m,
+                                    int64_t* d_slots);
+int osg_reservoir_sample_many(osg_reservoir* buf, uint64_t seed, const uint64_t* streams, int64_t n_streams, int64_t m,
+                              int64_t* d_slots);
+int osg_nfsp_learn(osg_ctx* ctx, const osg_nfsp_learn_job* jobs, int64_t n_jobs);
 
 /* ---- multi-GPU exchange step ---------------------------------------------------
  * One process per GPU.  Units shard by global index with no data-path collective; the ONE exchange

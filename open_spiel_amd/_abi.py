@@ -54,6 +54,31 @@ class MctsCfg(C.Structure):
     ]
 
 
+class NfspLearnJob(C.Structure):
+    """osg_nfsp_learn_job: one network and its sequential SGD updates (kind 0 DQN, 1 supervised)."""
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("n_linear", C.c_int32),
+        ("widths", C.c_int32 * 4),
+        ("batch", C.c_int32),
+        ("loss", C.c_int32),
+        ("updates", C.c_int64),
+        ("infostates", C.c_int64),
+        ("d_params", C.c_void_p),
+        ("d_target_params", C.c_void_p),
+        ("d_tensors", C.c_void_p),
+        ("d_legal_mask", C.c_void_p),
+        ("ring", C.c_void_p),
+        ("reservoir", C.c_void_p),
+        ("d_slots", C.c_void_p),
+        ("d_loss", C.c_void_p),
+        ("learning_rate", C.c_double),
+        ("discount", C.c_double),
+        ("huber_beta", C.c_double),
+        ("clip", C.c_double),
+    ]
+
+
 class AbCfg(C.Structure):
     _fields_ = [
         ("depth_limit", C.c_int32),
@@ -283,6 +308,9 @@ SIGNATURES = {
     "osg_transition_ring_rows": (INT, [VP, VP, I64, VP, VP, VP, VP, VP]),
     "osg_nfsp_collect": (INT, [VP, VP, VP, VP, VP, U64, I64, I64, VP, VP, VP]),
     "osg_nfsp_staged": (INT, [VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    "osg_transition_ring_sample_many": (INT, [VP, U64, VP, I64, I64, VP]),
+    "osg_reservoir_sample_many": (INT, [VP, U64, VP, I64, I64, VP]),
+    "osg_nfsp_learn": (INT, [VP, VP, I64]),
     "osg_cfr_infostate_key": (INT, [VP, I64, C.c_char_p, INT]),
     "osg_cfr_best_response_history_values": (INT, [VP, INT, VP, INT, VP]),
     "osg_cfr_tree_edges": (INT, [VP, VP, VP]),

@@ -14,6 +14,7 @@
 //   osg_cfr_efr.hip     k_efr_resident, k_efr_*       extensive-form regret minimization (osg_efr.h has the arithmetic)
 //   osg_deep_cfr.hip    k_dcfr_*, k_res_*             Deep CFR traversals and reservoir buffers (osg_deep_cfr.h has the arithmetic)
 //   osg_nfsp.hip        k_nfsp_*, k_ring_*            NFSP self-play episodes and the DQN transition ring (osg_nfsp.h has the arithmetic)
+//   osg_mlp_train.hip   k_mlp_train                   the fused NFSP / DQN learner: a workgroup per network, LDS layout in osg_mlp_plan.h
 //
 // Every kernel is launched from the translation unit that defines it; what crosses the units are the device-side
 // argument structs below (views: raw pointers), the per-family plans that own the memory behind them (SplitPlan,
@@ -715,6 +716,17 @@ int deep_supported(const osg_cfr* s, const char* who);   // what Deep CFR and NF
 bool reservoir_serves(const osg_reservoir* b, const osg_cfr* s);   // the solver's row width and context
 // m sequential appends of device rows, in row order (osg_reservoir_append without its argument checks)
 int reservoir_append(osg_reservoir* b, int64_t m, const int32_t* d_info, int32_t iteration, const float* d_values);
+// What the fused learner (osg_mlp_train.hip) reads of a buffer: its filled rows, column by column (device pointers).
+struct ReservoirView { osg_ctx* ctx; int A; int64_t size; const int32_t* info; const float* vals; };
+ReservoirView reservoir_view(const osg_reservoir* b);
+// d_slots [U, m]: for every stream id the m filled slots with the smallest dcfr_sample_key(seed, stream, slot),
+// ascending by (key, slot): k_sample_many, a workgroup per stream, nothing materialised and nothing sorted globally.
+// d_streams: the buffer's own grow-only home of the stream ids on the device.
+int sample_many(osg_ctx* ctx, const char* who, int64_t size, uint64_t seed, const uint64_t* streams, int64_t U, int64_t m,
+                DeviceArray<uint64_t>& d_streams, int64_t* d_slots);
+// ---- osg_nfsp.hip ----
+struct RingView { osg_ctx* ctx; int64_t size; const int32_t* info; const int32_t* action; const float* reward; const int32_t* next; const uint8_t* final_; };
+RingView ring_view(const osg_transition_ring* b);
 // ---- osg_cfr_efr.hip ----
 bool efr_mode(const osg_cfr* s);       // osg_efr_set_deviations was accepted
 int efr_after_reset(osg_cfr* s);       // R and y back to 0

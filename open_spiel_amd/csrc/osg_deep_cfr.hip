@@ -25,6 +25,7 @@ struct osg_reservoir {
   DeviceArray<uint64_t> d_key_in, d_key_out;
   DeviceArray<int64_t> d_slot_in, d_slot_out;
   DeviceArray<unsigned char> d_tmp;
+  DeviceArray<uint64_t> d_streams;      // the stream ids of the last osg_reservoir_sample_many
 };
 
 namespace {
@@ -69,9 +70,102 @@ __global__ void k_res_keys(uint64_t* key, int64_t* slot, uint64_t seed, uint64_t
   slot[k] = k;
 }
 
+
+// ---- batched draws --------------------------------------------------------------------------------------------------------
+// One workgroup per stream.  The keys are uniform 64-bit values, so the m-th smallest of `size` lies near m / size * 2^64:
+// a pass over the slots recomputes every key and keeps those at or below `limit` (the host's (2 m + 16) / size * 2^64) in
+// an LDS list; fewer than m: four times the limit and again; more than the list holds: half of it and again.  Either way
+// the list then holds EVERY key at or below the limit, so its m smallest are the m smallest of all: exact.  The list is
+// filled in any order (an integer counter in LDS) and then put in order by (key, slot) — a bitonic network over the next
+// power of two, padded with the largest pair — so the row does not depend on who came first.
+constexpr int kSampleCap = 4096;       // candidates: 48 KB of LDS
+constexpr int kSampleMaxM = 1024;      // 2 m + 16 expected candidates stay well inside the list
+
+OSG_D bool pair_less(uint64_t ka, uint32_t sa, uint64_t kb, uint32_t sb) { return ka < kb || (ka == kb && sa < sb); }
+
+__global__ void __launch_bounds__(kThreads)
+k_sample_many(const uint64_t* __restrict__ streams, uint64_t seed, int64_t size, int m, uint64_t limit0, int64_t* __restrict__ slots) {
+  __shared__ uint64_t key[kSampleCap];
+  __shared__ uint32_t slot[kSampleCap];
+  __shared__ unsigned int count;
+  const uint64_t stream = streams[blockIdx.x];
+  const int tid = threadIdx.x;
+  // `below`: a limit known to give fewer than m; `above`: one known to overflow the list.  Once both are known the
+  // search bisects between them: the counts grow one key at a time, so a limit with m .. kSampleCap keys lies between.
+  uint64_t limit = limit0, below = 0, above = 0;
+  bool bracketed = false;
+  unsigned int n;
+  for (;;) {
+    if (tid == 0) count = 0u;
+    __syncthreads();
+    for (int64_t k = tid; k < size; k += kThreads) {
+      const uint64_t x = dcfr_sample_key(seed, stream, k);
+      if (x <= limit) {
+        const unsigned int at = atomicAdd(&count, 1u);
+        if (at < static_cast<unsigned int>(kSampleCap)) { key[at] = x; slot[at] = static_cast<uint32_t>(k); }
+      }
+    }
+    __syncthreads();
+    n = count;
+    __syncthreads();
+    if (n < static_cast<unsigned int>(m)) {
+      below = limit;
+      if (bracketed) limit = below + (above - below) / 2u;
+      else limit = limit > (~uint64_t{0} >> 2) ? ~uint64_t{0} : limit * 4u;
+    } else if (n > static_cast<unsigned int>(kSampleCap)) {
+      above = limit;
+      bracketed = true;
+      limit = below + (above - below) / 2u;
+    } else {
+      break;
+    }
+  }
+  unsigned int np = 1u;
+  while (np < n) np <<= 1;
+  for (unsigned int x = n + tid; x < np; x += kThreads) { key[x] = ~uint64_t{0}; slot[x] = ~uint32_t{0}; }
+  __syncthreads();
+  for (unsigned int span = 2u; span <= np; span <<= 1)
+    for (unsigned int step = span >> 1; step > 0u; step >>= 1) {
+      for (unsigned int x = tid; x < np; x += kThreads) {
+        const unsigned int y = x ^ step;
+        if (y > x) {
+          const bool up = (x & span) == 0u;
+          const uint64_t kx = key[x], ky = key[y];
+          const uint32_t sx = slot[x], sy = slot[y];
+          if (pair_less(ky, sy, kx, sx) == up) { key[x] = ky; slot[x] = sy; key[y] = kx; slot[y] = sx; }
+        }
+      }
+      __syncthreads();
+    }
+  for (int j = tid; j < m; j += kThreads) slots[static_cast<int64_t>(blockIdx.x) * m + j] = static_cast<int64_t>(slot[j]);
+}
+
 }  // namespace
 
 namespace osg_cfr_impl {
+ReservoirView reservoir_view(const osg_reservoir* b) {
+  return ReservoirView{b->ctx, b->A, std::min(b->add_calls, b->capacity), b->d_info, b->d_vals};
+}
+
+int sample_many(osg_ctx* ctx, const char* who, int64_t size, uint64_t seed, const uint64_t* streams, int64_t U, int64_t m,
+                DeviceArray<uint64_t>& d_streams, int64_t* d_slots) {
+  if (!streams || !d_slots || U < 1 || m < 1) return set_error(OSG_ERR_INVALID, std::string(who) + ": bad argument");
+  if (m > size) return set_error(OSG_ERR_INVALID, std::string(who) + ": more rows asked for than the buffer holds");
+  if (m > kSampleMaxM) return set_error(OSG_ERR_INVALID, std::string(who) + ": more than 1024 rows per draw");
+  if (U >= (int64_t{1} << 31)) return set_error(OSG_ERR_UNSUPPORTED, std::string(who) + ": 2^31 streams or more in one call");
+  hipStream_t st = ctx->stream;
+  OSG_HIP(d_streams.ensure(static_cast<size_t>(U)));   // (in stream order behind an earlier call's kernel)
+  OSG_HIP(hipMemcpyAsync(d_streams.get(), streams, sizeof(uint64_t) * U, hipMemcpyHostToDevice, st));
+  const long double share = static_cast<long double>(2 * m + 16) / static_cast<long double>(size);
+  const uint64_t limit = share >= 1.0L ? ~uint64_t{0} : static_cast<uint64_t>(share * 18446744073709551616.0L);
+  k_sample_many<<<dim3(static_cast<unsigned>(U)), dim3(kThreads), 0, st>>>(d_streams, seed, size, static_cast<int>(m), limit, d_slots);
+  OSG_HIP(hipGetLastError());
+  // A small copy from pageable memory is staged before the call returns; a large one may still be reading the
+  // caller's array (upload() in osg_internal.h draws the same line).
+  if (sizeof(uint64_t) * static_cast<size_t>(U) > (64u << 10)) OSG_HIP(hipStreamSynchronize(st));
+  return OSG_OK;
+}
+
 bool reservoir_serves(const osg_reservoir* b, const osg_cfr* s) { return b->A == s->A && b->ctx == s->ctx; }
 
 int reservoir_append(osg_reservoir* b, int64_t m, const int32_t* d_info, int32_t iteration, const float* d_values) {
@@ -366,6 +460,13 @@ int osg_reservoir_sample(osg_reservoir* buf, uint64_t seed, uint64_t stream, int
                                     buf->d_slot_out.get(), static_cast<size_t>(size), 0u, 64u, st));
   OSG_HIP(hipMemcpyAsync(d_slots, buf->d_slot_out.get(), sizeof(int64_t) * m, hipMemcpyDeviceToDevice, st));
   return OSG_OK;
+}
+
+int osg_reservoir_sample_many(osg_reservoir* buf, uint64_t seed, const uint64_t* streams, int64_t n_streams, int64_t m,
+                              int64_t* d_slots) {
+  if (!buf) return set_error(OSG_ERR_INVALID, "osg_reservoir_sample_many: bad argument");
+  return sample_many(buf->ctx, "osg_reservoir_sample_many", std::min(buf->add_calls, buf->capacity), seed, streams, n_streams, m,
+                     buf->d_streams, d_slots);
 }
 
 int osg_deep_cfr_traverse(osg_cfr* s, const float* d_advantages, int player, int iteration, uint64_t seed,

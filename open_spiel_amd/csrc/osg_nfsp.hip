@@ -31,6 +31,7 @@ struct osg_transition_ring {
   DeviceArray<uint64_t> d_key_in, d_key_out;
   DeviceArray<int64_t> d_slot_in, d_slot_out;
   DeviceArray<unsigned char> d_tmp;
+  DeviceArray<uint64_t> d_streams;      // the stream ids of the last osg_transition_ring_sample_many
 };
 
 namespace {
@@ -260,6 +261,12 @@ bool tables_in_lds() {   // read at every call
 
 }  // namespace
 
+namespace osg_cfr_impl {
+RingView ring_view(const osg_transition_ring* b) {
+  return RingView{b->ctx, std::min(b->entry_index, b->capacity), b->d_info, b->d_action, b->d_reward, b->d_next, b->d_final};
+}
+}  // namespace osg_cfr_impl
+
 extern "C" {
 
 int osg_transition_ring_create(osg_ctx* ctx, int64_t capacity, osg_transition_ring** out) {
@@ -339,6 +346,13 @@ int osg_transition_ring_sample(osg_transition_ring* ring, uint64_t seed, uint64_
                                     ring->d_slot_out.get(), static_cast<size_t>(size), 0u, 64u, st));
   OSG_HIP(hipMemcpyAsync(d_slots, ring->d_slot_out.get(), sizeof(int64_t) * m, hipMemcpyDeviceToDevice, st));
   return OSG_OK;
+}
+
+int osg_transition_ring_sample_many(osg_transition_ring* ring, uint64_t seed, const uint64_t* streams, int64_t n_streams, int64_t m,
+                                    int64_t* d_slots) {
+  if (!ring) return set_error(OSG_ERR_INVALID, "osg_transition_ring_sample_many: bad argument");
+  return sample_many(ring->ctx, "osg_transition_ring_sample_many", std::min(ring->entry_index, ring->capacity), seed, streams,
+                     n_streams, m, ring->d_streams, d_slots);
 }
 
 int osg_nfsp_collect(osg_cfr* s, const float* d_q, const float* d_avg_probs, const double* eps, const double* anticipatory,

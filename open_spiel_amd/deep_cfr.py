@@ -25,6 +25,16 @@ RESERVOIR_SALT = 0x7265736572766F69   # the buffers' streams are keyed apart fro
 SAMPLE_SALT = 0x73616D706C655F6B
 
 
+def sample_slots_many(entry, buffer, num_samples, seed, streams):
+    """The batched draw of a ReservoirBuffer or a TransitionRing through its C entry point."""
+    ids = np.ascontiguousarray(np.asarray(streams, dtype=np.uint64).reshape(-1))
+    if num_samples > len(buffer):
+        raise ValueError(f"{num_samples} elements could not be sampled from size {len(buffer)}")
+    slots = torch.empty((len(ids), int(num_samples)), dtype=torch.int64, device=buffer.ctx.device)
+    check(entry(buffer._h, int(seed) & (2 ** 64 - 1), ids.ctypes.data, len(ids), int(num_samples), slots.data_ptr()))
+    return slots
+
+
 class ReservoirBuffer:
     """ReservoirBuffer (deep_cfr.py:121-213) on the device: `capacity` rows of (infostate index int32, iteration int32,
     values float32 [num_actions]).  The row with add index n goes to slot n while n < capacity, else to
@@ -79,6 +89,10 @@ class ReservoirBuffer:
         slots = torch.empty(int(num_samples), dtype=torch.int64, device=self.ctx.device)
         check(lib().osg_reservoir_sample(self._h, int(seed) & (2 ** 64 - 1), int(stream), int(num_samples), slots.data_ptr()))
         return slots
+
+    def sample_slots_many(self, num_samples, seed, streams):
+        """[len(streams), num_samples] int64 (device): row u is sample_slots(num_samples, seed, streams[u]), one launch."""
+        return sample_slots_many(lib().osg_reservoir_sample_many, self, num_samples, seed, streams)
 
     def rows(self, slots):
         """(infostate index int32 [m], iteration int32 [m], values float32 [m, num_actions]) of the given slots."""

@@ -22,8 +22,8 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
-from ._abi import OsgError, check, describe, lib
-from .deep_cfr import RESERVOIR_SALT, SAMPLE_SALT, ReservoirBuffer
+from ._abi import NfspLearnJob, OsgError, check, describe, lib
+from .deep_cfr import RESERVOIR_SALT, SAMPLE_SALT, ReservoirBuffer, sample_slots_many
 from .engine import TabularSolver
 
 ILLEGAL_ACTION_LOGITS_PENALTY = torch.finfo(torch.float).min
@@ -85,6 +85,10 @@ class TransitionRing:
         check(lib().osg_transition_ring_sample(self._h, int(seed) & (2 ** 64 - 1), int(stream), int(num_samples), slots.data_ptr()))
         return slots
 
+    def sample_slots_many(self, num_samples, seed, streams):
+        """[len(streams), num_samples] int64 (device): row u is sample_slots(num_samples, seed, streams[u]), one launch."""
+        return sample_slots_many(lib().osg_transition_ring_sample_many, self, num_samples, seed, streams)
+
     def rows(self, slots):
         """(info int32, action int32, reward float32, next_info int32, final uint8), each [m], of the given slots."""
         m = int(slots.shape[0])
@@ -127,6 +131,18 @@ def linear_schedule(start_e, end_e, duration):
     return lambda t: max(slope * t + start_e, end_e)
 
 
+def _flatten(net):
+    """The module's parameters as views of one flat float32 buffer in nn.Linear order (weight, bias per layer): the
+    buffer the fused learner updates in place."""
+    params = list(net.parameters())
+    flat = torch.cat([p.detach().reshape(-1) for p in params]).contiguous()
+    at = 0
+    for p in params:
+        p.data = flat[at:at + p.numel()].view_as(p)
+        at += p.numel()
+    return flat
+
+
 def _optimizer(name, params, lr, allowed):
     makers = {"adam": torch.optim.Adam, "rmsprop": torch.optim.RMSprop, "sgd": torch.optim.SGD}
     if name not in allowed:
@@ -149,6 +165,13 @@ class NFSPSolver:
     update_target_network_every on that counter.  As in the reference, seed reaches the average networks only (seed + 1)
     and gradient_clipping the average network's update only: NFSP does not hand either on to its DQN agent.
 
+    learner="torch" (the default) makes every update with torch, one at a time.  learner="fused" makes all the updates a
+    chunk owes with two batched draws per player and ONE osg_nfsp_learn launch (csrc/osg_mlp_train.hip: a workgroup per
+    network, weights and batch in LDS, fp32 matrix instructions) and waits once, for the losses.  The batches are the
+    same — the stream ids are handed out in the torch path's order — and the arithmetic is fp32 in another summation
+    order.  It serves optimizer_str="sgd" and what fits a workgroup's LDS (osg_mlp_plan.h); each network's parameters
+    become views of one flat buffer, which the torch modules keep owning.
+
     Not served: board games and simultaneous-move games, checkpoint files, user-supplied buffer classes."""
 
     def __init__(self, ctx, game, hidden_layers_sizes, reservoir_buffer_capacity, anticipatory_param, batch_size=128,
@@ -156,8 +179,13 @@ class NFSPSolver:
                  gradient_clipping=None, seed=42, replay_buffer_capacity=10000, update_target_network_every=1000,
                  weight_update_coeff=0.995, discount_factor=1.0, epsilon_start=1.0, epsilon_end=0.1, epsilon_decay_duration=int(1e6),
                  epsilon_decay_schedule_str="exp", loss_str="mse", huber_loss_parameter=1.0, episodes_per_step=1024, device=None,
-                 tabular=None):
+                 tabular=None, learner="torch"):
         self.ctx, self.game_string = ctx, game
+        if learner not in ("torch", "fused"):
+            raise ValueError("learner: 'torch' or 'fused'")
+        if learner == "fused" and optimizer_str != "sgd":
+            raise ValueError(f"learner='fused' serves optimizer_str='sgd' only; use learner='torch' for {optimizer_str!r}")
+        self._learner = learner
         if device is not None and torch.device(device) != ctx.device:
             raise OsgError(f"NFSPSolver: the networks live on the context's device {ctx.device}")
         desc = describe(game)
@@ -177,6 +205,8 @@ class NFSPSolver:
         self._discount_factor = float(discount_factor)
         self._gradient_norm_clipping = gradient_clipping
         self._episodes_per_step, self._seed = int(episodes_per_step), int(seed)
+        self._loss_str, self._huber_beta = loss_str, float(huber_loss_parameter)
+        self._rl_learning_rate, self._sl_learning_rate = float(rl_learning_rate), float(sl_learning_rate)
         if loss_str == "mse":
             self._rl_loss = F.mse_loss
         elif loss_str == "huber":
@@ -205,6 +235,12 @@ class NFSPSolver:
         for target, net in zip(self._target_q_networks, self._q_networks):
             target.load_state_dict(net.state_dict())
         self._avg_networks = [MLP(size, hidden, A, self._seed + 1).to(dev) for _ in range(P)]
+        self._widths = [size] + hidden + [A]
+        self._flat = {}
+        if learner == "fused":
+            for kind, nets in (("q", self._q_networks), ("target", self._target_q_networks), ("avg", self._avg_networks)):
+                self._flat[kind] = [_flatten(net) for net in nets]
+            self._legal_mask_u8 = self._legal_mask.to(torch.uint8).contiguous()
         self._rl_optimizers = [_optimizer(optimizer_str, n.parameters(), rl_learning_rate, ("adam", "rmsprop", "sgd")) for n in self._q_networks]
         self._sl_optimizers = [_optimizer(optimizer_str, n.parameters(), sl_learning_rate, ("adam", "sgd")) for n in self._avg_networks]
 
@@ -265,6 +301,7 @@ class NFSPSolver:
         self._episodes += E
         self.last_totals = totals
         staged = self.tabular.nfsp_staged()
+        owed = []
         for p in range(self._num_players):
             before_n, before_d = self.nfsp_steps[p], self.dqn_steps[p]
             after_n, after_d = before_n + int(totals[p, 3]), before_d + int(totals[p, 2])
@@ -277,6 +314,9 @@ class NFSPSolver:
                 start = torch.cat([end.new_tensor([before_n]), end[:-1]])
                 average = ((staged["modes"] >> p) & 1) == 0
                 rl_updates += int(((end // L - start // L) * average).sum().item())
+            owed.append((sl_updates, rl_updates, after_d // self._update_target_network_every - before_d // self._update_target_network_every))
+            if self._learner == "fused":
+                continue
             for _ in range(sl_updates):
                 self.last_sl_loss[p] = self._learn_average(p)
                 self.updates[p][1] += 1
@@ -286,7 +326,60 @@ class NFSPSolver:
             for _ in range(after_d // self._update_target_network_every - before_d // self._update_target_network_every):
                 self._copy_weights(p)
                 self.updates[p][2] += 1
+        if self._learner == "fused":
+            self._learn_fused(owed)
         return totals
+
+    def _learn_fused(self, owed):
+        """All the updates of a chunk: stream ids in the torch path's order (per player its supervised updates, then its
+        Q updates), one batched draw per buffer, one osg_nfsp_learn launch, one wait (the losses), the target updates."""
+        P, B, seed = self._num_players, self._batch_size, self._seed ^ SAMPLE_SALT
+        n_linear = len(self._widths) - 1
+        jobs, losses = [], []
+        self.last_slots = [[None, None] for _ in range(P)]   # per player: the supervised and the Q updates' slots [U, B]
+        for p, (sl_updates, rl_updates, _) in enumerate(owed):
+            for kind, count, buffer in ((1, sl_updates, self._reservoir_buffers[p]), (0, rl_updates, self._replay_buffers[p])):
+                if not count:
+                    continue
+                if not self._ready(buffer):   # as _learn_average / _learn_q: counted, no loss
+                    if kind == 1:
+                        self.last_sl_loss[p] = None
+                    else:
+                        self.last_rl_loss[p] = None
+                    continue
+                streams = np.arange(self._samples_drawn + 1, self._samples_drawn + count + 1, dtype=np.uint64)
+                self._samples_drawn += count
+                slots = buffer.sample_slots_many(B, seed, streams)
+                self.last_slots[p][1 - kind] = slots
+                loss = torch.empty(count, dtype=torch.float32, device=self.ctx.device)
+                job = NfspLearnJob(kind=kind, n_linear=n_linear, batch=B, loss=1 if self._loss_str == "huber" else 0, updates=count,
+                                   infostates=self._tensors.shape[0], d_tensors=self._tensors.data_ptr(),
+                                   d_legal_mask=self._legal_mask_u8.data_ptr(), d_slots=slots.data_ptr(), d_loss=loss.data_ptr(),
+                                   discount=self._discount_factor, huber_beta=self._huber_beta)
+                job.widths[:n_linear + 1] = self._widths
+                if kind == 1:
+                    job.d_params, job.reservoir = self._flat["avg"][p].data_ptr(), buffer._h
+                    job.learning_rate = self._sl_learning_rate
+                    job.clip = float(self._gradient_norm_clipping) if self._gradient_norm_clipping is not None else 0.0
+                else:
+                    job.d_params, job.d_target_params = self._flat["q"][p].data_ptr(), self._flat["target"][p].data_ptr()
+                    job.ring, job.learning_rate = buffer._h, self._rl_learning_rate
+                jobs.append(job)
+                losses.append((p, kind, loss))
+        if jobs:
+            check(lib().osg_nfsp_learn(self.ctx._h, (NfspLearnJob * len(jobs))(*jobs), len(jobs)))
+            last = torch.stack([loss[-1] for _, _, loss in losses]).cpu().tolist()   # the one wait
+            for (p, kind, _), value in zip(losses, last):
+                if kind == 1:
+                    self.last_sl_loss[p] = value
+                else:
+                    self.last_rl_loss[p] = value
+        for p, (sl_updates, rl_updates, copies) in enumerate(owed):
+            self.updates[p][1] += sl_updates
+            self.updates[p][0] += rl_updates
+            for _ in range(copies):
+                self._copy_weights(p)
+                self.updates[p][2] += 1
 
     def _ready(self, buffer):
         return len(buffer) >= self._batch_size and len(buffer) >= self._min_buffer_size_to_learn
