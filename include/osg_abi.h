@@ -1188,6 +1188,45 @@ int osg_transition_ring_sample_many(osg_transition_ring* ring, uint64_t seed, co
 int osg_reservoir_sample_many(osg_reservoir* buf, uint64_t seed, const uint64_t* streams, int64_t n_streams, int64_t m,
                               int64_t* d_slots);
 int osg_nfsp_learn(osg_ctx* ctx, const osg_nfsp_learn_job* jobs, int64_t n_jobs);
+/* ---- the fused learner of Deep CFR ------------------------------------------------------------
+ * DeepCFRSolver._learn_advantage_network / _learn_strategy_network (deep_cfr.py:343-420) with Adam, for every update
+ * of a call, in one launch (open_spiel_amd/csrc/osg_deep_cfr_learn.hip; the layout is osg_adam_plan.h).
+ *
+ * osg_deep_cfr_learn: n_jobs networks of deep_cfr.MLP (Linear + ReLU per hidden layer, nn.LayerNorm with affine
+ *   weights and biased variance, Linear), job j's `updates` sequential Adam updates by workgroup j.  kind 0 (advantage)
+ *   y = z, kind 1 (policy) y = softmax(z) over all A action ids.  An update gathers the rows d_slots[u, :] of
+ *   `reservoir` (infostate, iteration it, values t [A]) and their tensors, and steps on
+ *   L = 1 / (B A) * sum_b sum_a it_b (y_ba - t_ba)^2 — MSELoss(sqrt(it) y, sqrt(it) t) — with torch's Adam:
+ *   m = beta1 m + (1 - beta1) g, v = beta2 v + (1 - beta2) g^2,
+ *   p -= learning_rate / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps), t = step0 + u + 1.
+ *   The batch is walked in tiles of 16 to 128 rows (what fits the LDS), the gradient accumulates over the tiles in
+ *   ascending order and the step is taken once per batch.
+ *   widths [n_linear + 1]: inputs S, the hidden widths, outputs A; d_params, d_adam_m, d_adam_v: flat fp32 in
+ *   network.parameters() order (Linear weight [out, in], bias, ...; LayerNorm weight, bias; Linear weight, bias), all
+ *   three updated in place; the caller keeps step0, the updates already made.  d_tensors [infostates, S] f32; d_slots
+ *   [updates, batch] i64 from osg_reservoir_sample_many; d_loss [updates] f32 (NaN for an update that met a slot or an
+ *   infostate out of range: such a row counts as zeros).  fp32 throughout (v_mfma_f32_16x16x4_f32), every sum in one
+ *   fixed order, no atomics: a job's bits do not depend on the other jobs.  Does not wait.  Served: n_linear 2 or 3,
+ *   hidden widths 1..128, S <= 256, A <= 16, batch 1..1024 (and at most the rows held), and what fits the device's LDS
+ *   per workgroup and the wavefronts' gradient registers; the rest is OSG_ERR_UNSUPPORTED. */
+typedef struct osg_deep_cfr_learn_job {
+  int32_t kind;            /* 0 advantage (y = z), 1 policy (y = softmax z) */
+  int32_t n_linear;        /* 2 or 3 linear layers */
+  int32_t widths[4];       /* S, hidden..., A */
+  int32_t batch;           /* 1..1024 (the batched draw's limit) */
+  int64_t updates, infostates, step0;
+  float *d_params, *d_adam_m, *d_adam_v;
+  const float* d_tensors;  /* [infostates, S] */
+  osg_reservoir* reservoir;
+  const int64_t* d_slots;  /* [updates, batch] */
+  float* d_loss;           /* [updates] */
+  double learning_rate, beta1, beta2, eps, ln_eps;
+} osg_deep_cfr_learn_job;
+int osg_deep_cfr_learn(osg_ctx* ctx, const osg_deep_cfr_learn_job* jobs, int64_t n_jobs);
+/* osg_deep_cfr_learn_plan: what the planner chooses for a shape on the context's device, without a launch: plan [6] =
+ *   tile height, tiles per batch, transposed copies resident (0 / 1), moments resident (0 / 1), LDS bytes, parameters.
+ *   OSG_ERR_UNSUPPORTED with the planner's reason for a shape osg_deep_cfr_learn refuses. */
+int osg_deep_cfr_learn_plan(osg_ctx* ctx, int32_t n_linear, const int32_t* widths, int32_t batch, int32_t* plan);
 
 /* ---- multi-GPU exchange step ---------------------------------------------------
  * One process per GPU.  Units shard by global index with no data-path collective; the ONE exchange

@@ -79,6 +79,31 @@ class NfspLearnJob(C.Structure):
     ]
 
 
+class DeepCfrLearnJob(C.Structure):
+    """osg_deep_cfr_learn_job: one deep_cfr.MLP network and its sequential Adam updates (kind 0 advantage, 1 policy)."""
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("n_linear", C.c_int32),
+        ("widths", C.c_int32 * 4),
+        ("batch", C.c_int32),
+        ("updates", C.c_int64),
+        ("infostates", C.c_int64),
+        ("step0", C.c_int64),
+        ("d_params", C.c_void_p),
+        ("d_adam_m", C.c_void_p),
+        ("d_adam_v", C.c_void_p),
+        ("d_tensors", C.c_void_p),
+        ("reservoir", C.c_void_p),
+        ("d_slots", C.c_void_p),
+        ("d_loss", C.c_void_p),
+        ("learning_rate", C.c_double),
+        ("beta1", C.c_double),
+        ("beta2", C.c_double),
+        ("eps", C.c_double),
+        ("ln_eps", C.c_double),
+    ]
+
+
 class AbCfg(C.Structure):
     _fields_ = [
         ("depth_limit", C.c_int32),
@@ -311,6 +336,8 @@ SIGNATURES = {
     "osg_transition_ring_sample_many": (INT, [VP, U64, VP, I64, I64, VP]),
     "osg_reservoir_sample_many": (INT, [VP, U64, VP, I64, I64, VP]),
     "osg_nfsp_learn": (INT, [VP, VP, I64]),
+    "osg_deep_cfr_learn": (INT, [VP, VP, I64]),
+    "osg_deep_cfr_learn_plan": (INT, [VP, C.c_int32, VP, C.c_int32, VP]),
     "osg_cfr_infostate_key": (INT, [VP, I64, C.c_char_p, INT]),
     "osg_cfr_best_response_history_values": (INT, [VP, INT, VP, INT, VP]),
     "osg_cfr_tree_edges": (INT, [VP, VP, VP]),

@@ -716,8 +716,9 @@ int deep_supported(const osg_cfr* s, const char* who);   // what Deep CFR and NF
 bool reservoir_serves(const osg_reservoir* b, const osg_cfr* s);   // the solver's row width and context
 // m sequential appends of device rows, in row order (osg_reservoir_append without its argument checks)
 int reservoir_append(osg_reservoir* b, int64_t m, const int32_t* d_info, int32_t iteration, const float* d_values);
-// What the fused learner (osg_mlp_train.hip) reads of a buffer: its filled rows, column by column (device pointers).
-struct ReservoirView { osg_ctx* ctx; int A; int64_t size; const int32_t* info; const float* vals; };
+// What the fused learners (osg_mlp_train.hip, osg_deep_cfr_learn.hip) read of a buffer: its filled rows, column by column
+// (device pointers).
+struct ReservoirView { osg_ctx* ctx; int A; int64_t size; const int32_t* info; const float* vals; const int32_t* iter; };
 ReservoirView reservoir_view(const osg_reservoir* b);
 // d_slots [U, m]: for every stream id the m filled slots with the smallest dcfr_sample_key(seed, stream, slot),
 // ascending by (key, slot): k_sample_many, a workgroup per stream, nothing materialised and nothing sorted globally.

@@ -144,7 +144,7 @@ k_sample_many(const uint64_t* __restrict__ streams, uint64_t seed, int64_t size,
 
 namespace osg_cfr_impl {
 ReservoirView reservoir_view(const osg_reservoir* b) {
-  return ReservoirView{b->ctx, b->A, std::min(b->add_calls, b->capacity), b->d_info, b->d_vals};
+  return ReservoirView{b->ctx, b->A, std::min(b->add_calls, b->capacity), b->d_info, b->d_vals, b->d_iter};
 }
 
 int sample_many(osg_ctx* ctx, const char* who, int64_t size, uint64_t seed, const uint64_t* streams, int64_t U, int64_t m,

@@ -21,13 +21,13 @@
 // turns the activations into gradients on its way down), the forward pass is run again — nothing has moved — and the
 // second backward pass steps with the clip coefficient.
 #include "osg_cfr_internal.h"
+#include "osg_mfma_tile.h"
 #include "osg_mlp_plan.h"
 
 using namespace osg_mlp;
+using namespace osg_mfma;   // f4, mma_rows, mma_cols, wave_sum
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int kWaves = kMlpThreads / 64;
 
@@ -51,34 +51,6 @@ struct MlpJob {   // one job as the kernel sees it (device pointers)
 };
 
 struct Net { const int* w; const int* b; };   // offsets of one network's layers in LDS (arrays of the job's layout)
-
-// D += A B with both operands stored row by row along the contraction: A[i][k] at a[i * sa + k], B[k][j] at
-// bt[j * sb + k].  K is a multiple of 4.
-OSG_D f4 mma_rows(const float* a, int sa, const float* bt, int sb, int K, f4 acc) {
-  const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
-  const float* pa = a + i * sa + g;
-  const float* pb = bt + i * sb + g;
-  for (int k = 0; k < K; k += 4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[k], pb[k], acc, 0, 0, 0);
-  return acc;
-}
-// D += A B contracting over rows: A[i][k] at a[k * sa + i], B[k][j] at b[k * sb + j] (b null: B is all ones).  K is a
-// multiple of 16; one instruction contracts rows k0 + t, + 4, + 8, + 12 (the bank argument of osg_mlp_plan.h).
-OSG_D f4 mma_cols(const float* a, int sa, const float* b, int sb, int K, f4 acc) {
-  const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
-  const float* pa = a + 4 * g * sa + i;
-  const float* pb = b ? b + 4 * g * sb + i : nullptr;
-  for (int k0 = 0; k0 < K; k0 += 16)
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[(k0 + t) * sa], pb ? pb[(k0 + t) * sb] : 1.0f, acc, 0, 0, 0);
-  return acc;
-}
-
-OSG_D float wave_sum(float v) {   // one fixed tree; every lane gets the sum
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
-  return v;
-}
 
 // The flat parameters (nn.Linear layout) into the padded LDS layout, zeros in the padding.
 OSG_D void load_params(float* lds, const MlpLayout& L, const Net& n, const float* __restrict__ src) {

@@ -4,7 +4,8 @@ the sampled advantages and the reservoir buffers on the device.
 The networks do not change while one player's traversals of one iteration run, so one forward pass over all infostate
 tensors — an [I, A] table of advantage-network outputs — stands for every per-node forward pass of the reference, and one
 TabularSolver.deep_cfr_traverse call does all num_traversals traversals and all reservoir appends of that step.  The
-networks, their losses and Adam are torch's; a buffer row is (infostate index, iteration, values) and the tensor the
+networks, their losses and Adam are torch's (or, with learner="fused", one osg_deep_cfr_learn launch per training call);
+a buffer row is (infostate index, iteration, values) and the tensor the
 reference stores with each row is looked up in TabularSolver.infostate_tensors() when a batch is formed.
 
 What is pinned against the reference (tests/golden/make_deep_cfr_vectors.py) is the device's part: given the networks'
@@ -18,9 +19,10 @@ import numpy as np
 import torch
 from torch import nn
 
-from ._abi import OsgError, check, describe, lib
+from ._abi import DeepCfrLearnJob, OsgError, check, describe, lib
 from .engine import TabularSolver
 
+FUSED_MAX_BATCH = 1024   # the batched draw's limit
 RESERVOIR_SALT = 0x7265736572766F69   # the buffers' streams are keyed apart from the trajectories'
 SAMPLE_SALT = 0x73616D706C655F6B
 
@@ -113,6 +115,28 @@ class ReservoirBuffer:
         return self.rows(torch.arange(len(self), dtype=torch.int64, device=self.ctx.device))
 
 
+def fused_plan(ctx, widths, batch):
+    """What the fused learner's planner (csrc/osg_adam_plan.h) chooses for a network [S, hidden ..., A] and a batch on the
+    context's device; OsgError with its reason for a shape it refuses."""
+    out = (C.c_int32 * 6)()
+    check(lib().osg_deep_cfr_learn_plan(ctx._h, len(widths) - 1, (C.c_int32 * len(widths))(*widths), int(batch), out))
+    return dict(tile=out[0], tiles=out[1], transposed_resident=bool(out[2]), moments_resident=bool(out[3]), lds_bytes=out[4], parameters=out[5])
+
+
+class _FusedState:
+    """One network's flat parameters (the module's parameters are views of them), Adam's moments and its step count."""
+
+    def __init__(self, network):
+        from .nfsp import _flatten
+        self.params = _flatten(network)
+        self.m, self.v, self.step = torch.zeros_like(self.params), torch.zeros_like(self.params), 0
+
+    def clear(self):
+        self.m.zero_()
+        self.v.zero_()
+        self.step = 0
+
+
 class MLP(nn.Module):
     """Linear + ReLU per hidden size, then LayerNorm and a Linear layer (and an optional final activation)."""
 
@@ -146,13 +170,22 @@ class DeepCFRSolver:
     [I, A] table, one deep_cfr_traverse call with first_trajectory = ((iteration - 1) * P + player) * num_traversals
     does the traversals and the appends, then the player's advantage network trains from the buffer's rows; nothing
     crosses to the host but the row counts.  With batch_size_* = None the filled rows are the batch (the reference
-    takes its whole array, uninitialised rows included)."""
+    takes its whole array, uninitialised rows included).
+
+    learner="torch" (the default) makes every network update with torch, one at a time.  learner="fused" makes all the
+    updates of a _train call with ONE batched draw and ONE osg_deep_cfr_learn launch (csrc/osg_deep_cfr_learn.hip: a
+    workgroup runs the network's Adam updates one after another with the parameters in LDS and the batch walked in
+    tiles) on the very batches the torch learner would draw; it needs both batch sizes (at most 1024) and networks the
+    kernel's planner serves: one or two hidden layers of at most 128, what fits a workgroup's LDS."""
 
     def __init__(self, ctx, game, policy_network_layers=(256, 256), advantage_network_layers=(128, 128), num_iterations=100,
                  num_traversals=20, learning_rate=1e-4, batch_size_advantage=None, batch_size_strategy=None,
                  memory_capacity=int(1e6), policy_network_train_steps=1, advantage_network_train_steps=1,
-                 reinitialize_advantage_networks=True, device=None, seed=42, print_nash_convs=False, tabular=None):
+                 reinitialize_advantage_networks=True, device=None, seed=42, print_nash_convs=False, tabular=None, learner="torch"):
         self.ctx, self.game_string = ctx, game
+        if learner not in ("torch", "fused"):
+            raise ValueError("learner: 'torch' or 'fused'")
+        self._learner = learner
         if device is not None and torch.device(device) != ctx.device:
             raise OsgError(f"DeepCFRSolver: the networks live on the context's device {ctx.device}")
         desc = describe(game)
@@ -188,6 +221,9 @@ class DeepCFRSolver:
         self._loss_advantages = nn.MSELoss(reduction="mean")
         self._optimizer_policy = None
         self._optimizer_advantages = [None] * self._num_players
+        self._fused, self.last_slots = {}, None
+        if learner == "fused":
+            self._init_fused(list(advantage_network_layers), list(policy_network_layers))
         self._reinitialize_policy_network()
         for p in range(self._num_players):
             self._reinitialize_advantage_network(p)
@@ -204,12 +240,31 @@ class DeepCFRSolver:
     def iteration(self):
         return self._iteration
 
+    def _init_fused(self, advantage_layers, policy_layers):
+        """The fused learner's refusals, then every network's flat buffers."""
+        for what, batch in (("batch_size_advantage", self._batch_size_advantage), ("batch_size_strategy", self._batch_size_strategy)):
+            if not batch:
+                raise ValueError(f"learner='fused' needs {what}: the whole-buffer batch is unbounded; use learner='torch'")
+            if batch > FUSED_MAX_BATCH:
+                raise ValueError(f"learner='fused' serves batches of at most {FUSED_MAX_BATCH} rows, {what} is {batch}; use learner='torch'")
+        for what, layers, batch in (("advantage", advantage_layers, self._batch_size_advantage), ("policy", policy_layers, self._batch_size_strategy)):
+            try:
+                fused_plan(self.ctx, [self._embedding_size] + layers + [self._num_actions], batch)
+            except OsgError as e:
+                raise ValueError(f"learner='fused' does not serve the {what} network {tuple(layers)}: {e}; use learner='torch'") from None
+        for network in self._advantage_networks + [self._policy_network]:
+            self._fused[network] = _FusedState(network)
+
     def _reinitialize_advantage_network(self, player):
         self._advantage_networks[player].reset()
+        if self._learner == "fused":
+            return self._fused[self._advantage_networks[player]].clear()
         self._optimizer_advantages[player] = torch.optim.Adam(self._advantage_networks[player].parameters(), lr=self._learning_rate)
 
     def _reinitialize_policy_network(self):
         self._policy_network.reset()
+        if self._learner == "fused":
+            return self._fused[self._policy_network].clear()
         self._optimizer_policy = torch.optim.Adam(self._policy_network.parameters(), lr=self._learning_rate)
 
     @torch.inference_mode()
@@ -255,7 +310,36 @@ class DeepCFRSolver:
             return memory.sample(batch_size, self._seed ^ SAMPLE_SALT, self._samples_drawn)
         return memory.filled() if len(memory) else None
 
+    def _train_fused(self, network, memory, batch_size, steps):
+        """All `steps` updates of a _train call: the torch path's stream ids, one batched draw, one launch, one host read."""
+        if steps < 1 or batch_size > len(memory):
+            return None
+        streams = np.arange(self._samples_drawn + 1, self._samples_drawn + steps + 1, dtype=np.uint64)
+        self._samples_drawn += steps
+        slots = memory.sample_slots_many(batch_size, self._seed ^ SAMPLE_SALT, streams)
+        self.last_slots = slots
+        state = self._fused[network]
+        loss = torch.empty(steps, dtype=torch.float32, device=self.ctx.device)
+        job = self._fused_job(network, memory, slots, loss, state.params, state.m, state.v, state.step)
+        check(lib().osg_deep_cfr_learn(self.ctx._h, C.byref(job), 1))
+        state.step += steps
+        return loss[-1].item()
+
+    def _fused_job(self, network, memory, slots, loss, params, m, v, step0):
+        """The osg_deep_cfr_learn job of `network` on the rows slots [U, B] of `memory`: flat params, m, v (updated in place)
+        after step0 updates, losses into loss [U]."""
+        widths = [self._embedding_size] + [layer.out_features for layer in network.modules() if isinstance(layer, nn.Linear)]
+        job = DeepCfrLearnJob(kind=1 if network is self._policy_network else 0, n_linear=len(widths) - 1, batch=slots.shape[1],
+                              updates=slots.shape[0], infostates=self._tensors.shape[0], step0=step0, d_params=params.data_ptr(),
+                              d_adam_m=m.data_ptr(), d_adam_v=v.data_ptr(), d_tensors=self._tensors.data_ptr(), reservoir=memory._h,
+                              d_slots=slots.data_ptr(), d_loss=loss.data_ptr(), learning_rate=self._learning_rate, beta1=0.9,
+                              beta2=0.999, eps=1e-8, ln_eps=1e-5)
+        job.widths[:len(widths)] = widths
+        return job
+
     def _train(self, network, optimizer, loss_fn, memory, batch_size, steps):
+        if self._learner == "fused":
+            return self._train_fused(network, memory, batch_size, steps)
         loss = None
         for _ in range(steps):
             batch = self._batch(memory, batch_size)
