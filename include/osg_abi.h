@@ -1227,6 +1227,23 @@ int osg_deep_cfr_learn(osg_ctx* ctx, const osg_deep_cfr_learn_job* jobs, int64_t
  *   tile height, tiles per batch, transposed copies resident (0 / 1), moments resident (0 / 1), LDS bytes, parameters.
  *   OSG_ERR_UNSUPPORTED with the planner's reason for a shape osg_deep_cfr_learn refuses. */
 int osg_deep_cfr_learn_plan(osg_ctx* ctx, int32_t n_linear, const int32_t* widths, int32_t batch, int32_t* plan);
+/* osg_deep_cfr_learn_wide: the same jobs, formulas and buffers for the networks one workgroup cannot hold (hidden widths
+ *   1..512, so the solver's default (256, 256); open_spiel_amd/csrc/osg_deep_cfr_learn_wide.hip, planned in
+ *   osg_adam_wide_plan.h).  A job is a group of G = ceil(batch / R) workgroups, workgroup g on rows [g R, (g + 1) R) of
+ *   every update's batch with their activations in LDS and the weights streamed from global memory in 16-row panels;
+ *   per update the workgroups write their gradients to the context's scratch, meet at a barrier of the job's group,
+ *   add the G partials of each parameter in ascending workgroup order and take the Adam step above on a slice each,
+ *   and meet again.  R and G follow from (widths, batch, the device's LDS per workgroup) alone; every sum has one
+ *   order and there are no floating-point atomics, so a job's bits depend neither on the other jobs nor on how the
+ *   updates are split into calls.  Does not wait.  Served: n_linear 2 or 3, hidden widths 1..512, S <= 256, A <= 16,
+ *   batch 1..1024; OSG_ERR_UNSUPPORTED for the rest, and for a call whose jobs' groups together exceed one workgroup
+ *   per compute unit (the groups must be resident at once; nothing is regrouped).  The barriers' waits are bounded: if
+ *   one runs out, the job's workgroups leave, its remaining d_loss entries are NaN and the NEXT call on the context
+ *   returns OSG_ERR_HIP.
+ * osg_deep_cfr_learn_wide_plan: plan [5] = rows per workgroup R, workgroups G, LDS bytes, scratch bytes of the job,
+ *   parameters; OSG_ERR_UNSUPPORTED with the planner's reason for a shape it refuses. */
+int osg_deep_cfr_learn_wide(osg_ctx* ctx, const osg_deep_cfr_learn_job* jobs, int64_t n_jobs);
+int osg_deep_cfr_learn_wide_plan(osg_ctx* ctx, int32_t n_linear, const int32_t* widths, int32_t batch, int64_t* plan);
 
 /* ---- multi-GPU exchange step ---------------------------------------------------
  * One process per GPU.  Units shard by global index with no data-path collective; the ONE exchange

@@ -48,22 +48,6 @@ struct AdamJob {   // one job as the kernel sees it (device pointers)
 
 typedef f4 Grads[kAdamMaxOwn];   // a wavefront's gradient tiles: tile t = wave + 8 s in accumulator s
 
-// D += A B, A stored row by row along the contraction (A[i][k] at a[i * sa + k]) and B row by row across it (B[k][j] at
-// b[k * sb + j]): dH = dY W without the transposed copy.  The B read collides (osg_adam_plan.h).  K is a multiple of 4.
-OSG_D f4 mma_mixed(const float* a, int sa, const float* b, int sb, int K, f4 acc) {
-  const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
-  const float* pa = a + i * sa + g;
-  const float* pb = b + g * sb + i;
-  for (int k = 0; k < K; k += 4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[k], pb[k * sb], acc, 0, 0, 0);
-  return acc;
-}
-
-OSG_D float sum16(float v) {   // one fixed tree over the 16 lanes of a row; each of them gets the sum
-#pragma unroll
-  for (int off = 8; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
-  return v;
-}
-
 // The flat parameters (network.parameters() order) into the padded LDS layout, zeros in the padding; the moments flat.
 OSG_D void load_params(float* lds, const AdamLayout& L, const AdamJob& j) {
   for (int l = 0; l < L.n_linear; ++l) {

@@ -4,7 +4,7 @@ the sampled advantages and the reservoir buffers on the device.
 The networks do not change while one player's traversals of one iteration run, so one forward pass over all infostate
 tensors — an [I, A] table of advantage-network outputs — stands for every per-node forward pass of the reference, and one
 TabularSolver.deep_cfr_traverse call does all num_traversals traversals and all reservoir appends of that step.  The
-networks, their losses and Adam are torch's (or, with learner="fused", one osg_deep_cfr_learn launch per training call);
+networks, their losses and Adam are torch's (or, with learner="fused" / "fused_wide", one launch per training call);
 a buffer row is (infostate index, iteration, values) and the tensor the
 reference stores with each row is looked up in TabularSolver.infostate_tensors() when a batch is formed.
 
@@ -123,6 +123,14 @@ def fused_plan(ctx, widths, batch):
     return dict(tile=out[0], tiles=out[1], transposed_resident=bool(out[2]), moments_resident=bool(out[3]), lds_bytes=out[4], parameters=out[5])
 
 
+def fused_wide_plan(ctx, widths, batch):
+    """What the wide fused learner's planner (csrc/osg_adam_wide_plan.h) chooses for a network [S, hidden ..., A] and a batch
+    on the context's device; OsgError with its reason for a shape it refuses."""
+    out = (C.c_int64 * 5)()
+    check(lib().osg_deep_cfr_learn_wide_plan(ctx._h, len(widths) - 1, (C.c_int32 * len(widths))(*widths), int(batch), out))
+    return dict(rows=out[0], workgroups=out[1], lds_bytes=out[2], scratch_bytes=out[3], parameters=out[4])
+
+
 class _FusedState:
     """One network's flat parameters (the module's parameters are views of them), Adam's moments and its step count."""
 
@@ -176,15 +184,18 @@ class DeepCFRSolver:
     updates of a _train call with ONE batched draw and ONE osg_deep_cfr_learn launch (csrc/osg_deep_cfr_learn.hip: a
     workgroup runs the network's Adam updates one after another with the parameters in LDS and the batch walked in
     tiles) on the very batches the torch learner would draw; it needs both batch sizes (at most 1024) and networks the
-    kernel's planner serves: one or two hidden layers of at most 128, what fits a workgroup's LDS."""
+    kernel's planner serves: one or two hidden layers of at most 128, what fits a workgroup's LDS.  learner="fused_wide"
+    is the same with osg_deep_cfr_learn_wide (csrc/osg_deep_cfr_learn_wide.hip): a group of workgroups per network, each on
+    its share of the batch rows with the weights streamed from global memory, two barriers per update; it serves hidden
+    widths up to 512 — the default (256, 256) — and the same batches (at most 1024).  All three see the same batches."""
 
     def __init__(self, ctx, game, policy_network_layers=(256, 256), advantage_network_layers=(128, 128), num_iterations=100,
                  num_traversals=20, learning_rate=1e-4, batch_size_advantage=None, batch_size_strategy=None,
                  memory_capacity=int(1e6), policy_network_train_steps=1, advantage_network_train_steps=1,
                  reinitialize_advantage_networks=True, device=None, seed=42, print_nash_convs=False, tabular=None, learner="torch"):
         self.ctx, self.game_string = ctx, game
-        if learner not in ("torch", "fused"):
-            raise ValueError("learner: 'torch' or 'fused'")
+        if learner not in ("torch", "fused", "fused_wide"):
+            raise ValueError("learner: 'torch', 'fused' or 'fused_wide'")
         self._learner = learner
         if device is not None and torch.device(device) != ctx.device:
             raise OsgError(f"DeepCFRSolver: the networks live on the context's device {ctx.device}")
@@ -222,7 +233,7 @@ class DeepCFRSolver:
         self._optimizer_policy = None
         self._optimizer_advantages = [None] * self._num_players
         self._fused, self.last_slots = {}, None
-        if learner == "fused":
+        if learner != "torch":
             self._init_fused(list(advantage_network_layers), list(policy_network_layers))
         self._reinitialize_policy_network()
         for p in range(self._num_players):
@@ -242,28 +253,29 @@ class DeepCFRSolver:
 
     def _init_fused(self, advantage_layers, policy_layers):
         """The fused learner's refusals, then every network's flat buffers."""
+        name, plan = self._learner, fused_plan if self._learner == "fused" else fused_wide_plan
         for what, batch in (("batch_size_advantage", self._batch_size_advantage), ("batch_size_strategy", self._batch_size_strategy)):
             if not batch:
-                raise ValueError(f"learner='fused' needs {what}: the whole-buffer batch is unbounded; use learner='torch'")
+                raise ValueError(f"learner='{name}' needs {what}: the whole-buffer batch is unbounded; use learner='torch'")
             if batch > FUSED_MAX_BATCH:
-                raise ValueError(f"learner='fused' serves batches of at most {FUSED_MAX_BATCH} rows, {what} is {batch}; use learner='torch'")
+                raise ValueError(f"learner='{name}' serves batches of at most {FUSED_MAX_BATCH} rows, {what} is {batch}; use learner='torch'")
         for what, layers, batch in (("advantage", advantage_layers, self._batch_size_advantage), ("policy", policy_layers, self._batch_size_strategy)):
             try:
-                fused_plan(self.ctx, [self._embedding_size] + layers + [self._num_actions], batch)
+                plan(self.ctx, [self._embedding_size] + layers + [self._num_actions], batch)
             except OsgError as e:
-                raise ValueError(f"learner='fused' does not serve the {what} network {tuple(layers)}: {e}; use learner='torch'") from None
+                raise ValueError(f"learner='{name}' does not serve the {what} network {tuple(layers)}: {e}; use learner='torch'") from None
         for network in self._advantage_networks + [self._policy_network]:
             self._fused[network] = _FusedState(network)
 
     def _reinitialize_advantage_network(self, player):
         self._advantage_networks[player].reset()
-        if self._learner == "fused":
+        if self._learner != "torch":
             return self._fused[self._advantage_networks[player]].clear()
         self._optimizer_advantages[player] = torch.optim.Adam(self._advantage_networks[player].parameters(), lr=self._learning_rate)
 
     def _reinitialize_policy_network(self):
         self._policy_network.reset()
-        if self._learner == "fused":
+        if self._learner != "torch":
             return self._fused[self._policy_network].clear()
         self._optimizer_policy = torch.optim.Adam(self._policy_network.parameters(), lr=self._learning_rate)
 
@@ -321,12 +333,13 @@ class DeepCFRSolver:
         state = self._fused[network]
         loss = torch.empty(steps, dtype=torch.float32, device=self.ctx.device)
         job = self._fused_job(network, memory, slots, loss, state.params, state.m, state.v, state.step)
-        check(lib().osg_deep_cfr_learn(self.ctx._h, C.byref(job), 1))
+        entry = lib().osg_deep_cfr_learn if self._learner == "fused" else lib().osg_deep_cfr_learn_wide
+        check(entry(self.ctx._h, C.byref(job), 1))
         state.step += steps
         return loss[-1].item()
 
     def _fused_job(self, network, memory, slots, loss, params, m, v, step0):
-        """The osg_deep_cfr_learn job of `network` on the rows slots [U, B] of `memory`: flat params, m, v (updated in place)
+        """The osg_deep_cfr_learn / osg_deep_cfr_learn_wide job of `network` on the rows slots [U, B] of `memory`: flat params, m, v (updated in place)
         after step0 updates, losses into loss [U]."""
         widths = [self._embedding_size] + [layer.out_features for layer in network.modules() if isinstance(layer, nn.Linear)]
         job = DeepCfrLearnJob(kind=1 if network is self._policy_network else 0, n_linear=len(widths) - 1, batch=slots.shape[1],
@@ -338,7 +351,7 @@ class DeepCFRSolver:
         return job
 
     def _train(self, network, optimizer, loss_fn, memory, batch_size, steps):
-        if self._learner == "fused":
+        if self._learner != "torch":
             return self._train_fused(network, memory, batch_size, steps)
         loss = None
         for _ in range(steps):
