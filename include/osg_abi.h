@@ -1245,6 +1245,31 @@ int osg_deep_cfr_learn_plan(osg_ctx* ctx, int32_t n_linear, const int32_t* width
 int osg_deep_cfr_learn_wide(osg_ctx* ctx, const osg_deep_cfr_learn_job* jobs, int64_t n_jobs);
 int osg_deep_cfr_learn_wide_plan(osg_ctx* ctx, int32_t n_linear, const int32_t* widths, int32_t batch, int64_t* plan);
 
+/* ---- fused policy-value network forward (alpha_zero_torch/model.cc, nn_model == "mlp"; vpevaluator.cc) -------------
+ * osg_vpnet_forward: the inference of the AlphaZero MLP for n states in ONE launch (open_spiel_amd/csrc/osg_vpnet.hip,
+ *   planned in osg_vpnet_plan.h), writing the two tensors osg_mcts_tree_advance reads.  The network: torso
+ *   Linear(obs_size, width) + ReLU and depth x (Linear(width, width) + ReLU); value head Linear(width, width) + ReLU,
+ *   Linear(width, 1), tanh; policy head Linear(width, width) + ReLU, Linear(width, actions), softmax over the LEGAL
+ *   actions (the reference sets illegal logits to -65536 first; here they take no part and get probability exactly 0,
+ *   as in osg_nfsp_learn).  d_params: flat fp32 in parameters() order — torso layers, value_linear_1, value_linear_2,
+ *   policy_linear_1, policy_linear_2, each weight [out, in] then its bias (alpha_zero.VPNetMLP keeps exactly this
+ *   tensor).  d_obs [n, obs_size] f32 as osg_observation writes it; d_legal_bits [n, mask_words] (bit a of word a / 32,
+ *   as osg_legal_mask writes it; actions <= 32 mask_words).  d_prior [n, actions] f64, 0 at illegal ids; d_value
+ *   [n, 2] f64 = {v, -v} (vpevaluator.cc:73-77).  A row without a legal action (a stale leaf) gets an all-zero prior
+ *   and its value, never a NaN.  A workgroup carries R rows through every layer with the activations in LDS and the
+ *   weights streamed from global memory in panels (v_mfma_f32_16x16x4_f32, fp32 throughout, f64 only at the store);
+ *   every sum has one order and there are no atomics: a row's bits depend on that row and the parameters alone, not
+ *   on n or on the other rows.  Runs on the context's stream; does not wait, allocate or read back, and can be
+ *   captured in a graph.  Served: obs_size 1..2048, width 1..512, depth 0..8, actions 1..384, n >= 1 (fewer than
+ *   2^31 workgroups); OSG_ERR_UNSUPPORTED with the planner's reason for the rest.
+ * osg_vpnet_plan: what the planner chooses on the context's device, without a launch: plan [8] = rows per workgroup R,
+ *   panel depth KC, LDS bytes, parameters, row tiles MR and column tiles NC per wavefront, panel rows, activation
+ *   stride; OSG_ERR_UNSUPPORTED with the planner's reason for a shape osg_vpnet_forward refuses. */
+int osg_vpnet_forward(osg_ctx* ctx, int32_t obs_size, int32_t width, int32_t depth, int32_t actions,
+                      const float* d_params, const float* d_obs, const int32_t* d_legal_bits,
+                      int32_t mask_words, int64_t n, double* d_prior, double* d_value);
+int osg_vpnet_plan(osg_ctx* ctx, int32_t obs_size, int32_t width, int32_t depth, int32_t actions, int64_t* plan);
+
 /* ---- multi-GPU exchange step ---------------------------------------------------
  * One process per GPU.  Units shard by global index with no data-path collective; the ONE exchange
  * on the path is external-sampling MCCFR's all-reduce(sum) of the regret / average-policy delta

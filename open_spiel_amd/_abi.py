@@ -340,6 +340,8 @@ SIGNATURES = {
     "osg_deep_cfr_learn_plan": (INT, [VP, C.c_int32, VP, C.c_int32, VP]),
     "osg_deep_cfr_learn_wide": (INT, [VP, VP, I64]),
     "osg_deep_cfr_learn_wide_plan": (INT, [VP, C.c_int32, VP, C.c_int32, VP]),
+    "osg_vpnet_forward": (INT, [VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, VP, VP, VP, C.c_int32, I64, VP, VP]),
+    "osg_vpnet_plan": (INT, [VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, VP]),
     "osg_cfr_infostate_key": (INT, [VP, I64, C.c_char_p, INT]),
     "osg_cfr_best_response_history_values": (INT, [VP, INT, VP, INT, VP]),
     "osg_cfr_tree_edges": (INT, [VP, VP, VP]),

@@ -6,7 +6,8 @@ targets p[a] = visits[a] ^ (1 / temperature) / sum and chooses the moves (drawn 
 moves of a game, the search's best action afterwards), and `osg_selfplay_commit` plays them, finds the games that ended
 and appends their trajectories — (state, policy, value = player 0's outcome) per ply — to a ring of training rows
 (`ReplayBuffer`: replay_buffer.py's append / sample).  Rows hold state records; observation tensors and legal masks are
-packed for the rows a learner samples.  The learner (model, loss, optimiser) is the user's.
+packed for the rows a learner samples.  `VPNetMLP` is the reference's MLP model with its losses; the optimiser and the
+training loop are the user's.
 
     buffer = ReplayBuffer(ctx, "connect_four", 1 << 20)
     actor = SelfPlay(StateBatch(ctx, "connect_four", 1 << 14), buffer, VPNetEvaluator(model), max_simulations=64,
@@ -36,6 +37,67 @@ NOISE_SALT = 0x6E6F6973655F7A31
 def noise_seed(seed):
     """The seed of SelfPlay(seed=seed)'s root noise: never the move draws' stream for the same (environment, ply)."""
     return (int(seed) ^ NOISE_SALT) & _MASK64
+
+
+class VPNetMLP(torch.nn.Module):
+    """alpha_zero_torch's nn_model == "mlp" (model.cc:216-263, 318-336, 391-396): torso Linear(observation_size, nn_width)
+    + ReLU and nn_depth x (Linear(nn_width, nn_width) + ReLU); value head Linear + ReLU, Linear(nn_width, 1), tanh;
+    policy head Linear + ReLU, Linear(nn_width, number_of_actions), softmax with the illegal logits at -65536.
+
+    Everything lives in ONE flat float32 parameter, `flat`, in the order the reference registers its modules — the torso
+    layers, value_linear_1, value_linear_2, policy_linear_1, policy_linear_2, each weight [out, in] then its bias; the
+    Linear weights and biases are views into it (`weights()`).  Training with torch (autograd, any optimizer) and
+    osg_vpnet_forward (mcts.VPNetEvaluator(model, forward="fused")) read the same memory: no copy between learner and
+    actor."""
+
+    def __init__(self, observation_size, number_of_actions, nn_width, nn_depth, weight_decay=1e-4):
+        super().__init__()
+        O, A, W, D = int(observation_size), int(number_of_actions), int(nn_width), int(nn_depth)
+        if min(O, A, W) < 1 or D < 0:
+            raise ValueError("VPNetMLP: observation_size, number_of_actions, nn_width >= 1 and nn_depth >= 0")
+        self.observation_size, self.number_of_actions, self.nn_width, self.nn_depth = O, A, W, D
+        self.weight_decay = float(weight_decay)
+        self.layer_shapes = [(W, O)] + [(W, W)] * D + [(W, W), (1, W), (W, W), (A, W)]   # [out, in]
+        self.flat = torch.nn.Parameter(torch.empty(sum(o * i + o for o, i in self.layer_shapes), dtype=torch.float32))
+        with torch.no_grad():   # nn.Linear's own initialisation, layer by layer
+            for w, b in self.weights():
+                torch.nn.init.kaiming_uniform_(w, a=5 ** 0.5)
+                bound = w.shape[1] ** -0.5
+                torch.nn.init.uniform_(b, -bound, bound)
+
+    def weights(self):
+        """[(weight [out, in], bias [out])] per Linear, views into `flat`."""
+        out, at = [], 0
+        for o, i in self.layer_shapes:
+            out.append((self.flat[at:at + o * i].view(o, i), self.flat[at + o * i:at + o * i + o]))
+            at += o * i + o
+        return out
+
+    def _forward(self, obs, legal):
+        """(value [B, 1], masked logits [B, A]) — ModelImpl::forward_."""
+        F = torch.nn.functional
+        layers = self.weights()
+        x = obs
+        for w, b in layers[:self.nn_depth + 1]:
+            x = torch.relu(F.linear(x, w, b))
+        (wv1, bv1), (wv2, bv2), (wp1, bp1), (wp2, bp2) = layers[self.nn_depth + 1:]
+        value = torch.tanh(F.linear(torch.relu(F.linear(x, wv1, bv1)), wv2, bv2))
+        logits = F.linear(torch.relu(F.linear(x, wp1, bp1)), wp2, bp2)
+        return value, torch.where(legal.bool(), logits, torch.full_like(logits, -65536.0))
+
+    def forward(self, obs, legal):
+        """(policy [B, A], value [B]) of observations [B, observation_size] f32 and legal masks [B, A] bool."""
+        value, logits = self._forward(obs, legal)
+        return torch.softmax(logits, 1), value.reshape(-1)
+
+    def losses(self, obs, legal, policy_targets, value_targets):
+        """(policy, value, l2) as ModelImpl::losses (model.cc:338-376): cross-entropy of the masked logits against the
+        policy targets, mean squared error of the value, weight_decay * sum(w ^ 2) / 2 over the weights (no biases)."""
+        value, logits = self._forward(obs, legal)
+        policy_loss = torch.mean(torch.sum(-policy_targets * torch.log_softmax(logits, 1), -1))
+        value_loss = torch.nn.functional.mse_loss(value.reshape(-1), value_targets.reshape(-1))
+        l2 = sum(self.weight_decay * torch.sum(torch.square(w)) / 2 for w, _ in self.weights())
+        return policy_loss, value_loss, l2
 
 
 class ReplayBuffer:

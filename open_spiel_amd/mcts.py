@@ -67,12 +67,53 @@ class VPNetEvaluator(BatchedEvaluator):
 
     joint = True   # every forward answers prior AND value of the same states: search() keeps the priors (flag 8)
 
-    def __init__(self, model):
+    def __init__(self, model, forward="torch"):
+        """forward="torch" calls `model`; forward="fused" takes an alpha_zero.VPNetMLP and answers with ONE launch of
+        osg_vpnet_forward on the model's flat parameter (csrc/osg_vpnet.hip), which writes the prior and {v, -v} as the
+        search reads them: observation pack, legal mask, forward — three launches a round."""
+        if forward not in ("torch", "fused"):
+            raise ValueError('VPNetEvaluator: forward is "torch" or "fused"')
         self.model = model
+        self.forward = forward
+        if forward == "fused":
+            from .alpha_zero import VPNetMLP
+            from .engine import Context
+            if not isinstance(model, VPNetMLP):
+                raise ValueError('VPNetEvaluator: forward="fused" serves alpha_zero.VPNetMLP; use forward="torch" for another model')
+            self._shape = (model.observation_size, model.nn_width, model.nn_depth, model.number_of_actions)
+            self._answers = {}   # n -> (prior [n, A] f64, value [n, 2] f64), written in place every round
+            ctx = Context(model.flat.device.index or 0)
+            try:
+                plan = (C.c_int64 * 8)()
+                if lib().osg_vpnet_plan(ctx._h, *self._shape, plan) != 0:
+                    raise ValueError(f'VPNetEvaluator: {lib().osg_last_error().decode()}; use forward="torch" for this model')
+                self.rows_per_workgroup = int(plan[0])
+            finally:
+                ctx.close()
+
+    def _evaluate_fused(self, leaf):
+        O, W, D, A = self._shape
+        if leaf.desc.obs_size != O or leaf.num_distinct_actions != A:
+            raise OsgError(f"VPNetEvaluator: the model is for observations of {O} and {A} actions, the game has "
+                           f"{leaf.desc.obs_size} and {leaf.num_distinct_actions}")
+        flat = self.model.flat
+        if flat.device != leaf.ctx.device or not flat.is_contiguous():
+            raise OsgError("VPNetEvaluator: the model's parameters are not on the leaves' device")
+        obs = leaf.observation_tensor(-1)
+        bits = leaf.legal_actions_mask_bits()
+        if leaf.n not in self._answers:
+            self._answers[leaf.n] = (torch.empty((leaf.n, A), dtype=torch.float64, device=flat.device),
+                                     torch.empty((leaf.n, 2), dtype=torch.float64, device=flat.device))
+        prior, value = self._answers[leaf.n]
+        check(lib().osg_vpnet_forward(leaf.ctx._h, O, W, D, A, flat.data_ptr(), obs.data_ptr(), bits.data_ptr(),
+                                      bits.shape[1], leaf.n, prior.data_ptr(), value.data_ptr()))
+        return prior, value
 
     def evaluate(self, leaf, want_prior, want_value):
         if leaf.num_players != 2:
             raise OsgError("VPNetEvaluator assumes a two-player zero-sum game (vpevaluator.cc:74)")
+        if self.forward == "fused":
+            return self._evaluate_fused(leaf)
         obs = leaf.observation_tensor(-1)
         legal = leaf.legal_actions_bool()
         with torch.no_grad():
