@@ -1269,6 +1269,41 @@ int osg_vpnet_forward(osg_ctx* ctx, int32_t obs_size, int32_t width, int32_t dep
                       const float* d_params, const float* d_obs, const int32_t* d_legal_bits,
                       int32_t mask_words, int64_t n, double* d_prior, double* d_value);
 int osg_vpnet_plan(osg_ctx* ctx, int32_t obs_size, int32_t width, int32_t depth, int32_t actions, int64_t* plan);
+/* osg_vpnet_learn: VPNetModel::Learn (alpha_zero_torch vpnet.cc:223-287) on the same network for `updates` sequential
+ *   Adam updates in ONE launch (open_spiel_amd/csrc/osg_vpnet_learn.hip, planned in osg_vpnet_learn_plan.h).  Update u
+ *   works on rows [u, :] of d_obs [updates, batch, obs_size], d_legal_bits [updates, batch, mask_words], d_policy
+ *   [updates, batch, actions] and d_value [updates, batch].  The loss is alpha_zero.VPNetMLP.losses:
+ *   policy = mean_b sum_legal -t_ba log_softmax(z_b)_a over the LEGAL logits (an illegal logit takes no part and gets
+ *   gradient exactly 0; the targets are expected to be 0 at illegal ids, as the replay ring writes them, and need not
+ *   sum to 1; a row without a legal action adds nothing here and still counts below), value = mean_b (tanh(y_b) - z_b)^2,
+ *   l2 = weight_decay * sum w^2 / 2 over the weights (no biases); the step is torch's Adam as under osg_deep_cfr_learn,
+ *   t = step0 + u + 1, on d_params, d_adam_m, d_adam_v (flat, the forward's order, in place; the caller keeps step0).
+ *   d_loss [updates, 3] f32 = {policy, value, l2} before each update's step.  A group of G = ceil(batch / 32)
+ *   workgroups: workgroup g carries rows [32 g, 32 g + 32) forward and backward (fp32, v_mfma_f32_16x16x4_f32, weights
+ *   streamed through LDS panels, saved activations in the context's scratch), writes its gradient to the scratch, the
+ *   group meets, each workgroup adds the G partials of its slice in ascending order and steps, the group meets again.
+ *   No floating-point atomics and one order per sum: the bits depend neither on the run nor on how the updates are
+ *   split into calls.  The waits are bounded as osg_deep_cfr_learn_wide's: if one runs out the remaining d_loss
+ *   entries are NaN and the NEXT call on the context returns OSG_ERR_HIP.  Runs on the context's stream; does not wait.
+ *   Served: the forward's shapes and batch 1..1024; OSG_ERR_UNSUPPORTED with the planner's reason for the rest, and
+ *   where G exceeds the device's compute units.
+ * osg_vpnet_learn_plan: plan [8] = rows per workgroup R, workgroups G, LDS bytes, scratch bytes, parameters, activation
+ *   buffers resident in LDS (1: the layer at hand; every saved activation lives in the scratch), saved activation
+ *   slots per workgroup, parameters per Adam slice. */
+typedef struct osg_vpnet_learn_job {
+  int32_t obs_size, width, depth, actions, batch, mask_words;
+  int64_t updates, step0;                       /* step0: updates already made (Adam's t = step0 + u + 1) */
+  float *d_params, *d_adam_m, *d_adam_v;        /* flat, VPNetMLP.flat's order, updated in place */
+  const float* d_obs;                           /* [updates, batch, obs_size] */
+  const int32_t* d_legal_bits;                  /* [updates, batch, mask_words], as osg_legal_mask writes them */
+  const float* d_policy;                        /* [updates, batch, actions] targets, 0 at illegal ids */
+  const float* d_value;                         /* [updates, batch] targets */
+  float* d_loss;                                /* [updates, 3]: policy, value, l2 — before the update's step */
+  double learning_rate, beta1, beta2, eps, weight_decay;
+} osg_vpnet_learn_job;
+int osg_vpnet_learn(osg_ctx* ctx, const osg_vpnet_learn_job* job);
+int osg_vpnet_learn_plan(osg_ctx* ctx, int32_t obs_size, int32_t width, int32_t depth, int32_t actions, int32_t batch,
+                         int64_t* plan);
 
 /* ---- multi-GPU exchange step ---------------------------------------------------
  * One process per GPU.  Units shard by global index with no data-path collective; the ONE exchange

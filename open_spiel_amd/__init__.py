@@ -46,7 +46,7 @@ def __getattr__(name):
     if name in ("ISMCTSBot", "ISMCTSFinalPolicyType", "ChildSelectionPolicy"):
         from . import ismcts
         return getattr(ismcts, name)
-    if name in ("SelfPlay", "ReplayBuffer", "TrainInput", "VPNetMLP"):
+    if name in ("SelfPlay", "ReplayBuffer", "TrainInput", "VPNetMLP", "VPNetLearner"):
         from . import alpha_zero
         return getattr(alpha_zero, name)
     if name in ("DeepCFRSolver", "ReservoirBuffer", "deep_cfr"):   # (ReservoirBuffer: Deep CFR's; AlphaZero's ring is ReplayBuffer)

@@ -79,6 +79,14 @@ class NfspLearnJob(C.Structure):
     ]
 
 
+class VpnetLearnJob(C.Structure):
+    """osg_vpnet_learn_job: one alpha_zero.VPNetMLP and its sequential Adam updates on plain device tensors."""
+    _fields_ = ([(name, C.c_int32) for name in ("obs_size", "width", "depth", "actions", "batch", "mask_words")] +
+                [("updates", C.c_int64), ("step0", C.c_int64)] +
+                [(name, C.c_void_p) for name in ("d_params", "d_adam_m", "d_adam_v", "d_obs", "d_legal_bits", "d_policy", "d_value", "d_loss")] +
+                [(name, C.c_double) for name in ("learning_rate", "beta1", "beta2", "eps", "weight_decay")])
+
+
 class DeepCfrLearnJob(C.Structure):
     """osg_deep_cfr_learn_job: one deep_cfr.MLP network and its sequential Adam updates (kind 0 advantage, 1 policy)."""
     _fields_ = [
@@ -342,6 +350,8 @@ SIGNATURES = {
     "osg_deep_cfr_learn_wide_plan": (INT, [VP, C.c_int32, VP, C.c_int32, VP]),
     "osg_vpnet_forward": (INT, [VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, VP, VP, VP, C.c_int32, I64, VP, VP]),
     "osg_vpnet_plan": (INT, [VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, VP]),
+    "osg_vpnet_learn": (INT, [VP, C.POINTER(VpnetLearnJob)]),
+    "osg_vpnet_learn_plan": (INT, [VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, VP]),
     "osg_cfr_infostate_key": (INT, [VP, I64, C.c_char_p, INT]),
     "osg_cfr_best_response_history_values": (INT, [VP, INT, VP, INT, VP]),
     "osg_cfr_tree_edges": (INT, [VP, VP, VP]),

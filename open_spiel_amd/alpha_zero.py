@@ -6,14 +6,16 @@ targets p[a] = visits[a] ^ (1 / temperature) / sum and chooses the moves (drawn 
 moves of a game, the search's best action afterwards), and `osg_selfplay_commit` plays them, finds the games that ended
 and appends their trajectories — (state, policy, value = player 0's outcome) per ply — to a ring of training rows
 (`ReplayBuffer`: replay_buffer.py's append / sample).  Rows hold state records; observation tensors and legal masks are
-packed for the rows a learner samples.  `VPNetMLP` is the reference's MLP model with its losses; the optimiser and the
-training loop are the user's.
+packed for the rows a learner samples.  `VPNetMLP` is the reference's MLP model with its losses, and `VPNetLearner` is
+VPNetModel::Learn on it: Adam on the three losses with torch, or all the updates of a call in one launch of
+osg_vpnet_learn on the very rows torch would draw; only the loop around actor and learner is the user's.
 
     buffer = ReplayBuffer(ctx, "connect_four", 1 << 20)
     actor = SelfPlay(StateBatch(ctx, "connect_four", 1 << 14), buffer, VPNetEvaluator(model), max_simulations=64,
                      uct_c=1.4, dirichlet_alpha=1.0, dirichlet_epsilon=0.25, seed=1)
     actor.run(1 << 16)
     batch = buffer.sample(1024, seed=step)       # TrainInput(observation, legals_mask, policy, value)
+    losses = VPNetLearner(ctx, model, 1e-3, learner="fused").learn(buffer, 1024, 64, seed=step)   # [64, 3] on the device
 """
 import collections
 import ctypes as C
@@ -304,3 +306,95 @@ class SelfPlay:
             self.step()
             taken += 1
         return taken
+
+
+def _mask_bits(legal):
+    """[n, A] bool -> [n, ceil(A / 32)] i32 with bit a of word a / 32, as osg_legal_mask writes them."""
+    n, A = legal.shape
+    words = (A + 31) // 32
+    padded = torch.zeros((n, 32 * words), dtype=torch.int64, device=legal.device)
+    padded[:, :A] = legal
+    bits = (padded.reshape(n, words, 32) << torch.arange(32, device=legal.device)).sum(2)
+    return torch.where(bits >= 2 ** 31, bits - 2 ** 32, bits).to(torch.int32).contiguous()
+
+
+class VPNetLearner:
+    """VPNetModel::Learn (alpha_zero_torch vpnet.cc:223-287) on a VPNetMLP: Adam on policy + value + l2 of `model.losses`.
+
+    learner="torch" is torch.optim.Adam([model.flat]), one update at a time; it works on a CPU model too.
+    learner="fused" takes all the updates of a call in ONE launch of osg_vpnet_learn (csrc/osg_vpnet_learn.hip): it keeps
+    Adam's m, v and the step count itself and updates `model.flat` in place, so a mcts.VPNetEvaluator(model,
+    forward="fused") sees the new weights without a copy.  Both learners draw the same rows for the same seed."""
+
+    def __init__(self, ctx, model, learning_rate, learner="torch", betas=(0.9, 0.999), eps=1e-8):
+        if learner not in ("torch", "fused"):
+            raise ValueError("learner: 'torch' or 'fused'")
+        if not isinstance(model, VPNetMLP):
+            raise ValueError("VPNetLearner serves alpha_zero.VPNetMLP")
+        self.ctx, self.model, self.learner = ctx, model, learner
+        self.learning_rate, self.betas, self.eps = float(learning_rate), (float(betas[0]), float(betas[1])), float(eps)
+        self.steps = 0
+        if learner == "torch":
+            self._opt = torch.optim.Adam([model.flat], lr=self.learning_rate, betas=self.betas, eps=self.eps)
+        else:
+            if ctx is None or model.flat.device != ctx.device or not model.flat.is_contiguous():
+                raise ValueError("learner='fused' needs the model's parameters on the context's device; use learner='torch'")
+            self.m, self.v = torch.zeros_like(model.flat.data), torch.zeros_like(model.flat.data)
+            self.plan(1)   # (the network's own limits, before any batch is known)
+
+    def plan(self, batch_size):
+        """What the fused learner's planner (csrc/osg_vpnet_learn_plan.h) chooses for this network and a batch."""
+        m = self.model
+        out = (C.c_int64 * 8)()
+        if lib().osg_vpnet_learn_plan(self.ctx._h, m.observation_size, m.nn_width, m.nn_depth, m.number_of_actions, int(batch_size), out) != 0:
+            raise ValueError(f"learner='fused' does not serve this network and batch: {lib().osg_last_error().decode()}; use learner='torch'")
+        keys = ("rows", "workgroups", "lds_bytes", "scratch_bytes", "parameters", "resident", "saved_slots", "slice")
+        return dict(zip(keys, (int(x) for x in out)))
+
+    def _torch_update(self, obs, legal, policy, value):
+        self._opt.zero_grad(set_to_none=True)
+        losses = self.model.losses(obs, legal, policy, value)
+        (losses[0] + losses[1] + losses[2]).backward()
+        self._opt.step()
+        self.steps += 1
+        return torch.stack([l.detach() for l in losses])
+
+    def _fused(self, obs, bits, policy, value, batch_size, updates):
+        """osg_vpnet_learn on obs [U B, O] f32, bits [U B, words] i32, policy [U B, A] f32, value [U B] f32."""
+        m = self.model
+        self.plan(batch_size)
+        obs, bits = obs.to(torch.float32).contiguous(), bits.contiguous()
+        policy, value = policy.to(torch.float32).contiguous(), value.to(torch.float32).contiguous()
+        if (obs.shape != (updates * batch_size, m.observation_size) or policy.shape != (updates * batch_size, m.number_of_actions) or
+                value.numel() != updates * batch_size or bits.shape[0] != updates * batch_size):
+            raise OsgError("VPNetLearner: the batch does not fit the model")
+        loss = torch.empty((updates, 3), dtype=torch.float32, device=m.flat.device)
+        job = _abi.VpnetLearnJob(m.observation_size, m.nn_width, m.nn_depth, m.number_of_actions, batch_size, bits.shape[1], updates,
+                                 self.steps, m.flat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), obs.data_ptr(), bits.data_ptr(),
+                                 policy.data_ptr(), value.data_ptr(), loss.data_ptr(), self.learning_rate, self.betas[0], self.betas[1],
+                                 self.eps, m.weight_decay)
+        check(lib().osg_vpnet_learn(self.ctx._h, C.byref(job)))
+        self._keep = (obs, bits, policy, value)   # (the launch does not wait: its inputs live until the next call)
+        self.steps += updates
+        return loss
+
+    def step(self, train_input):
+        """One update on a TrainInput; returns its (policy, value, l2) losses, before the step, as a tensor [3]."""
+        obs, legal, policy, value = train_input
+        if self.learner == "torch":
+            return self._torch_update(obs, legal, policy, value)
+        return self._fused(obs, _mask_bits(legal.bool()), policy, value, obs.shape[0], 1)[0]
+
+    def learn(self, buffer, batch_size, updates, seed):
+        """`updates` updates on batches of `batch_size` rows of a ReplayBuffer: update u's rows are
+        buffer.sample(batch_size, seed, index_offset=u * batch_size).  Returns the losses [updates, 3] on the device."""
+        batch_size, updates = int(batch_size), int(updates)
+        if self.learner == "fused":
+            self.plan(batch_size)   # (refuse before drawing)
+        _, states, policy, value = buffer.sample_rows(updates * batch_size, seed)
+        obs = states.observation_tensor(-1)
+        if self.learner == "fused":
+            return self._fused(obs, states.legal_actions_mask_bits(), policy, value, batch_size, updates)
+        legal = states.legal_actions_bool()
+        rows = [slice(u * batch_size, (u + 1) * batch_size) for u in range(updates)]
+        return torch.stack([self._torch_update(obs[r], legal[r], policy[r], value[r]) for r in rows])

@@ -155,7 +155,7 @@ struct osg_ctx {
                                                    // histogram / bucket offsets, then the root order [roots]
   osg::DeviceArray<unsigned char> d_ismcts;        // IS-MCTS node tables, hashes and root samples; kept for osg_ismcts_tree_*
   osg::IsmctsKept ismcts;
-  osg::PinnedArray<unsigned int> h_learn_err;      // mapped: raised by k_deep_cfr_train_wide when a group barrier times out
+  osg::PinnedArray<unsigned int> h_learn_err;      // mapped: raised by k_deep_cfr_train_wide / k_vpnet_learn when a group barrier times out
   int num_cus = 0;
   // Lifetime: the creator holds one reference, every batch / solver / communicator made on the context
   // another; osg_ctx_destroy drops the creator's, and the device resources go with the last one, so a

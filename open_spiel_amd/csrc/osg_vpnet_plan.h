@@ -80,6 +80,17 @@ struct VpPlan {
   size_t lds_bytes = 0;
 };
 
+// Where every Linear of a plan whose shape is set starts in the flat parameters (osg_vpnet_learn_plan.h calls it too).
+inline void vp_param_offsets(VpPlan& p) {
+  const int W = p.width;
+  int at_param = 0;
+  const auto linear = [&at_param](int out, int in) { const int o = at_param; at_param += out * in + out; return o; };
+  p.torso[0] = linear(W, p.obs);
+  for (int l = 1; l <= p.depth; ++l) p.torso[l] = linear(W, W);
+  p.v1 = linear(W, W); p.v2 = linear(1, W); p.p1 = linear(W, W); p.p2 = linear(p.actions, W);
+  p.param_count = at_param;
+}
+
 inline VpPlan plan_vpnet(const VpShape& s, size_t lds_limit_bytes) {
   VpPlan p;
   const auto refuse = [&p](const char* why) { p.ok = false; p.why = why; return p; };
@@ -89,13 +100,7 @@ inline VpPlan plan_vpnet(const VpShape& s, size_t lds_limit_bytes) {
   if (s.actions < 1 || s.actions > kVpMaxActions) return refuse("1 to 384 actions are served");
   p.obs = s.obs; p.width = s.width; p.depth = s.depth; p.actions = s.actions;
   p.wp = vp_pad(s.width); p.ap = vp_pad(s.actions);
-  const int W = s.width;
-  int at_param = 0;
-  const auto linear = [&at_param](int out, int in) { const int o = at_param; at_param += out * in + out; return o; };
-  p.torso[0] = linear(W, s.obs);
-  for (int l = 1; l <= s.depth; ++l) p.torso[l] = linear(W, W);
-  p.v1 = linear(W, W); p.v2 = linear(1, W); p.p1 = linear(W, W); p.p2 = linear(s.actions, W);
-  p.param_count = at_param;
+  vp_param_offsets(p);
   p.act_stride = p.wp + 4;
   p.logits_stride = p.ap + 4;
   size_t at = 0;

@@ -2,7 +2,11 @@
 forward of the same alpha_zero.VPNetMLP: microseconds per evaluate() — observation pack, legal mask, forward, the answers
 as the search reads them — and per round of mcts._search_joint, the two paths alternating in one run (the median of the
 pairs).  Shapes: the connect_four net 126-256-256 at 2^10, 2^13 and 2^16 states and hex(9) at 729-256-256.  Writes
-profiles/vpnet_probe.txt (or the file named as the first argument)."""
+profiles/vpnet_probe.txt (or the file named as the first argument).
+
+`probe_vpnet.py learn [file]` times the two learners of alpha_zero.VPNetLearner the same way: one learn(buffer, batch, 64,
+seed) call — the draw, the observation and mask pack, 64 updates — of VPNetMLP(126, 7, 256, 1) at batch 256 and 1024, per
+update; writes profiles/vpnet_learn_probe.txt."""
 import os
 import sys
 import time
@@ -67,5 +71,40 @@ def main(path):
         f.write("\n".join(lines) + "\n")
 
 
+def main_learn(path):
+    ctx = osa.Context(0)
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    updates = 64
+    say(f"tools/probe_vpnet.py learn on {torch.cuda.get_device_name(0)}: alternating pairs, median of {PAIRS}; {updates} updates per call")
+    buf = alpha_zero.ReplayBuffer(ctx, "connect_four", 1 << 16)
+    alpha_zero.SelfPlay(osa.StateBatch(ctx, "connect_four", 1024), buf, mcts.RolloutEvaluator(), max_simulations=8, uct_c=1.4, seed=1).run(1 << 14)
+    for batch in (256, 1024):
+        learners = {}
+        for name in ("torch", "fused"):
+            torch.manual_seed(0)
+            learners[name] = alpha_zero.VPNetLearner(ctx, alpha_zero.VPNetMLP(126, 7, 256, 1).to(ctx.device), 1e-3, learner=name)
+        got = {k: [] for k in learners}
+        for pair in range(PAIRS):
+            for name, learner in learners.items():
+                got[name].append(timed(ctx, lambda: learner.learn(buf, batch, updates, seed=pair), 3) / updates)
+        med = {k: sorted(v)[len(v) // 2] for k, v in got.items()}
+        plan = learners["fused"].plan(batch)
+        flop = 6.0 * batch * sum(o * i for o, i in learners["fused"].model.layer_shapes)
+        say(f"connect_four net 126-256-(1)-7, batch {batch} (R = {plan['rows']}, G = {plan['workgroups']}, {flop / 1e9:.2f} GFLOP an update):")
+        for k in learners:
+            say(f"  {k:5s} {med[k] * 1e6:8.1f} us per update (min {min(got[k]) * 1e6:.1f}, max {max(got[k]) * 1e6:.1f}; {flop / med[k] / 1e12:.2f} TFLOP/s end to end)")
+        say(f"  torch / fused = {med['torch'] / med['fused']:.2f}")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "learn":
+        main_learn(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "vpnet_learn_probe.txt"))
+        sys.exit(0)
     main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "vpnet_probe.txt"))
